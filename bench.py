@@ -8,8 +8,22 @@ into the device framebuffer, then the frame gathered to rank 0 (RCCL gather for 
 Scene buffers and the framebuffer are resident in HBM before the timed region.
 
     python bench.py [--gpus N --steps K --warmup W] [--config c1|c2|c3|c4|c5|mesh] [--rough R]
-                    [--scaling weak|strong] [--deadline S]
+                    [--scaling weak|strong] [--deadline S] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
+
+A plain run does what its headline figure needs and no more: upload, AUTO trials, W warm-up
+steps, K timed steps, the line.  ``--full`` adds the legs that take runs of their own: the
+counting launch behind `roofline.reference_equivalent_bytes` (``--no-count`` drops it), rank 0's
+`self_check` (``--no-check``) and the `cpu_baseline` (``--no-cpu-baseline``); without it those
+fields are empty (0 bytes, null, null).  The PMC-derived roofline fields need no run (a record
+on file, the timed steps' own HIP events) and are in every line.
+
+``--dump-outputs DIR`` writes, after the timed steps, the frame the last timed step's gather
+returned on rank 0 (the sum of every pass since the warm-up began, [H, W, 3] float32) as
+``DIR/frame.npy`` (c3: ``DIR/frame_rough<R>.npy`` per point).  The files hold at most 64 MB in
+all: a frame above its share (c5's 4K frame, the c3 sweep's five) is written as a fixed, seeded
+sample of whole rows, in row order (`dump_rows`).  Scene, camera and RNG seeds are functions of
+the arguments alone, so two builds run with the same arguments can be compared file for file.
 
 Launch: with ``--gpus N > 1`` and no launcher (``WORLD_SIZE`` unset) the process starts N
 child ranks itself (one process per GPU, RANK/LOCAL_RANK/WORLD_SIZE/MASTER_* set, rendezvous
@@ -142,9 +156,15 @@ def parse(argv=None):
     ap.add_argument("--light", type=float, default=1.2)
     ap.add_argument("--band-rows", type=int, default=8)
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline sample budget (s)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-count", action="store_true", help="skip the reference-byte counting launch")
-    ap.add_argument("--no-check", action="store_true", help="skip rank 0's post-run self check")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs that take runs of their own: the reference-byte counting launch, "
+                         "rank 0's self check and the CPU baseline (each has its --no-... switch)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's gathered frame (rank 0) to DIR/frame.npy, float32, at most "
+                         "64 MB in all (a larger frame: a fixed seeded sample of its rows)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-count", action="store_true", help="--full: skip the reference-byte counting launch")
+    ap.add_argument("--no-check", action="store_true", help="--full: skip rank 0's post-run self check")
     ap.add_argument("--scaling", choices=("weak", "strong"), default=None,
                     help="c2/c3: strong (default: one fixed frame split over the N GPUs) or weak (one C2 frame "
                          "of samples per GPU)")
@@ -158,6 +178,10 @@ def parse(argv=None):
     a = ap.parse_args(argv)
     if a.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not a.full:   # a plain run: the timed steps and the line only
+        a.no_cpu_baseline = a.no_count = a.no_check = True
     if a.deadline is None:
         n_pts = 1 if a.config != "c3" or a.rough is not None else len(C3_ROUGHNESS)
         a.deadline = 600.0 + 30.0 * (a.steps + a.warmup) * n_pts
@@ -565,6 +589,24 @@ def self_check(args, scene, ipv, iv, frame: torch.Tensor, n_calls: int, S: int, 
     return {"rows": len(rows), "passes": int(n), "bit_equal": diff == 0, "channels_differing": diff}
 
 
+DUMP_BYTES = 64_000_000   # --dump-outputs: the files' arrays hold at most this much in all
+
+
+def dump_rows(H: int, W: int, n_points: int = 1):
+    """--dump-outputs: the rows of an [H, W, 3] float32 frame that are written, None for all of
+    them.  Each of the run's `n_points` frames gets an equal share of DUMP_BYTES; a frame above
+    its share is sampled: as many whole rows as fit, drawn without replacement by a generator
+    seeded with 0 (the same rows for the same H, W and n_points), in increasing order."""
+    fit = DUMP_BYTES // n_points // (W * 3 * 4)
+    if fit >= H:
+        return None
+    return np.sort(np.random.default_rng(0).choice(H, size=int(fit), replace=False))
+
+
+def dump_name(rough=None) -> str:
+    return "frame.npy" if rough is None else f"frame_rough{rough:g}.npy"
+
+
 def roofline(workload: str, sha: str, avg_trace_ms: float, ref_bytes: float, bytes_per_sample: float, world: int,
              launches: int = 1, bound: str = "valu", sched=None):
     """`avg_trace_ms` is one timed call's kernel time, summed over its `launches` sub-launches; a
@@ -707,6 +749,10 @@ def run_point(args, sr, rough, S, world, barrier, stat_dev, wd):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
     gather_ms = float(np.mean([a.elapsed_time(b) for a, b in gather_ev]))
+    output = None   # --dump-outputs: the last timed step's frame (a buffer the next gather reuses)
+    if args.dump_outputs is not None and args.rank == 0:
+        rows = dump_rows(H, W, len(args.rough_points))
+        output = (frame if rows is None else frame[torch.as_tensor(rows, device=frame.device)]).cpu().numpy()
 
     # reference-equivalent bytes of one launch: the counting build over the first timed pass range
     ev_local = np.zeros(len(mcpt.EVENT_NAMES), np.uint64)
@@ -733,7 +779,7 @@ def run_point(args, sr, rough, S, world, barrier, stat_dev, wd):
         check = self_check(args, scene, ipv, iv, frame, args.warmup + args.steps, S, args.local_rank)
     return dict(rough=rough, elapsed=elapsed, sched=sched, launches=launches, gather_ms=gather_ms, avg_trace_ms=avg_trace_ms,
                 avg_span_ms=avg_span_ms,
-                avg_combine_ms=avg_combine_ms, allstats=allstats, check=check, scene=scene,
+                avg_combine_ms=avg_combine_ms, allstats=allstats, check=check, scene=scene, output=output,
                 events={n: int(v) for n, v in zip(mcpt.EVENT_NAMES, ev_local)})
 
 
@@ -847,6 +893,10 @@ def main():
     points = [run_point(args, sr, rough, S, world, barrier, stat_dev, wd) for rough in args.rough_points]
 
     if rank == 0:
+        if args.dump_outputs is not None:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for pt in points:
+                np.save(os.path.join(args.dump_outputs, dump_name(pt["rough"])), pt["output"])
         sha = lib_sha256()
         samples_per_step = float(W) * H * S
         total_s = sum(pt["elapsed"] for pt in points)
@@ -896,6 +946,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": round(total_s / n_steps * 1e3, 3),
             "higher_is_better": True,
             "scaling": args.scaling,

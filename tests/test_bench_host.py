@@ -302,6 +302,41 @@ def test_deadline_default_and_off():
     assert bench.parse(["--deadline", "42"]).deadline == 42.0
 
 
+def test_plain_run_skips_the_legs_with_runs_of_their_own():
+    """A plain run times its steps and prints the line; the counting launch, the self check and
+    the CPU baseline run under --full only, each still with its own switch."""
+    a = bench.parse(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert (a.steps, a.warmup, a.full) == (3, 1, False)
+    assert a.no_count and a.no_check and a.no_cpu_baseline and a.dump_outputs is None
+    a = bench.parse(["--full"])
+    assert a.full and not (a.no_count or a.no_check or a.no_cpu_baseline)
+    a = bench.parse(["--full", "--no-check"])
+    assert a.no_check and not (a.no_count or a.no_cpu_baseline)
+    assert bench.parse(["--dump-outputs", "d"]).dump_outputs == "d"
+    for argv in (["--steps", "0"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            bench.parse(argv)
+
+
+def test_dump_rows_fit_the_budget():
+    """--dump-outputs: a frame within its share of the 64 MB is written whole; above it, a fixed
+    seeded sample of whole rows, the same from run to run, every point of a sweep sharing the budget."""
+    assert bench.DUMP_BYTES <= 64_000_000
+    assert bench.dump_rows(1080, 1920) is None and bench.dump_rows(256, 256) is None
+    for name, c in bench.CONFIGS.items():
+        n = len(c.get("rough_sweep", (None,)))
+        H, W = c["height"], c["width"]
+        rows = bench.dump_rows(H, W, n)
+        kept = H if rows is None else len(rows)
+        assert 0 < n * kept * W * 3 * 4 <= bench.DUMP_BYTES, name
+        if rows is not None:
+            assert (np.diff(rows) > 0).all() and 0 <= rows[0] and rows[-1] < H
+            assert np.array_equal(rows, bench.dump_rows(H, W, n))
+            assert (kept + 1) * n * W * 3 * 4 > bench.DUMP_BYTES      # as many rows as fit
+    assert bench.dump_rows(2160, 3840) is not None and bench.dump_rows(1080, 1920, 5) is not None
+    assert bench.dump_name() == "frame.npy" and bench.dump_name(0.5) == "frame_rough0.5.npy"
+
+
 def test_drill_rank_deadline_under_torchrun():
     """Launched by torch.distributed.run (the driver's N-GPU command), a rank past --deadline
     names its phase and exits 124 by itself."""

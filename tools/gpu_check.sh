@@ -37,27 +37,27 @@ if has pmcall "${FLAGS[@]}"; then   # PMC records for the C3 line's dominant poi
   cp $O/pmc_records.json profiles/pmc_records.json || exit $?
 fi
 has nobench "${FLAGS[@]}" && exit 0
-timeout -k 10 400 python bench.py > $O/bench.json 2> $O/bench.err && echo "bench ok" && cat $O/bench.json &&
-timeout -k 10 400 python bench.py --config c4 > $O/bench_c4.json 2> $O/bench_c4.err &&
+timeout -k 10 400 python bench.py --full > $O/bench.json 2> $O/bench.err && echo "bench ok" && cat $O/bench.json &&
+timeout -k 10 400 python bench.py --full --config c4 > $O/bench_c4.json 2> $O/bench_c4.err &&
 echo "bench c4 ok" && cat $O/bench_c4.json &&
-timeout -k 10 400 python bench.py --config mesh > $O/bench_mesh.json 2> $O/bench_mesh.err &&
+timeout -k 10 400 python bench.py --full --config mesh > $O/bench_mesh.json 2> $O/bench_mesh.err &&
 echo "bench mesh ok" && cat $O/bench_mesh.json &&
-timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- python3 bench.py --no-cpu-baseline > $O/prof_bench.json 2> $O/prof.err && echo "prof ok" &&
-timeout -k 10 200 python bench.py --config c1 > $O/bench_c1.json 2> $O/bench_c1.err && echo "bench c1 ok" &&
-timeout -k 10 400 python bench.py --config c3 > $O/bench_c3.json 2> $O/bench_c3.err && echo "bench c3 ok" &&
-timeout -k 10 400 python bench.py --config c5 > $O/bench_c5.json 2> $O/bench_c5.err && echo "bench c5 ok" || exit $?
+timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- python3 bench.py --full --no-cpu-baseline > $O/prof_bench.json 2> $O/prof.err && echo "prof ok" &&
+timeout -k 10 200 python bench.py --full --config c1 > $O/bench_c1.json 2> $O/bench_c1.err && echo "bench c1 ok" &&
+timeout -k 10 400 python bench.py --full --config c3 > $O/bench_c3.json 2> $O/bench_c3.err && echo "bench c3 ok" &&
+timeout -k 10 400 python bench.py --full --config c5 > $O/bench_c5.json 2> $O/bench_c5.err && echo "bench c5 ok" || exit $?
 has full "${FLAGS[@]}" || exit 0
 # N>1 path rehearsal on the one GPU: the ranks share cuda:0 with gloo collectives (RCCL needs
 # one GPU per rank; the driver runs the real N>1 nccl bench on an 8-GPU node)
-MCPT_DIST_BACKEND=gloo timeout -k 10 300 python bench.py --gpus 2 --steps 2 --warmup 1 --no-cpu-baseline \
+MCPT_DIST_BACKEND=gloo timeout -k 10 300 python bench.py --full --gpus 2 --steps 2 --warmup 1 --no-cpu-baseline \
   > $O/bench_gloo2.json 2> $O/bench_gloo2.err && echo "gloo2 ok" &&
-MCPT_DIST_BACKEND=gloo timeout -k 10 300 python bench.py --gpus 4 --steps 2 --warmup 1 --no-cpu-baseline \
+MCPT_DIST_BACKEND=gloo timeout -k 10 300 python bench.py --full --gpus 4 --steps 2 --warmup 1 --no-cpu-baseline \
   > $O/bench_gloo4.json 2> $O/bench_gloo4.err && echo "gloo4 ok" &&
-MCPT_DIST_BACKEND=gloo timeout -k 10 300 python bench.py --gpus 2 --steps 2 --warmup 1 --no-cpu-baseline --config c4 \
+MCPT_DIST_BACKEND=gloo timeout -k 10 300 python bench.py --full --gpus 2 --steps 2 --warmup 1 --no-cpu-baseline --config c4 \
   > $O/bench_gloo2_c4.json 2> $O/bench_gloo2_c4.err && echo "gloo2 c4 ok" &&
-MCPT_DIST_BACKEND=gloo timeout -k 10 300 python bench.py --gpus 8 --steps 2 --warmup 1 --no-cpu-baseline \
+MCPT_DIST_BACKEND=gloo timeout -k 10 300 python bench.py --full --gpus 8 --steps 2 --warmup 1 --no-cpu-baseline \
   > $O/bench_gloo8.json 2> $O/bench_gloo8.err && echo "gloo8 ok" &&
-MCPT_DIST_BACKEND=gloo timeout -k 10 300 python bench.py --gpus 8 --steps 2 --warmup 1 --no-cpu-baseline --scaling strong \
+MCPT_DIST_BACKEND=gloo timeout -k 10 300 python bench.py --full --gpus 8 --steps 2 --warmup 1 --no-cpu-baseline --scaling strong \
   > $O/bench_gloo8_strong.json 2> $O/bench_gloo8_strong.err && echo "gloo8 strong ok" &&
 { timeout -k 10 120 python bench.py --gpus 2 --steps 1 --warmup 0 --no-cpu-baseline > $O/bench_nccl2_1gpu.json \
     2> $O/bench_nccl2_1gpu.err; rc=$?; echo "nccl2 on one GPU: exit $rc (expected non-zero, no line)";

@@ -21,7 +21,7 @@ cp $O/bench.json ${P}_bench.json
 [ -f $O/bench_nccl2_1gpu.err ] && cp $O/bench_nccl2_1gpu.err ${P}_bench_nccl2_on_1gpu_refused.txt
 cp $O/prof/run_kernel_stats.csv ${P}_kernel_stats.csv
 python tools/trace_summary.py $O/prof/run_kernel_trace.csv \
-  "$R $V: rocprofv3 --kernel-trace --stats -- python3 bench.py --no-cpu-baseline" > ${P}_kernel_trace_summary.txt
+  "$R $V: rocprofv3 --kernel-trace --stats -- python3 bench.py --full --no-cpu-baseline" > ${P}_kernel_trace_summary.txt
 # (raw counter CSVs are not kept: since round 5 the records below carry every counter per launch)
 [ -f $O/pmc_records.json ] && cp $O/pmc_records.json ${P}_pmc_records.json && cp $O/pmc_records.json profiles/pmc_records.json
 [ -f $O/pytest_gpu.log ] && cp $O/pytest_gpu.log ${P}_pytest_gpu.log
