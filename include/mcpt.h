@@ -34,6 +34,7 @@ enum mcpt_status {
   MCPT_ERR_HIP = -4,         /* a HIP runtime call failed (no GPU, launch failure ...) */
   MCPT_ERR_NOT_FINALIZED = -5,
   MCPT_ERR_BAD_SCENE = -6,
+  MCPT_ERR_NO_GUIDES = -7,   /* mcpt_denoise / mcpt_read_guides without current guide buffers */
 };
 
 /* integrator variants: the SrcLoader list of MontecarloGPU/montecarlo.cpp:27 */
@@ -300,6 +301,45 @@ typedef struct mcpt_hit {
 } mcpt_hit;
 int mcpt_trace(mcpt_ctx* ctx, const float* origins, const float* dirs, int n, int any_hit, int prim,
                mcpt_hit* out);
+
+/* Guide buffers (AOVs) and the edge-avoiding a-trous denoiser (no reference
+ * equivalent: fs_frag only averages).  Device memory: 80 B per local pixel (guides 32, albedo 16,
+ * two filter buffers 16 each), allocated by the first of these calls after a mcpt_set_target* and
+ * freed by the next mcpt_set_target* / mcpt_destroy.  No render call does any work for them.
+ *
+ * mcpt_render_guides: per local pixel the primary hit of its camera ray (the render kernel's ray:
+ * invPV, invV as mcpt_render takes them) — normal, world position, distance, primitive key, and
+ * the hit primitive's colour.  Works on any target, row shards included.  Asynchronous on the
+ * context's stream.  mcpt_set_target*, mcpt_upload_scene, mcpt_upload_meshes and
+ * mcpt_set_flat_face invalidate the guides (MCPT_ERR_NO_GUIDES until rendered again).
+ * mcpt_read_guides: guide8 = n_local x 8 f32 {N.xyz, key as int32 bits, P.xyz, dist} with key =
+ * shape << 28 | primitive index (a miss: key -1, N = P = 0, dist = FLT_MAX); albedo4 = n_local x 4
+ * f32 rgba (0 on a miss).  Either pointer may be NULL.  Synchronizes. */
+int mcpt_render_guides(mcpt_ctx* ctx, const float* invPV, const float* invV);
+int mcpt_read_guides(mcpt_ctx* ctx, float* guide8, float* albedo4);
+/* `iterations` (0..8) a-trous passes (tap spacing 1, 2, 4, ...) over accum / pass_count, guided by
+ * the guide buffers; the weights' arithmetic is fixed bit for bit, 0 iterations
+ * give accum / pass_count itself.  The accumulator and the pass count are not touched, so a
+ * progressive render goes on afterwards.  Needs a full-frame target in row order (local row i =
+ * global row i; after mcpt_gather_rows for sharded renders) and pass_count > 0, positive finite
+ * sigmas (else MCPT_ERR_INVALID_ARG), and current guides (else MCPT_ERR_NO_GUIDES).  Asynchronous,
+ * ordered after the queued renders.  sigma_color: colour distance (in radiance units) at which a
+ * tap's weight falls to 1/4 in the first iteration (halved each iteration); sigma_plane: the same
+ * for a tap's distance from the centre's tangent plane, in world units per pixel of tap spacing.
+ * Env MCPT_DENOISE_NAIVE=1: every tap from global memory; =0: steps 1 and 2 from LDS tiles (the A/B
+ * of DESIGN.md §3.7; same bits). */
+int mcpt_denoise(mcpt_ctx* ctx, int iterations, float sigma_color, float sigma_plane);
+/* the last mcpt_denoise's image, n_local x 3 f32.  Synchronizes. */
+int mcpt_read_denoised(mcpt_ctx* ctx, float* rgb_out);
+/* Device times (HIP events) of the last mcpt_render_guides and the last mcpt_denoise (its average
+ * and iterations); 0 for what has not run.  Either pointer may be NULL.  Waits for them.
+ * mcpt_denoise_iteration_ms: iteration 0 .. iterations-1 of the last mcpt_denoise alone (-1: its
+ * averaging step). */
+int mcpt_last_denoise_ms(mcpt_ctx* ctx, float* guides_ms, float* filter_ms);
+int mcpt_denoise_iteration_ms(mcpt_ctx* ctx, int iteration, float* ms);
+/* Which kernel the last mcpt_denoise's iterations ran: bit s of *lds_mask set = iteration s
+ * staged its taps in LDS, clear = it read them from global memory (the same bits either way). */
+int mcpt_last_denoise_path(mcpt_ctx* ctx, int* lds_mask);
 
 /* DrawSampling's point cloud (DrawSampling/draw_sampling.cpp:144-150, tp/sampling_base.vert
  * seeding, tp/hsphere.vert random_ray): point k = random_ray(normalize(normal), roughness)

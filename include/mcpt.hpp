@@ -384,6 +384,38 @@ class Renderer {
     for (const Renderer* r : shards) h.push_back(r->c_);
     check(mcpt_gather_rows(c_, h.data(), (int)h.size()), "mcpt_gather_rows");
   }
+  // guide buffers (AOVs) of every local pixel's primary hit (mcpt_render_guides / mcpt_read_guides):
+  // guide8 = local pixels x {N.xyz, key bits, P.xyz, dist}, albedo4 = local pixels x rgba
+  void render_guides(const Camera& cam) {
+    check(mcpt_render_guides(c_, cam.invPV.m, cam.invV.m), "mcpt_render_guides");
+  }
+  void read_guides(std::vector<float>& guide8, std::vector<float>& albedo4) const {
+    guide8.assign((size_t)rows_ * W_ * 8, 0.0f);
+    albedo4.assign((size_t)rows_ * W_ * 4, 0.0f);
+    check(mcpt_read_guides(c_, guide8.data(), albedo4.data()), "mcpt_read_guides");
+  }
+  // the edge-avoiding a-trous filter over accum / pass_count (mcpt_denoise; full-frame targets,
+  // after render_guides); the accumulator stays as it is.  Default sigmas: DESIGN.md §3.7
+  static constexpr float kDenoiseSigmaColor = 4.0f, kDenoiseSigmaPlane = 1.0f;
+  std::vector<float> denoise(int iterations = 5, float sigma_color = kDenoiseSigmaColor,
+                             float sigma_plane = kDenoiseSigmaPlane) {
+    check(mcpt_denoise(c_, iterations, sigma_color, sigma_plane), "mcpt_denoise");
+    std::vector<float> img((size_t)rows_ * W_ * 3);
+    check(mcpt_read_denoised(c_, img.data()), "mcpt_read_denoised");
+    return img;
+  }
+  // (guides kernel ms, filter ms) of the last render_guides / denoise
+  void last_denoise_ms(float& guides_ms, float& filter_ms) const {
+    check(mcpt_last_denoise_ms(c_, &guides_ms, &filter_ms), "mcpt_last_denoise_ms");
+  }
+  // one iteration of the last denoise alone (-1: its averaging step), and which iterations staged
+  // their taps in LDS (bit s)
+  float denoise_iteration_ms(int iteration) const {
+    float ms = 0; check(mcpt_denoise_iteration_ms(c_, iteration, &ms), "mcpt_denoise_iteration_ms"); return ms;
+  }
+  int last_denoise_path() const {
+    int m = 0; check(mcpt_last_denoise_path(c_, &m), "mcpt_last_denoise_path"); return m;
+  }
   void set_traversal(int mode) { check(mcpt_set_traversal(c_, mode), "mcpt_set_traversal"); }
   // render lanes (consecutive launches overlapping each other's tails; same bits): on by default
   void set_render_lanes(bool on) { check(mcpt_set_render_lanes(c_, on ? 1 : 0), "mcpt_set_render_lanes"); }

@@ -17,6 +17,7 @@
 //
 //   mcpt_render --scene 6 --width 1920 --height 1080 --spp 256 --bounces 8 --out s6.png
 //   mcpt_render --scene 8 --width 1920 --height 1080 --spp 512 --bounces 12 --devices 0,1,2,3,4,5,6,7
+//   mcpt_render --scene 6 --spp 16 --denoise --aov s6 --out s6_denoised.png   (a-trous filter + guide AOVs)
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -37,6 +38,8 @@ struct Args {
   std::string png, pfm;
   std::string checkpoint, resume;   // --checkpoint FILE (after every chunk), --resume FILE
   std::vector<int> devices;   // --devices: one shard per entry
+  int denoise = -1;           // --denoise [N]: a-trous iterations (-1: off; N defaults to 5)
+  std::string aov;            // --aov PREFIX: PREFIX_normal.pfm, _albedo.pfm, _depth.pfm
 };
 
 bool parse_list(const char* v, std::vector<int>& out) {
@@ -59,13 +62,21 @@ void usage() {
                "                   [--light L] [--date T] [--variant montecarlo|mat|mat_tr]\n"
                "                   [--traversal auto|lane|wave|stream] [--device D | --devices D0,D1,...]\n"
                "                   [--out img.png] [--pfm img.pfm]\n"
-               "                   [--checkpoint state.ckpt] [--resume state.ckpt]   (one device)\n");
+               "                   [--checkpoint state.ckpt] [--resume state.ckpt]   (one device)\n"
+               "                   [--denoise [N]]   (write the a-trous filtered image, N iterations, default 5)\n"
+               "                   [--aov PREFIX]    (PREFIX_normal.pfm, PREFIX_albedo.pfm, PREFIX_depth.pfm)\n");
 }
 
 bool parse(int argc, char** argv, Args& a) {
   for (int i = 1; i < argc; ++i) {
     const std::string k = argv[i];
     if (k == "-h" || k == "--help") return false;
+    if (k == "--denoise") {   // the iteration count is optional
+      a.denoise = 5;
+      if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') a.denoise = std::atoi(argv[++i]);
+      if (a.denoise > 8) return false;
+      continue;
+    }
     if (i + 1 >= argc) return false;
     const char* v = argv[++i];
     if (k == "--scene") a.scene = std::atoi(v);
@@ -87,6 +98,7 @@ bool parse(int argc, char** argv, Args& a) {
     else if (k == "--pfm") a.pfm = v;
     else if (k == "--checkpoint") a.checkpoint = v;
     else if (k == "--resume") a.resume = v;
+    else if (k == "--aov") a.aov = v;
     else if (k == "--variant") {
       const std::string s = v;
       a.variant = s == "mat" ? MCPT_MAT : (s == "mat_tr" ? MCPT_MAT_TR : MCPT_MONTECARLO);
@@ -105,6 +117,32 @@ bool parse(int argc, char** argv, Args& a) {
   return a.width > 0 && a.height > 0 && a.spp >= 0 && a.chunk > 0 && a.subsampling >= 0 && a.subsampling < 16;
 }
 
+// --denoise / --aov on the context that holds the whole frame: the guide buffers, the AOV files,
+// and the filtered image in place of the averaged one
+void post_process(const Args& a, mcpt::Renderer& r, const mcpt::Camera& cam, int W, int H, std::vector<float>& img,
+                  double& guides_ms, double& filter_ms) {
+  r.render_guides(cam);
+  if (!a.aov.empty()) {
+    std::vector<float> g, al;
+    r.read_guides(g, al);
+    const size_t n = (size_t)W * H;
+    std::vector<float> normal(n * 3), albedo(n * 3), depth(n * 3);
+    for (size_t i = 0; i < n; ++i)
+      for (int k = 0; k < 3; ++k) {
+        normal[3 * i + k] = g[8 * i + k];
+        albedo[3 * i + k] = al[4 * i + k];
+        depth[3 * i + k] = g[8 * i + 7];
+      }
+    mcpt::write_pfm(a.aov + "_normal.pfm", normal, W, H);
+    mcpt::write_pfm(a.aov + "_albedo.pfm", albedo, W, H);
+    mcpt::write_pfm(a.aov + "_depth.pfm", depth, W, H);
+  }
+  if (a.denoise >= 0) img = r.denoise(a.denoise);
+  float gm = 0.0f, fm = 0.0f;
+  r.last_denoise_ms(gm, fm);
+  guides_ms = gm; filter_ms = fm;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -121,7 +159,8 @@ int main(int argc, char** argv) {
     if (W <= 0 || H <= 0) throw std::runtime_error("sub-sampled framebuffer is empty");
     const mcpt::Camera cam = mcpt::Camera::canonical(a.width, a.height);
 
-    double kernel_ms = 0.0, wall_ms = 0.0, gather_ms = 0.0;
+    double kernel_ms = 0.0, wall_ms = 0.0, gather_ms = 0.0, guides_ms = 0.0, filter_ms = 0.0;
+    const bool post = a.denoise >= 0 || !a.aov.empty();
     std::vector<float> img;
     std::string shard_json;
     if (a.devices.empty()) {
@@ -148,6 +187,7 @@ int main(int argc, char** argv) {
         if (!a.checkpoint.empty()) r.save_checkpoint(a.checkpoint, a.first_pass + done + n, tag);
       }
       img = r.read_image();
+      if (post) post_process(a, r, cam, W, H, img, guides_ms, filter_ms);
       wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     } else {
       // N shards: scene upload and targets first (untimed), then one host thread per shard
@@ -161,6 +201,7 @@ int main(int argc, char** argv) {
       }
       mcpt::Renderer frame(a.devices[0]);
       frame.set_target(W, H);
+      if (post) frame.upload(scene);   // the guides are traced on the frame context
       std::vector<double> shard_ms((size_t)N, 0.0);
       std::vector<std::string> errors((size_t)N);
       const auto t0 = std::chrono::steady_clock::now();
@@ -185,6 +226,7 @@ int main(int argc, char** argv) {
       for (const auto& r : shards) views.push_back(r.get());
       frame.gather_rows(views);
       img = frame.read_image();
+      if (post) post_process(a, frame, cam, W, H, img, guides_ms, filter_ms);
       const auto t2 = std::chrono::steady_clock::now();
       wall_ms = std::chrono::duration<double, std::milli>(t2 - t0).count();
       gather_ms = std::chrono::duration<double, std::milli>(t2 - t1).count();
@@ -207,6 +249,12 @@ int main(int argc, char** argv) {
     for (float v : img) mean += v;
     mean /= (double)(img.size() ? img.size() : 1);
     const double samples = (double)W * H * a.spp;
+    if (post) {
+      char buf[96];
+      std::snprintf(buf, sizeof(buf), ", \"denoise\": %d, \"guides_ms\": %.3f, \"filter_ms\": %.3f", a.denoise, guides_ms,
+                    filter_ms);
+      shard_json += buf;
+    }
     std::printf("{\"scene\": %d, \"width\": %d, \"height\": %d, \"spp\": %d, \"bounces\": %d, \"ior\": %g, "
                 "\"light\": %g, \"variant\": %d, \"prims\": %d, \"depth\": %d, \"kernel_ms\": %.3f, "
                 "\"wall_ms\": %.3f, \"msamples_per_s\": %.2f, \"mean\": %.6f%s}\n",

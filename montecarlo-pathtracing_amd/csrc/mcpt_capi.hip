@@ -183,6 +183,18 @@ struct mcpt_ctx {
     int order_age = 0;              // launches since the order was last sorted
   };
   Lane lanes[2];
+  // guide buffers and the à-trous denoiser (mcpt_denoise.hip): 80 B per local pixel, allocated by
+  // the first mcpt_render_guides / mcpt_denoise after a mcpt_set_target*, freed by the next one
+  float4* d_guide = nullptr;        // 2 per pixel: {N, key} {P, dist}
+  float4* d_albedo = nullptr;
+  float4* d_dn[2] = {nullptr, nullptr};   // the filter's ping-pong colour buffers
+  bool guides_valid = false;        // rendered since the last change of target, scene, meshes, flat_face
+  int dn_result = -1;               // which of d_dn holds the last mcpt_denoise's result (-1: none)
+  int dn_iters = -1;                // its iterations (-1: none timed)
+  int dn_lds_mask = 0;              // bit s: its iteration s ran the LDS-tile kernel
+  bool guides_timed = false;
+  hipEvent_t guide_ev[2] = {nullptr, nullptr};
+  hipEvent_t dn_ev[10] = {};        // before the first iteration, then after each (<= 8); [9]: before the average
   int next_lane = 0;                // the lane of the next sub-launch
   int overlap = 1;                  // MCPT_OVERLAP (0: every launch in order on `stream`)
   int prev_lane = -1;               // the lane of the previous sub-launch if it was a lane launch, else -1
@@ -395,6 +407,7 @@ const char* mcpt_error_string(int status) {
                        : status == MCPT_ERR_NO_SCENE  ? "no scene uploaded"
                        : status == MCPT_ERR_NO_TARGET ? "no render target"
                        : status == MCPT_ERR_BAD_SCENE ? "malformed scene buffers"
+                       : status == MCPT_ERR_NO_GUIDES ? "no current guide buffers"
                                                       : "error";
     std::snprintf(g_detail, sizeof(g_detail), "%s (%s)", base, g_last_error);
     return g_detail;
@@ -407,6 +420,7 @@ const char* mcpt_error_string(int status) {
     case MCPT_ERR_HIP: return g_last_error[0] ? g_last_error : "HIP runtime error";
     case MCPT_ERR_NOT_FINALIZED: return "scene not finalized";
     case MCPT_ERR_BAD_SCENE: return "malformed scene buffers";
+    case MCPT_ERR_NO_GUIDES: return "no current guide buffers (call mcpt_render_guides)";
     default: return "unknown status";
   }
 }
@@ -490,6 +504,12 @@ static void free_meshes(mcpt_ctx* c) {
   c->n_meshes = 0;
 }
 
+static void free_denoise(mcpt_ctx* c) {
+  (void)hipFree(c->d_guide); (void)hipFree(c->d_albedo); (void)hipFree(c->d_dn[0]); (void)hipFree(c->d_dn[1]);
+  c->d_guide = nullptr; c->d_albedo = nullptr; c->d_dn[0] = nullptr; c->d_dn[1] = nullptr;
+  c->guides_valid = false; c->dn_result = -1; c->dn_iters = -1; c->guides_timed = false;
+}
+
 static void free_scene(mcpt_ctx* c) {
   (void)hipFree(c->d_nodes); (void)hipFree(c->d_leaves); (void)hipFree(c->d_ptype); (void)hipFree(c->d_prims);
   c->d_nodes = nullptr; c->d_leaves = nullptr; c->d_ptype = nullptr; c->d_prims = nullptr;
@@ -502,6 +522,9 @@ int mcpt_destroy(mcpt_ctx* c) {
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   free_scene(c);
   free_meshes(c);
+  free_denoise(c);
+  for (hipEvent_t e : c->guide_ev) if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : c->dn_ev) if (e) (void)hipEventDestroy(e);
   (void)hipFree(c->d_accum);
   (void)hipFree(c->d_rows);
   (void)hipFree(c->d_events);
@@ -602,6 +625,7 @@ int mcpt_upload_scene(mcpt_ctx* c, const float* prims, int n_prims, const float*
   HIP_OR_RETURN(hipMemcpy(c->d_prims, hp.data(), hp.size() * sizeof(float4), hipMemcpyHostToDevice));
   c->n_prims = n_prims; c->depth = depth; c->nb_emissive = nb_emissives;
   c->mesh_ids = mesh_ids;
+  c->guides_valid = false;
   free_meshes(c);                 // a new scene drops the previous meshes (upload them again)
   c->has_scene = true;
   reset_tuning(c);
@@ -664,6 +688,7 @@ int mcpt_upload_meshes(mcpt_ctx* c, int n_meshes, const int* info, int n_nodes, 
   HIP_OR_RETURN(hipSetDevice(c->device));
   HIP_OR_RETURN(hipStreamSynchronize(c->stream));
   free_meshes(c);
+  c->guides_valid = false;
   if (n_meshes == 0) {
     for (int id : c->mesh_ids)
       if (id >= 0) return set_err(MCPT_ERR_BAD_SCENE, "the scene has mesh instances but no meshes were uploaded");
@@ -756,6 +781,7 @@ int mcpt_upload_meshes(mcpt_ctx* c, int n_meshes, const int* info, int n_nodes, 
 int mcpt_set_flat_face(mcpt_ctx* c, int flat_face) {
   if (!c) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
   c->flat_face = flat_face ? 1 : 0;
+  c->guides_valid = false;
   return MCPT_OK;
 }
 
@@ -768,6 +794,7 @@ static int set_target_rows(mcpt_ctx* c, int W, int H, const int* rows, int n_row
     return set_err(MCPT_ERR_INVALID_ARG, "mcpt_set_target: a shard of 2^31 pixels or more");
   HIP_OR_RETURN(hipSetDevice(c->device));
   HIP_OR_RETURN(hipStreamSynchronize(c->stream));
+  free_denoise(c);   // (sized by the target; allocated again by the next guides / denoise call)
   size_t bytes = (size_t)n_rows * W * 3 * sizeof(float);
   if (bytes != c->accum_bytes) {
     (void)hipFree(c->d_accum);
@@ -1625,6 +1652,162 @@ int mcpt_gather_rows(mcpt_ctx* frame, mcpt_ctx* const* shards, int n_shards) {
     HIP_OR_RETURN(hipStreamWaitEvent(s->stream, copied.e, 0));
   }
   if (n_shards > 0) frame->pass_count = shards[0]->pass_count;
+  return MCPT_OK;
+}
+
+// ---- guide buffers and the à-trous denoiser (mcpt_denoise.hip)
+// the kernel of the filter's steps 1 and 2 when MCPT_DENOISE_NAIVE is unset: 0 the LDS-tile
+// kernels, 1 the global-tap kernel (the A/B: tools/denoise_bench.py, profiles/denoise_bench.json)
+constexpr int kAtrousNaiveDefault = 0;
+static hipError_t ensure_denoise_buffers(mcpt_ctx* c) {
+  if (c->d_guide) return hipSuccess;
+  const size_t n = (size_t)c->n_local_rows * c->W;
+  if (!n) return hipSuccess;
+  hipError_t e = hipMalloc(&c->d_guide, n * 2 * sizeof(float4));
+  if (e == hipSuccess) e = hipMalloc(&c->d_albedo, n * sizeof(float4));
+  if (e == hipSuccess) e = hipMalloc(&c->d_dn[0], n * sizeof(float4));
+  if (e == hipSuccess) e = hipMalloc(&c->d_dn[1], n * sizeof(float4));
+  if (e != hipSuccess) free_denoise(c);
+  return e;
+}
+static hipError_t ensure_timing_events(hipEvent_t* ev, int n) {
+  for (int i = 0; i < n; ++i)
+    if (!ev[i]) {
+      const hipError_t e = hipEventCreate(&ev[i]);
+      if (e != hipSuccess) return e;
+    }
+  return hipSuccess;
+}
+
+int mcpt_render_guides(mcpt_ctx* c, const float* invPV, const float* invV) {
+  if (!c || !invPV || !invV) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_render_guides: bad arguments");
+  if (!c->has_scene) return set_err(MCPT_ERR_NO_SCENE, "no scene uploaded");
+  if (!c->has_target) return set_err(MCPT_ERR_NO_TARGET, "no render target");
+  if (c->n_meshes == 0)
+    for (int id : c->mesh_ids)
+      if (id >= 0) return set_err(MCPT_ERR_BAD_SCENE, "mesh instances present: call mcpt_upload_meshes");
+  HIP_OR_RETURN(hipSetDevice(c->device));
+  HIP_OR_RETURN(ensure_denoise_buffers(c));
+  HIP_OR_RETURN(ensure_timing_events(c->guide_ev, 2));
+  mcpt::GuideParams g;
+  std::memset(&g, 0, sizeof(g));
+  mcpt::RenderParams& p = g.r;
+  p.nodes = c->d_nodes; p.leaves = c->d_leaves; p.ptype = c->d_ptype; p.prims = c->d_prims;
+  corner_rays(invPV, invV, p);
+  p.W = c->W; p.H = c->H; p.rows = c->d_rows; p.n_local_rows = c->n_local_rows;
+  p.n_local_px = (long long)c->n_local_rows * c->W;
+  p.depth = c->depth; p.n_prims = c->n_prims;
+  p.minfo = c->d_minfo; p.mpairs = c->d_mpairs; p.mleaftris = c->d_mleaftris; p.mtris = c->d_mtris;
+  p.mverts = c->d_mverts; p.mnorms = c->d_mnorms; p.n_meshes = c->n_meshes; p.flat_face = c->flat_face;
+  g.guide = c->d_guide; g.albedo = c->d_albedo;
+  HIP_OR_RETURN(hipEventRecord(c->guide_ev[0], c->stream));
+  HIP_OR_RETURN(mcpt_launch_guides(g, c->stream));
+  HIP_OR_RETURN(hipEventRecord(c->guide_ev[1], c->stream));
+  c->guides_valid = true;
+  c->guides_timed = true;
+  return MCPT_OK;
+}
+
+int mcpt_read_guides(mcpt_ctx* c, float* guide8, float* albedo4) {
+  if (!c) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  if (!c->has_target) return mcpt_err_bare(MCPT_ERR_NO_TARGET);
+  if (!c->guides_valid) return set_err(MCPT_ERR_NO_GUIDES, "mcpt_read_guides: no guides rendered for this target and scene");
+  HIP_OR_RETURN(hipSetDevice(c->device));
+  const size_t n = (size_t)c->n_local_rows * c->W;
+  if (guide8 && n)
+    HIP_OR_RETURN(hipMemcpyAsync(guide8, c->d_guide, n * 2 * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+  if (albedo4 && n)
+    HIP_OR_RETURN(hipMemcpyAsync(albedo4, c->d_albedo, n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+  HIP_OR_RETURN(hipStreamSynchronize(c->stream));
+  return MCPT_OK;
+}
+
+int mcpt_denoise(mcpt_ctx* c, int iterations, float sigma_color, float sigma_plane) {
+  if (!c || iterations < 0 || iterations > 8) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_denoise: iterations not in 0..8");
+  if (!(sigma_color > 0.0f) || !(sigma_plane > 0.0f) || !std::isfinite(sigma_color) || !std::isfinite(sigma_plane))
+    return set_err(MCPT_ERR_INVALID_ARG, "mcpt_denoise: sigmas must be positive and finite");
+  if (!c->has_target) return set_err(MCPT_ERR_NO_TARGET, "no render target");
+  bool full = c->n_local_rows == c->H;
+  for (int i = 0; full && i < c->n_local_rows; ++i) full = c->rows[(size_t)i] == i;
+  if (!full) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_denoise: needs a full-frame target (gather the shards first)");
+  if (c->pass_count <= 0) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_denoise: the accumulator holds no passes");
+  if (!c->guides_valid) return set_err(MCPT_ERR_NO_GUIDES, "mcpt_denoise: no guides rendered for this target and scene");
+  HIP_OR_RETURN(hipSetDevice(c->device));
+  HIP_OR_RETURN(ensure_denoise_buffers(c));
+  HIP_OR_RETURN(ensure_timing_events(c->dn_ev, 10));
+  // which kernel runs steps 1 and 2 (same bits): MCPT_DENOISE_NAIVE=1 the
+  // global-tap kernel, =0 the LDS-tile kernels, unset the measured default
+  const bool naive = env_int("MCPT_DENOISE_NAIVE", kAtrousNaiveDefault) != 0;
+  int lds_mask = 0;
+  const long long n = (long long)c->H * c->W;
+  // (the context's stream is ordered after all queued renders: their combines run on it)
+  HIP_OR_RETURN(hipEventRecord(c->dn_ev[9], c->stream));
+  HIP_OR_RETURN(mcpt_launch_average4(c->d_accum, c->d_dn[0], n, c->pass_count, c->stream));
+  HIP_OR_RETURN(hipEventRecord(c->dn_ev[0], c->stream));
+  for (int s = 0; s < iterations; ++s) {
+    const int step = 1 << s;
+    // the iteration's constants in binary32: 2^-s and step are exact factors
+    const float sc = sigma_color * std::ldexp(1.0f, -s);
+    const float sp = sigma_plane * (float)step;
+    const float kc = 1.0f / (sc * sc), kp = 1.0f / (sp * sp);
+    HIP_OR_RETURN(mcpt_launch_atrous(c->d_dn[s & 1], c->d_dn[(s + 1) & 1], c->d_guide, c->W, c->H, step, kc, kp, naive,
+                                     c->stream));
+    HIP_OR_RETURN(hipEventRecord(c->dn_ev[s + 1], c->stream));
+    if (!naive && step <= 2) lds_mask |= 1 << s;
+  }
+  c->dn_lds_mask = lds_mask;
+  c->dn_result = iterations & 1;
+  c->dn_iters = iterations;
+  return MCPT_OK;
+}
+
+int mcpt_read_denoised(mcpt_ctx* c, float* rgb_out) {
+  if (!c || !rgb_out) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  if (!c->has_target) return mcpt_err_bare(MCPT_ERR_NO_TARGET);
+  if (c->dn_result < 0) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_read_denoised: no mcpt_denoise on this target yet");
+  HIP_OR_RETURN(hipSetDevice(c->device));
+  const size_t n = (size_t)c->n_local_rows * c->W;
+  std::vector<float4> h(n);
+  if (n) HIP_OR_RETURN(hipMemcpyAsync(h.data(), c->d_dn[c->dn_result], n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+  HIP_OR_RETURN(hipStreamSynchronize(c->stream));
+  for (size_t i = 0; i < n; ++i) {
+    rgb_out[3 * i] = h[i].x; rgb_out[3 * i + 1] = h[i].y; rgb_out[3 * i + 2] = h[i].z;
+  }
+  return MCPT_OK;
+}
+
+int mcpt_last_denoise_ms(mcpt_ctx* c, float* guides_ms, float* filter_ms) {
+  if (!c) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  HIP_OR_RETURN(hipSetDevice(c->device));
+  if (guides_ms) {
+    *guides_ms = 0.0f;
+    if (c->guides_timed) {
+      HIP_OR_RETURN(hipEventSynchronize(c->guide_ev[1]));
+      HIP_OR_RETURN(hipEventElapsedTime(guides_ms, c->guide_ev[0], c->guide_ev[1]));
+    }
+  }
+  if (filter_ms) {
+    *filter_ms = 0.0f;
+    if (c->dn_iters >= 0) {   // the average and every iteration
+      HIP_OR_RETURN(hipEventSynchronize(c->dn_ev[c->dn_iters]));
+      HIP_OR_RETURN(hipEventElapsedTime(filter_ms, c->dn_ev[9], c->dn_ev[c->dn_iters]));
+    }
+  }
+  return MCPT_OK;
+}
+
+int mcpt_last_denoise_path(mcpt_ctx* c, int* lds_mask) {
+  if (!c || !lds_mask || c->dn_iters < 0) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  *lds_mask = c->dn_lds_mask;
+  return MCPT_OK;
+}
+
+int mcpt_denoise_iteration_ms(mcpt_ctx* c, int iteration, float* ms) {
+  if (!c || !ms || iteration < -1 || iteration >= c->dn_iters) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  HIP_OR_RETURN(hipSetDevice(c->device));
+  hipEvent_t a = iteration < 0 ? c->dn_ev[9] : c->dn_ev[iteration], b = c->dn_ev[iteration + 1];
+  HIP_OR_RETURN(hipEventSynchronize(b));
+  HIP_OR_RETURN(hipEventElapsedTime(ms, a, b));
   return MCPT_OK;
 }
 

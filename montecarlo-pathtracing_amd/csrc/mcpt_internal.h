@@ -206,6 +206,16 @@ struct TraceParams {
   float* out;                   // n × kTraceFloats
 };
 
+// guide buffers (mcpt_render_guides; mcpt_denoise.hip): the scene, target and camera fields of
+// RenderParams, and per local pixel two float4 guide words {N.xyz, key as int bits}
+// {P.xyz, dist} (key = shape << 28 | prim index; a miss: -1, N = P = 0, dist = FLT_MAX) and
+// the hit primitive's rgba (0 on a miss)
+struct GuideParams {
+  RenderParams r;
+  float4* guide;                // 2 x n_local_px
+  float4* albedo;               // n_local_px
+};
+
 struct SampleParams {
   float normal[3], fseed[3];
   float roughness;
@@ -218,6 +228,13 @@ struct SampleParams {
 
 hipError_t mcpt_launch_trace(const mcpt::TraceParams& q, bool any_hit, hipStream_t stream);
 hipError_t mcpt_launch_sample(const mcpt::SampleParams& q, hipStream_t stream);
+hipError_t mcpt_launch_guides(const mcpt::GuideParams& g, hipStream_t stream);
+// out[i] = (accum[3i .. 3i+2] / pass_count, 0): the à-trous filter's first input
+hipError_t mcpt_launch_average4(const float* accum, float4* out, long long n_px, int pass_count, hipStream_t stream);
+// one à-trous iteration over a full W x H frame; naive: every tap from global
+// memory whatever the step (the A/B baseline of the LDS kernels; same bits)
+hipError_t mcpt_launch_atrous(const float4* src, float4* dst, const float4* guide, int W, int H, int step, float kc,
+                              float kp, bool naive, hipStream_t stream);
 hipError_t mcpt_launch_render(const mcpt::RenderParams& p, bool count, hipStream_t stream);
 hipError_t mcpt_launch_combine(const mcpt::RenderParams& p, hipStream_t stream);
 hipError_t mcpt_iota(int* a, int n, hipStream_t stream);

@@ -45,6 +45,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 
 
 DEBUG_SLOTS = 64   # MCPT_DEBUG_SLOTS
+# the denoiser's default edge-stopping widths (chosen by the sweep of DESIGN.md §3.7)
+DENOISE_SIGMA_COLOR = 4.0
+DENOISE_SIGMA_PLANE = 1.0
 
 
 class MCPTError(RuntimeError):
@@ -152,6 +155,13 @@ def _declare(L: ctypes.CDLL) -> None:
         "mcpt_checkpoint_save": (i, [_vp, ctypes.c_char_p, i, ctypes.c_char_p]),
         "mcpt_checkpoint_load": (i, [_vp, ctypes.c_char_p, ctypes.c_char_p, ip]),
         "mcpt_checkpoint_read": (i, [ctypes.c_char_p, fp, ctypes.c_longlong, ip, ip, ip, ip, ctypes.c_char_p]),
+        "mcpt_render_guides": (i, [_vp, fp, fp]),
+        "mcpt_read_guides": (i, [_vp, fp, fp]),
+        "mcpt_denoise": (i, [_vp, i, f, f]),
+        "mcpt_read_denoised": (i, [_vp, fp]),
+        "mcpt_last_denoise_ms": (i, [_vp, fp, fp]),
+        "mcpt_denoise_iteration_ms": (i, [_vp, i, fp]),
+        "mcpt_last_denoise_path": (i, [_vp, ip]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -603,6 +613,49 @@ class Renderer:
         device-to-device peer copies inside one process, ordered after the shards' renders)."""
         hs = (_vp * max(len(shards), 1))(*[s._h for s in shards])
         _check(lib().mcpt_gather_rows(self._h, hs, len(shards)), "mcpt_gather_rows")
+
+    # ---- guide buffers and the a-trous denoiser (mcpt.h; DESIGN.md §3.7)
+    def render_guides(self, invPV, invV) -> None:
+        """mcpt_render_guides: the primary hit of every local pixel's camera ray (asynchronous)."""
+        a, b = _f32(invPV, 16), _f32(invV, 16)
+        _check(lib().mcpt_render_guides(self._h, _fp(a), _fp(b)), "mcpt_render_guides")
+
+    def read_guides(self) -> dict:
+        """The guide buffers as local rows x W arrays: normal (.., 3), key (int32: shape << 28 |
+        primitive index, -1 = miss), position (.., 3), dist, albedo (.., 4 rgba)."""
+        g = np.zeros((self.n_local_rows, self.W, 8), np.float32)
+        al = np.zeros((self.n_local_rows, self.W, 4), np.float32)
+        _check(lib().mcpt_read_guides(self._h, _fp(g), _fp(al)), "mcpt_read_guides")
+        return {"normal": np.ascontiguousarray(g[..., 0:3]), "key": np.ascontiguousarray(g[..., 3]).view(np.int32),
+                "position": np.ascontiguousarray(g[..., 4:7]), "dist": np.ascontiguousarray(g[..., 7]),
+                "albedo": al}
+
+    def denoise(self, iterations: int = 5, sigma_color: float = DENOISE_SIGMA_COLOR,
+                sigma_plane: float = DENOISE_SIGMA_PLANE) -> np.ndarray:
+        """mcpt_denoise + mcpt_read_denoised: the H x W x 3 image after `iterations` a-trous passes
+        over accum / pass_count (the accumulator stays as it is).  Needs render_guides first."""
+        _check(lib().mcpt_denoise(self._h, int(iterations), float(sigma_color), float(sigma_plane)), "mcpt_denoise")
+        out = np.zeros((self.n_local_rows, self.W, 3), np.float32)
+        _check(lib().mcpt_read_denoised(self._h, _fp(out)), "mcpt_read_denoised")
+        return out
+
+    def last_denoise_ms(self) -> Tuple[float, float]:
+        """(guides kernel ms, filter ms) of the last render_guides / denoise."""
+        g, fl = ctypes.c_float(), ctypes.c_float()
+        _check(lib().mcpt_last_denoise_ms(self._h, ctypes.byref(g), ctypes.byref(fl)), "mcpt_last_denoise_ms")
+        return g.value, fl.value
+
+    def denoise_iteration_ms(self, iteration: int) -> float:
+        """Device ms of one iteration of the last denoise (-1: its averaging step)."""
+        ms = ctypes.c_float()
+        _check(lib().mcpt_denoise_iteration_ms(self._h, int(iteration), ctypes.byref(ms)), "mcpt_denoise_iteration_ms")
+        return ms.value
+
+    def last_denoise_path(self) -> int:
+        """Bit s set: iteration s of the last denoise staged its taps in LDS (clear: global taps)."""
+        m = ctypes.c_int()
+        _check(lib().mcpt_last_denoise_path(self._h, ctypes.byref(m)), "mcpt_last_denoise_path")
+        return m.value
 
     def trace(self, origins, dirs, any_hit: bool = False, prim: int = -1) -> np.ndarray:
         """Ray queries (traverse_all_bvh / just_hit_bvh, or one primitive) + intersection_info.
