@@ -35,6 +35,7 @@ enum mcpt_status {
   MCPT_ERR_NOT_FINALIZED = -5,
   MCPT_ERR_BAD_SCENE = -6,
   MCPT_ERR_NO_GUIDES = -7,   /* mcpt_denoise / mcpt_read_guides without current guide buffers */
+  MCPT_ERR_NO_STATS = -8,    /* a statistics query with statistics off, fewer than two batches or no error map */
 };
 
 /* integrator variants: the SrcLoader list of MontecarloGPU/montecarlo.cpp:27 */
@@ -340,6 +341,58 @@ int mcpt_denoise_iteration_ms(mcpt_ctx* ctx, int iteration, float* ms);
 /* Which kernel the last mcpt_denoise's iterations ran: bit s of *lds_mask set = iteration s
  * staged its taps in LDS, clear = it read them from global memory (the same bits either way). */
 int mcpt_last_denoise_path(mcpt_ctx* ctx, int* lds_mask);
+
+/* Noise statistics, the convergence metric and the noise-guided filter (no
+ * reference equivalent).  Opt-in: with statistics off no render call does any work for them.
+ * Device memory while on: +16 B per local pixel for the state, +8 B per local pixel for the error
+ * map, allocated by the first mcpt_stats_begin after a mcpt_set_target* and freed by mcpt_stats_end,
+ * the next mcpt_set_target* (which turns statistics off) and mcpt_destroy.  Works on any target, row
+ * shards included: the records of shards add (n_px, n_above, sum_q) and max (max_r).
+ *
+ * The statistics are batch means of the pixels' luminance sums over a window of render calls:
+ * mcpt_stats_begin snapshots the accumulator and starts a window (passes = batches = 0;
+ * asynchronous); from then on every mcpt_render / mcpt_render_counted of n_passes > 0 appends one
+ * batch of its n_passes, enqueued on the context's stream behind the call's last combine without a
+ * host wait, whatever the schedule and however many launches the call runs.  mcpt_clear_accum,
+ * mcpt_write_accum, mcpt_checkpoint_load and mcpt_gather_rows do not touch the statistics: after
+ * them the caller declares the accumulator's n new passes as a batch (mcpt_stats_add_batch, n > 0;
+ * asynchronous) or begins again.  Checkpoints do not store statistics: a resumed render begins a
+ * new window.
+ *
+ * mcpt_convergence: per local pixel the standard error `se` of the window's mean luminance and the
+ * relative error r = se / (max(0, mean) + mu_floor), clamped to 64 (an overflowed pixel counts 64),
+ * written to the error map, and the frame's record: n_px, n_above = #{r > threshold}, max_r, and
+ * sum_q = the sum of trunc(r * 65536) (an integer: the same bits for any reduction order);
+ * mean_r = sum_q / 65536 / n_px.  Needs statistics on and two batches or more (else
+ * MCPT_ERR_NO_STATS), positive finite threshold and mu_floor (else MCPT_ERR_INVALID_ARG).
+ * Synchronizes.  mcpt_read_error_map: n_local x 2 f32 {se, r} of the window's last
+ * mcpt_convergence (MCPT_ERR_NO_STATS without one).  Synchronizes.
+ *
+ * mcpt_denoise_guided: mcpt_denoise with the colour term's width taken per pixel from the error
+ * map, k_color * se (halved each iteration), in place of sigma_color; mcpt_denoise's preconditions
+ * plus an error map of the current window (else MCPT_ERR_NO_STATS).  The map is read as the last
+ * mcpt_convergence wrote it.  It writes mcpt_denoise's result buffers: mcpt_read_denoised,
+ * mcpt_last_denoise_ms, mcpt_denoise_iteration_ms and mcpt_last_denoise_path serve both filters.
+ *
+ * mcpt_last_stats_ms: device times (HIP events) of the last batch update and the last error kernel;
+ * 0 for what has not run.  Either pointer may be NULL.  Waits for them. */
+int mcpt_stats_begin(mcpt_ctx* ctx);
+int mcpt_stats_end(mcpt_ctx* ctx);
+int mcpt_stats_add_batch(mcpt_ctx* ctx, int n);
+/* on / passes / batches of the window (0 / 0 / 0 with statistics off); any pointer may be NULL */
+int mcpt_stats_info(mcpt_ctx* ctx, int* on, long long* passes, int* batches);
+typedef struct mcpt_convergence_t {
+  long long n_px, n_above;
+  unsigned long long sum_q;
+  float max_r;
+  double mean_r;
+  long long passes;
+  int batches;
+} mcpt_convergence_t;
+int mcpt_convergence(mcpt_ctx* ctx, float threshold, float mu_floor, mcpt_convergence_t* out);
+int mcpt_read_error_map(mcpt_ctx* ctx, float* se_r2);
+int mcpt_denoise_guided(mcpt_ctx* ctx, int iterations, float k_color, float sigma_plane);
+int mcpt_last_stats_ms(mcpt_ctx* ctx, float* update_ms, float* error_ms);
 
 /* DrawSampling's point cloud (DrawSampling/draw_sampling.cpp:144-150, tp/sampling_base.vert
  * seeding, tp/hsphere.vert random_ray): point k = random_ray(normalize(normal), roughness)

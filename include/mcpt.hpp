@@ -416,6 +416,67 @@ class Renderer {
   int last_denoise_path() const {
     int m = 0; check(mcpt_last_denoise_path(c_, &m), "mcpt_last_denoise_path"); return m;
   }
+  // noise statistics, the convergence metric and the noise-guided filter (mcpt.h):
+  // between stats_begin and stats_end every render call is one batch of the window
+  static constexpr float kDenoiseKColor = 64.0f, kErrorMuFloor = 0.01f;
+  void stats_begin() { check(mcpt_stats_begin(c_), "mcpt_stats_begin"); }
+  void stats_end() { check(mcpt_stats_end(c_), "mcpt_stats_end"); }
+  void stats_add_batch(int n) { check(mcpt_stats_add_batch(c_, n), "mcpt_stats_add_batch"); }
+  struct StatsInfo { bool on; long long passes; int batches; };
+  StatsInfo stats_info() const {
+    int on = 0, b = 0; long long n = 0;
+    check(mcpt_stats_info(c_, &on, &n, &b), "mcpt_stats_info");
+    return StatsInfo{on != 0, n, b};
+  }
+  mcpt_convergence_t convergence(float threshold, float mu_floor = kErrorMuFloor) {
+    mcpt_convergence_t rec;
+    check(mcpt_convergence(c_, threshold, mu_floor, &rec), "mcpt_convergence");
+    return rec;
+  }
+  // local pixels x {se, r} of the last convergence()
+  std::vector<float> read_error_map() const {
+    std::vector<float> m((size_t)rows_ * W_ * 2);
+    check(mcpt_read_error_map(c_, m.data()), "mcpt_read_error_map");
+    return m;
+  }
+  std::vector<float> denoise_guided(int iterations = 5, float k_color = kDenoiseKColor,
+                                    float sigma_plane = kDenoiseSigmaPlane) {
+    check(mcpt_denoise_guided(c_, iterations, k_color, sigma_plane), "mcpt_denoise_guided");
+    std::vector<float> img((size_t)rows_ * W_ * 3);
+    check(mcpt_read_denoised(c_, img.data()), "mcpt_read_denoised");
+    return img;
+  }
+  void last_stats_ms(float& update_ms, float& error_ms) const {
+    check(mcpt_last_stats_ms(c_, &update_ms, &error_ms), "mcpt_last_stats_ms");
+  }
+  // Render passes first_pass, first_pass + 1, ... in calls of `batch` passes until the mean relative
+  // error is at most target_error or max_passes are rendered; the convergence is queried after every
+  // check_every calls (and at the cap), the calls in between are queued without a wait.  Begins a
+  // statistics window unless one is on.  Returns the last record; *rendered = this call's passes.
+  mcpt_convergence_t render_until(const Camera& cam, float target_error, int batch = 32, int max_passes = 4096,
+                                  int check_every = 4, int first_pass = 1, float date = 0.0f, int bounces = 3,
+                                  float refract_ind = 1.0f, int variant = MCPT_MONTECARLO, int* rendered = nullptr,
+                                  float mu_floor = kErrorMuFloor) {
+    if (batch <= 0 || check_every <= 0 || max_passes <= 0 || !(target_error > 0.0f))
+      throw std::runtime_error("render_until: batch, check_every, max_passes and target_error must be positive");
+    if (!stats_info().on) stats_begin();
+    mcpt_convergence_t rec;
+    bool have = false;
+    int done = 0;
+    for (int calls = 1; done < max_passes; ++calls) {
+      const int n = batch < max_passes - done ? batch : max_passes - done;
+      render(cam, first_pass + done, n, date, bounces, refract_ind, variant);
+      done += n;
+      if ((calls % check_every == 0 || done >= max_passes) && stats_info().batches >= 2) {
+        rec = convergence(target_error, mu_floor);
+        have = true;
+        if (rec.mean_r <= (double)target_error) break;
+      }
+    }
+    if (!have) rec = convergence(target_error, mu_floor);   // (fewer than two batches: MCPT_ERR_NO_STATS)
+    if (rendered) *rendered = done;
+    return rec;
+  }
   void set_traversal(int mode) { check(mcpt_set_traversal(c_, mode), "mcpt_set_traversal"); }
   // render lanes (consecutive launches overlapping each other's tails; same bits): on by default
   void set_render_lanes(bool on) { check(mcpt_set_render_lanes(c_, on ? 1 : 0), "mcpt_set_render_lanes"); }

@@ -18,6 +18,7 @@
 //   mcpt_render --scene 6 --width 1920 --height 1080 --spp 256 --bounces 8 --out s6.png
 //   mcpt_render --scene 8 --width 1920 --height 1080 --spp 512 --bounces 12 --devices 0,1,2,3,4,5,6,7
 //   mcpt_render --scene 6 --spp 16 --denoise --aov s6 --out s6_denoised.png   (a-trous filter + guide AOVs)
+//   mcpt_render --scene 6 --spp 4096 --chunk 32 --target-error 0.02 --out s6.png   (stop at 2 % mean relative error)
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -39,7 +40,9 @@ struct Args {
   std::string checkpoint, resume;   // --checkpoint FILE (after every chunk), --resume FILE
   std::vector<int> devices;   // --devices: one shard per entry
   int denoise = -1;           // --denoise [N]: a-trous iterations (-1: off; N defaults to 5)
-  std::string aov;            // --aov PREFIX: PREFIX_normal.pfm, _albedo.pfm, _depth.pfm
+  std::string aov;            // --aov PREFIX: PREFIX_normal.pfm, _albedo.pfm, _depth.pfm (+ _error.pfm with statistics)
+  double target_error = 0.0;  // --target-error E: stop once the mean relative error <= E (--spp: the cap; 0: off)
+  int denoise_guided = -1;    // --denoise-guided [N]: the noise-guided filter (-1: off; N defaults to 5)
 };
 
 bool parse_list(const char* v, std::vector<int>& out) {
@@ -64,7 +67,12 @@ void usage() {
                "                   [--out img.png] [--pfm img.pfm]\n"
                "                   [--checkpoint state.ckpt] [--resume state.ckpt]   (one device)\n"
                "                   [--denoise [N]]   (write the a-trous filtered image, N iterations, default 5)\n"
-               "                   [--aov PREFIX]    (PREFIX_normal.pfm, PREFIX_albedo.pfm, PREFIX_depth.pfm)\n");
+               "                   [--aov PREFIX]    (PREFIX_normal.pfm, PREFIX_albedo.pfm, PREFIX_depth.pfm;\n"
+               "                                      PREFIX_error.pfm = {se, r, 0} with noise statistics)\n"
+               "                   [--target-error E]   (one device: render chunks of --chunk passes until the mean\n"
+               "                                         relative error <= E, at most --spp passes)\n"
+               "                   [--denoise-guided [N]]   (one device: the a-trous filter with the colour width\n"
+               "                                             from each pixel's standard error; >= 2 chunks)\n");
 }
 
 bool parse(int argc, char** argv, Args& a) {
@@ -75,6 +83,12 @@ bool parse(int argc, char** argv, Args& a) {
       a.denoise = 5;
       if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') a.denoise = std::atoi(argv[++i]);
       if (a.denoise > 8) return false;
+      continue;
+    }
+    if (k == "--denoise-guided") {
+      a.denoise_guided = 5;
+      if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') a.denoise_guided = std::atoi(argv[++i]);
+      if (a.denoise_guided > 8) return false;
       continue;
     }
     if (i + 1 >= argc) return false;
@@ -99,6 +113,10 @@ bool parse(int argc, char** argv, Args& a) {
     else if (k == "--checkpoint") a.checkpoint = v;
     else if (k == "--resume") a.resume = v;
     else if (k == "--aov") a.aov = v;
+    else if (k == "--target-error") {
+      a.target_error = std::atof(v);
+      if (!(a.target_error > 0.0)) return false;
+    }
     else if (k == "--variant") {
       const std::string s = v;
       a.variant = s == "mat" ? MCPT_MAT : (s == "mat_tr" ? MCPT_MAT_TR : MCPT_MONTECARLO);
@@ -114,6 +132,8 @@ bool parse(int argc, char** argv, Args& a) {
     }
   }
   if (!a.devices.empty() && (!a.checkpoint.empty() || !a.resume.empty())) return false;   // one device only
+  if (!a.devices.empty() && (a.target_error > 0.0 || a.denoise_guided >= 0)) return false;  // (statistics: one device)
+  if (a.denoise >= 0 && a.denoise_guided >= 0) return false;                                // one filter
   return a.width > 0 && a.height > 0 && a.spp >= 0 && a.chunk > 0 && a.subsampling >= 0 && a.subsampling < 16;
 }
 
@@ -137,7 +157,21 @@ void post_process(const Args& a, mcpt::Renderer& r, const mcpt::Camera& cam, int
     mcpt::write_pfm(a.aov + "_albedo.pfm", albedo, W, H);
     mcpt::write_pfm(a.aov + "_depth.pfm", depth, W, H);
   }
+  if (r.stats_info().batches >= 2) {   // noise statistics on: the error map (of the final state) and its filter
+    r.convergence(a.target_error > 0.0 ? (float)a.target_error : 0.05f);
+    if (!a.aov.empty()) {
+      const std::vector<float> m = r.read_error_map();
+      const size_t n = (size_t)W * H;
+      std::vector<float> err(n * 3, 0.0f);
+      for (size_t i = 0; i < n; ++i) {
+        err[3 * i] = m[2 * i];
+        err[3 * i + 1] = m[2 * i + 1];
+      }
+      mcpt::write_pfm(a.aov + "_error.pfm", err, W, H);
+    }
+  }
   if (a.denoise >= 0) img = r.denoise(a.denoise);
+  if (a.denoise_guided >= 0) img = r.denoise_guided(a.denoise_guided);   // (fewer than two chunks: an error)
   float gm = 0.0f, fm = 0.0f;
   r.last_denoise_ms(gm, fm);
   guides_ms = gm; filter_ms = fm;
@@ -160,9 +194,11 @@ int main(int argc, char** argv) {
     const mcpt::Camera cam = mcpt::Camera::canonical(a.width, a.height);
 
     double kernel_ms = 0.0, wall_ms = 0.0, gather_ms = 0.0, guides_ms = 0.0, filter_ms = 0.0;
-    const bool post = a.denoise >= 0 || !a.aov.empty();
+    const bool post = a.denoise >= 0 || a.denoise_guided >= 0 || !a.aov.empty();
+    const bool stats = a.target_error > 0.0 || a.denoise_guided >= 0;
     std::vector<float> img;
     std::string shard_json;
+    int rendered = a.spp;   // passes in the image (fewer with --target-error)
     if (a.devices.empty()) {
       mcpt::Renderer r(a.device);
       r.set_traversal(a.traversal);
@@ -180,14 +216,40 @@ int main(int argc, char** argv) {
       int next = a.first_pass;
       if (!a.resume.empty()) next = r.load_checkpoint(a.resume, tag);
       const auto t0 = std::chrono::steady_clock::now();
-      for (int done = next - a.first_pass; done < a.spp; done += a.chunk) {
+      // noise statistics: a window from here (a resumed render begins a new one), a batch per chunk;
+      // --target-error asks every 4 chunks and after the last
+      if (stats) r.stats_begin();
+      mcpt_convergence_t rec{};
+      bool have_rec = false, converged = false;
+      int calls = 0;
+      for (int done = next - a.first_pass; done < a.spp && !converged; done += a.chunk) {
         const int n = std::min(a.chunk, a.spp - done);
         r.render(cam, a.first_pass + done, n, a.date, a.bounces, a.ior, a.variant);
         kernel_ms += r.last_render_ms();
         if (!a.checkpoint.empty()) r.save_checkpoint(a.checkpoint, a.first_pass + done + n, tag);
+        rendered = done + n;
+        ++calls;
+        if (a.target_error > 0.0 && (calls % 4 == 0 || rendered >= a.spp) && r.stats_info().batches >= 2) {
+          rec = r.convergence((float)a.target_error);
+          have_rec = true;
+          converged = rec.mean_r <= a.target_error;
+        }
       }
       img = r.read_image();
       if (post) post_process(a, r, cam, W, H, img, guides_ms, filter_ms);
+      if (a.target_error > 0.0) {
+        char buf[320];
+        if (have_rec)
+          std::snprintf(buf, sizeof(buf),
+                        ", \"target_error\": %g, \"converged\": %s, \"window_passes\": %lld, \"batches\": %d, "
+                        "\"mean_r\": %.6f, \"max_r\": %.6f, \"n_above\": %lld, \"n_px\": %lld, \"sum_q\": %llu",
+                        a.target_error, converged ? "true" : "false", rec.passes, rec.batches, rec.mean_r, rec.max_r,
+                        rec.n_above, rec.n_px, rec.sum_q);
+        else   // fewer than two chunks: no estimate
+          std::snprintf(buf, sizeof(buf), ", \"target_error\": %g, \"converged\": false, \"mean_r\": null",
+                        a.target_error);
+        shard_json += buf;
+      }
       wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     } else {
       // N shards: scene upload and targets first (untimed), then one host thread per shard
@@ -248,13 +310,15 @@ int main(int argc, char** argv) {
     double mean = 0.0;
     for (float v : img) mean += v;
     mean /= (double)(img.size() ? img.size() : 1);
-    const double samples = (double)W * H * a.spp;
+    const double samples = (double)W * H * rendered;
     if (post) {
-      char buf[96];
+      char buf[128];
       std::snprintf(buf, sizeof(buf), ", \"denoise\": %d, \"guides_ms\": %.3f, \"filter_ms\": %.3f", a.denoise, guides_ms,
                     filter_ms);
       shard_json += buf;
+      if (a.denoise_guided >= 0) shard_json += ", \"denoise_guided\": " + std::to_string(a.denoise_guided);
     }
+    shard_json += ", \"passes\": " + std::to_string(rendered);
     std::printf("{\"scene\": %d, \"width\": %d, \"height\": %d, \"spp\": %d, \"bounces\": %d, \"ior\": %g, "
                 "\"light\": %g, \"variant\": %d, \"prims\": %d, \"depth\": %d, \"kernel_ms\": %.3f, "
                 "\"wall_ms\": %.3f, \"msamples_per_s\": %.2f, \"mean\": %.6f%s}\n",

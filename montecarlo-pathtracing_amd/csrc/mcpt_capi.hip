@@ -195,6 +195,17 @@ struct mcpt_ctx {
   bool guides_timed = false;
   hipEvent_t guide_ev[2] = {nullptr, nullptr};
   hipEvent_t dn_ev[10] = {};        // before the first iteration, then after each (<= 8); [9]: before the average
+  // noise statistics (mcpt_stats.hip): 24 B per local pixel, allocated by the first
+  // mcpt_stats_begin after a mcpt_set_target*, freed by mcpt_stats_end and the next mcpt_set_target*
+  float4* d_stats = nullptr;        // per pixel {Yacc, S2, Ybase, 0}
+  float2* d_emap = nullptr;         // per pixel {se, r} of the last mcpt_convergence
+  unsigned long long* d_conv = nullptr;   // the partial frame records the error kernel reduces into
+  bool stats_on = false;
+  long long stats_passes = 0;       // N: passes in the window
+  int stats_batches = 0;            // B: batches in the window
+  bool emap_valid = false;          // d_emap was written in this window
+  bool stats_update_timed = false, stats_error_timed = false;
+  hipEvent_t stats_ev[4] = {};      // around the last batch update [0, 1] and the last error kernel [2, 3]
   int next_lane = 0;                // the lane of the next sub-launch
   int overlap = 1;                  // MCPT_OVERLAP (0: every launch in order on `stream`)
   int prev_lane = -1;               // the lane of the previous sub-launch if it was a lane launch, else -1
@@ -408,6 +419,7 @@ const char* mcpt_error_string(int status) {
                        : status == MCPT_ERR_NO_TARGET ? "no render target"
                        : status == MCPT_ERR_BAD_SCENE ? "malformed scene buffers"
                        : status == MCPT_ERR_NO_GUIDES ? "no current guide buffers"
+                       : status == MCPT_ERR_NO_STATS  ? "no noise statistics"
                                                       : "error";
     std::snprintf(g_detail, sizeof(g_detail), "%s (%s)", base, g_last_error);
     return g_detail;
@@ -421,6 +433,7 @@ const char* mcpt_error_string(int status) {
     case MCPT_ERR_NOT_FINALIZED: return "scene not finalized";
     case MCPT_ERR_BAD_SCENE: return "malformed scene buffers";
     case MCPT_ERR_NO_GUIDES: return "no current guide buffers (call mcpt_render_guides)";
+    case MCPT_ERR_NO_STATS: return "no noise statistics (mcpt_stats_begin, two batches, mcpt_convergence)";
     default: return "unknown status";
   }
 }
@@ -510,6 +523,13 @@ static void free_denoise(mcpt_ctx* c) {
   c->guides_valid = false; c->dn_result = -1; c->dn_iters = -1; c->guides_timed = false;
 }
 
+static void free_stats(mcpt_ctx* c) {
+  (void)hipFree(c->d_stats); (void)hipFree(c->d_emap); (void)hipFree(c->d_conv);
+  c->d_stats = nullptr; c->d_emap = nullptr; c->d_conv = nullptr;
+  c->stats_on = false; c->stats_passes = 0; c->stats_batches = 0; c->emap_valid = false;
+  c->stats_update_timed = false; c->stats_error_timed = false;
+}
+
 static void free_scene(mcpt_ctx* c) {
   (void)hipFree(c->d_nodes); (void)hipFree(c->d_leaves); (void)hipFree(c->d_ptype); (void)hipFree(c->d_prims);
   c->d_nodes = nullptr; c->d_leaves = nullptr; c->d_ptype = nullptr; c->d_prims = nullptr;
@@ -525,6 +545,8 @@ int mcpt_destroy(mcpt_ctx* c) {
   free_denoise(c);
   for (hipEvent_t e : c->guide_ev) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->dn_ev) if (e) (void)hipEventDestroy(e);
+  free_stats(c);
+  for (hipEvent_t e : c->stats_ev) if (e) (void)hipEventDestroy(e);
   (void)hipFree(c->d_accum);
   (void)hipFree(c->d_rows);
   (void)hipFree(c->d_events);
@@ -795,6 +817,7 @@ static int set_target_rows(mcpt_ctx* c, int W, int H, const int* rows, int n_row
   HIP_OR_RETURN(hipSetDevice(c->device));
   HIP_OR_RETURN(hipStreamSynchronize(c->stream));
   free_denoise(c);   // (sized by the target; allocated again by the next guides / denoise call)
+  free_stats(c);     // (statistics off: a new target begins again)
   size_t bytes = (size_t)n_rows * W * 3 * sizeof(float);
   if (bytes != c->accum_bytes) {
     (void)hipFree(c->d_accum);
@@ -1128,6 +1151,26 @@ static int checked_sub_launch(mcpt_ctx* c, int k, int n_sub, const mcpt::RenderP
 }
 #endif
 
+// One batch of the noise statistics: "the accumulator now holds n more passes than
+// at the previous batch", enqueued on the context's stream (which is ordered after every queued
+// render's combine), no host wait.
+static hipError_t stats_batch(mcpt_ctx* c, int n) {
+  for (int i = 0; i < 2; ++i)
+    if (!c->stats_ev[i]) {
+      const hipError_t e = hipEventCreate(&c->stats_ev[i]);
+      if (e != hipSuccess) return e;
+    }
+  hipError_t e = hipEventRecord(c->stats_ev[0], c->stream);
+  if (e == hipSuccess)
+    e = mcpt_launch_stats_update(c->d_accum, c->d_stats, (long long)c->n_local_rows * c->W, n, c->stream);
+  if (e == hipSuccess) e = hipEventRecord(c->stats_ev[1], c->stream);
+  if (e != hipSuccess) return e;
+  c->stats_passes += n;
+  c->stats_batches += 1;
+  c->stats_update_timed = true;
+  return hipSuccess;
+}
+
 static int launch(mcpt_ctx* c, const float* invPV, const float* invV, int first_pass, int n_passes, float date,
                   int bounces, float refract_ind, int variant, bool count, unsigned long long* events) {
   if (!c || !invPV || !invV || n_passes < 0 || variant < 0 || variant > 2)
@@ -1442,6 +1485,8 @@ static int launch(mcpt_ctx* c, const float* invPV, const float* invV, int first_
   c->pass_split = split ? 1 : 0;
   c->timed = true;
   c->pass_count += n_passes;
+  // noise statistics on: the call is one batch, behind its last combine
+  if (c->stats_on && n_passes > 0) HIP_OR_RETURN(stats_batch(c, n_passes));
   if (count) {
     unsigned long long h[mcpt::EV_COUNT];
     HIP_OR_RETURN(hipMemcpyAsync(h, c->d_events, sizeof(h), hipMemcpyDeviceToHost, c->stream));
@@ -1722,7 +1767,9 @@ int mcpt_read_guides(mcpt_ctx* c, float* guide8, float* albedo4) {
   return MCPT_OK;
 }
 
-int mcpt_denoise(mcpt_ctx* c, int iterations, float sigma_color, float sigma_plane) {
+// mcpt_denoise (guided false: sigma_color is the global width) and mcpt_denoise_guided (guided
+// true: sigma_color is k_color, the width per pixel k_color * 2^-s * se from the error map)
+static int denoise_run(mcpt_ctx* c, int iterations, float sigma_color, float sigma_plane, bool guided) {
   if (!c || iterations < 0 || iterations > 8) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_denoise: iterations not in 0..8");
   if (!(sigma_color > 0.0f) || !(sigma_plane > 0.0f) || !std::isfinite(sigma_color) || !std::isfinite(sigma_plane))
     return set_err(MCPT_ERR_INVALID_ARG, "mcpt_denoise: sigmas must be positive and finite");
@@ -1732,6 +1779,8 @@ int mcpt_denoise(mcpt_ctx* c, int iterations, float sigma_color, float sigma_pla
   if (!full) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_denoise: needs a full-frame target (gather the shards first)");
   if (c->pass_count <= 0) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_denoise: the accumulator holds no passes");
   if (!c->guides_valid) return set_err(MCPT_ERR_NO_GUIDES, "mcpt_denoise: no guides rendered for this target and scene");
+  if (guided && !(c->stats_on && c->emap_valid))
+    return set_err(MCPT_ERR_NO_STATS, "mcpt_denoise_guided: no error map (mcpt_convergence) of the current statistics");
   HIP_OR_RETURN(hipSetDevice(c->device));
   HIP_OR_RETURN(ensure_denoise_buffers(c));
   HIP_OR_RETURN(ensure_timing_events(c->dn_ev, 10));
@@ -1749,15 +1798,138 @@ int mcpt_denoise(mcpt_ctx* c, int iterations, float sigma_color, float sigma_pla
     // the iteration's constants in binary32: 2^-s and step are exact factors
     const float sc = sigma_color * std::ldexp(1.0f, -s);
     const float sp = sigma_plane * (float)step;
-    const float kc = 1.0f / (sc * sc), kp = 1.0f / (sp * sp);
-    HIP_OR_RETURN(mcpt_launch_atrous(c->d_dn[s & 1], c->d_dn[(s + 1) & 1], c->d_guide, c->W, c->H, step, kc, kp, naive,
-                                     c->stream));
+    // (guided: the kernel forms kc per pixel from sc = k_color * 2^-s and the pixel's se, §3.8)
+    const float kc = guided ? sc : 1.0f / (sc * sc), kp = 1.0f / (sp * sp);
+    HIP_OR_RETURN(mcpt_launch_atrous(c->d_dn[s & 1], c->d_dn[(s + 1) & 1], c->d_guide, c->W, c->H, step, kc, kp,
+                                     guided ? c->d_emap : nullptr, naive, c->stream));
     HIP_OR_RETURN(hipEventRecord(c->dn_ev[s + 1], c->stream));
     if (!naive && step <= 2) lds_mask |= 1 << s;
   }
   c->dn_lds_mask = lds_mask;
   c->dn_result = iterations & 1;
   c->dn_iters = iterations;
+  return MCPT_OK;
+}
+
+int mcpt_denoise(mcpt_ctx* c, int iterations, float sigma_color, float sigma_plane) {
+  return denoise_run(c, iterations, sigma_color, sigma_plane, false);
+}
+
+int mcpt_denoise_guided(mcpt_ctx* c, int iterations, float k_color, float sigma_plane) {
+  return denoise_run(c, iterations, k_color, sigma_plane, true);
+}
+
+// ---- noise statistics and the convergence metric (mcpt_stats.hip)
+int mcpt_stats_begin(mcpt_ctx* c) {
+  if (!c) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  if (!c->has_target) return set_err(MCPT_ERR_NO_TARGET, "no render target");
+  HIP_OR_RETURN(hipSetDevice(c->device));
+  const size_t n = (size_t)c->n_local_rows * c->W;
+  if (!c->d_conv) {
+    hipError_t e = hipMalloc(&c->d_conv, sizeof(unsigned long long) * mcpt::kStatsRecWords);
+    if (e == hipSuccess && n) e = hipMalloc(&c->d_stats, n * sizeof(float4));
+    if (e == hipSuccess && n) e = hipMalloc(&c->d_emap, n * sizeof(float2));
+    if (e != hipSuccess) {
+      free_stats(c);
+      return set_err(MCPT_ERR_HIP, "mcpt_stats_begin: hipMalloc", e);
+    }
+  }
+  HIP_OR_RETURN(mcpt_launch_stats_begin(c->d_accum, c->d_stats, (long long)n, c->stream));
+  c->stats_on = true;
+  c->stats_passes = 0;
+  c->stats_batches = 0;
+  c->emap_valid = false;
+  return MCPT_OK;
+}
+
+int mcpt_stats_end(mcpt_ctx* c) {
+  if (!c) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  HIP_OR_RETURN(hipSetDevice(c->device));
+  if (c->d_conv) HIP_OR_RETURN(hipStreamSynchronize(c->stream));   // (queued updates still use the buffers)
+  free_stats(c);
+  return MCPT_OK;
+}
+
+int mcpt_stats_add_batch(mcpt_ctx* c, int n) {
+  if (!c || n <= 0) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_stats_add_batch: a batch holds at least one pass");
+  if (!c->stats_on) return set_err(MCPT_ERR_NO_STATS, "mcpt_stats_add_batch: statistics are off (mcpt_stats_begin)");
+  HIP_OR_RETURN(hipSetDevice(c->device));
+  HIP_OR_RETURN(stats_batch(c, n));
+  return MCPT_OK;
+}
+
+int mcpt_stats_info(mcpt_ctx* c, int* on, long long* passes, int* batches) {
+  if (!c) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  if (on) *on = c->stats_on ? 1 : 0;
+  if (passes) *passes = c->stats_passes;
+  if (batches) *batches = c->stats_batches;
+  return MCPT_OK;
+}
+
+int mcpt_convergence(mcpt_ctx* c, float threshold, float mu_floor, mcpt_convergence_t* out) {
+  if (!c || !out) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  if (!(threshold > 0.0f) || !(mu_floor > 0.0f) || !std::isfinite(threshold) || !std::isfinite(mu_floor))
+    return set_err(MCPT_ERR_INVALID_ARG, "mcpt_convergence: threshold and mu_floor must be positive and finite");
+  if (!c->stats_on) return set_err(MCPT_ERR_NO_STATS, "mcpt_convergence: statistics are off (mcpt_stats_begin)");
+  if (c->stats_batches < 2) return set_err(MCPT_ERR_NO_STATS, "mcpt_convergence: needs two batches or more");
+  HIP_OR_RETURN(hipSetDevice(c->device));
+  HIP_OR_RETURN(ensure_timing_events(c->stats_ev + 2, 2));
+  const long long n = (long long)c->n_local_rows * c->W;
+  HIP_OR_RETURN(hipEventRecord(c->stats_ev[2], c->stream));
+  HIP_OR_RETURN(mcpt_launch_stats_error(c->d_stats, c->d_emap, n, c->stats_passes, c->stats_batches, mu_floor,
+                                        threshold, c->d_conv, c->stream));
+  HIP_OR_RETURN(hipEventRecord(c->stats_ev[3], c->stream));
+  c->stats_error_timed = true;
+  c->emap_valid = true;
+  unsigned long long part[mcpt::kStatsRecWords] = {};
+  HIP_OR_RETURN(hipMemcpyAsync(part, c->d_conv, sizeof(part), hipMemcpyDeviceToHost, c->stream));
+  HIP_OR_RETURN(hipStreamSynchronize(c->stream));
+  unsigned long long h[3] = {0, 0, 0};   // the partial records add (max for max_r's bits)
+  for (int s = 0; s < mcpt::kStatsRecSlots; ++s) {
+    const unsigned long long* q = part + (size_t)s * mcpt::kStatsRecStride;
+    h[0] += q[0];
+    h[1] += q[1];
+    h[2] = std::max(h[2], q[2] & 0xffffffffull);
+  }
+  out->n_px = n;
+  out->n_above = (long long)h[0];
+  out->sum_q = h[1];
+  const unsigned mb = (unsigned)(h[2] & 0xffffffffull);
+  std::memcpy(&out->max_r, &mb, sizeof(float));
+  out->mean_r = n > 0 ? (double)h[1] / 65536.0 / (double)n : 0.0;
+  out->passes = c->stats_passes;
+  out->batches = c->stats_batches;
+  return MCPT_OK;
+}
+
+int mcpt_read_error_map(mcpt_ctx* c, float* se_r2) {
+  if (!c || !se_r2) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  if (!c->stats_on || c->stats_batches < 2 || !c->emap_valid)
+    return set_err(MCPT_ERR_NO_STATS, "mcpt_read_error_map: no mcpt_convergence of the current statistics");
+  HIP_OR_RETURN(hipSetDevice(c->device));
+  const size_t n = (size_t)c->n_local_rows * c->W;
+  if (n) HIP_OR_RETURN(hipMemcpyAsync(se_r2, c->d_emap, n * sizeof(float2), hipMemcpyDeviceToHost, c->stream));
+  HIP_OR_RETURN(hipStreamSynchronize(c->stream));
+  return MCPT_OK;
+}
+
+int mcpt_last_stats_ms(mcpt_ctx* c, float* update_ms, float* error_ms) {
+  if (!c) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  HIP_OR_RETURN(hipSetDevice(c->device));
+  if (update_ms) {
+    *update_ms = 0.0f;
+    if (c->stats_update_timed) {
+      HIP_OR_RETURN(hipEventSynchronize(c->stats_ev[1]));
+      HIP_OR_RETURN(hipEventElapsedTime(update_ms, c->stats_ev[0], c->stats_ev[1]));
+    }
+  }
+  if (error_ms) {
+    *error_ms = 0.0f;
+    if (c->stats_error_timed) {
+      HIP_OR_RETURN(hipEventSynchronize(c->stats_ev[3]));
+      HIP_OR_RETURN(hipEventElapsedTime(error_ms, c->stats_ev[2], c->stats_ev[3]));
+    }
+  }
   return MCPT_OK;
 }
 

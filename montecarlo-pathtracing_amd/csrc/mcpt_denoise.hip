@@ -15,6 +15,10 @@
 //        global memory — a wave is 64 pixels of one row, so each tap is one contiguous 1 KB read
 //        per word; the taps of step >= 4 are sparse (a halo tile would be mostly unused) and
 //        neighbouring rows' re-reads are served by L2.
+//    Each has a noise-guided form (GUIDED, mcpt_denoise_guided): the colour term's
+//    kc is not the launch's constant but a value of the centre pixel, from one extra 4-byte load
+//    of its standard error (the error map of mcpt_convergence); the taps and atrous_pixel are the
+//    same.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "mcpt_device.h"
@@ -105,12 +109,21 @@ __device__ __forceinline__ float4 atrous_pixel(int x, int y, int W, int H, int s
   return make_float4(sx / wsum, sy / wsum, sz / wsum, 0.0f);
 }
 
+// kc of the centre pixel px.  Fixed sigma: the launch's kc.  GUIDED: kc carries k_color * 2^-s
+// (formed on the host, exact) and the pixel's width is that times its standard error.
+template <bool GUIDED>
+__device__ __forceinline__ float atrous_kc(float kc, const float2* __restrict__ emap, size_t px) {
+  if constexpr (!GUIDED) return kc;
+  const float sg = kc * emap[px].x;
+  return rcp_rn(sg * sg + 0x1p-40f);
+}
+
 constexpr int kAtrousTile = 16;   // LDS kernels: 16x16 pixels (2x2 waves of 8x8) + the halo
 
-template <int STEP>
+template <int STEP, bool GUIDED>
 __global__ __launch_bounds__(256) void atrous_lds_kernel(const float4* __restrict__ src, float4* __restrict__ dst,
                                                          const float4* __restrict__ guide, int W, int H, float kc,
-                                                         float kp) {
+                                                         float kp, const float2* __restrict__ emap) {
   constexpr int R = 2 * STEP, TW = kAtrousTile + 2 * R, TH = kAtrousTile + 2 * R;
   __shared__ float4 s_c[TH * TW], s_g0[TH * TW], s_g1[TH * TW];
   const int tid = threadIdx.x;
@@ -137,13 +150,15 @@ __global__ __launch_bounds__(256) void atrous_lds_kernel(const float4* __restric
     const int i = (qy - ty0 + R) * TW + (qx - tx0 + R);   // |q - p| <= R per axis: inside the staged tile
     c = s_c[i]; g0 = s_g0[i]; g1 = s_g1[i];
   };
-  dst[(size_t)y * W + x] = atrous_pixel(x, y, W, H, STEP, kc, kp, s_c[ci], s_g0[ci], s_g1[ci], fetch);
+  const size_t px = (size_t)y * W + x;
+  dst[px] = atrous_pixel(x, y, W, H, STEP, atrous_kc<GUIDED>(kc, emap, px), kp, s_c[ci], s_g0[ci], s_g1[ci], fetch);
 }
 
 // 64x4 pixels per workgroup, a wave = 64 pixels of one row
+template <bool GUIDED>
 __global__ __launch_bounds__(256) void atrous_global_kernel(const float4* __restrict__ src, float4* __restrict__ dst,
                                                             const float4* __restrict__ guide, int W, int H, int step,
-                                                            float kc, float kp) {
+                                                            float kc, float kp, const float2* __restrict__ emap) {
   const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
   if (x >= W || y >= H) return;
   auto fetch = [&](int qx, int qy, float4& c, float4& g0, float4& g1) {
@@ -151,7 +166,8 @@ __global__ __launch_bounds__(256) void atrous_global_kernel(const float4* __rest
     c = src[q]; g0 = guide[2 * q]; g1 = guide[2 * q + 1];
   };
   const size_t px = (size_t)y * W + x;
-  dst[px] = atrous_pixel(x, y, W, H, step, kc, kp, src[px], guide[2 * px], guide[2 * px + 1], fetch);
+  dst[px] = atrous_pixel(x, y, W, H, step, atrous_kc<GUIDED>(kc, emap, px), kp, src[px], guide[2 * px],
+                         guide[2 * px + 1], fetch);
 }
 
 }  // namespace mcpt
@@ -173,16 +189,25 @@ hipError_t mcpt_launch_average4(const float* accum, float4* out, long long n_px,
   return hipGetLastError();
 }
 
-hipError_t mcpt_launch_atrous(const float4* src, float4* dst, const float4* guide, int W, int H, int step, float kc,
-                              float kp, bool naive, hipStream_t stream) {
+template <bool GUIDED>
+static void launch_atrous(const float4* src, float4* dst, const float4* guide, int W, int H, int step, float kc,
+                          float kp, const float2* emap, bool naive, hipStream_t stream) {
   constexpr int T = mcpt::kAtrousTile;
   const dim3 tiles((unsigned)((W + T - 1) / T), (unsigned)((H + T - 1) / T));
   if (!naive && step == 1)
-    hipLaunchKernelGGL((mcpt::atrous_lds_kernel<1>), tiles, dim3(256), 0, stream, src, dst, guide, W, H, kc, kp);
+    hipLaunchKernelGGL((mcpt::atrous_lds_kernel<1, GUIDED>), tiles, dim3(256), 0, stream, src, dst, guide, W, H, kc, kp,
+                       emap);
   else if (!naive && step == 2)
-    hipLaunchKernelGGL((mcpt::atrous_lds_kernel<2>), tiles, dim3(256), 0, stream, src, dst, guide, W, H, kc, kp);
+    hipLaunchKernelGGL((mcpt::atrous_lds_kernel<2, GUIDED>), tiles, dim3(256), 0, stream, src, dst, guide, W, H, kc, kp,
+                       emap);
   else
-    hipLaunchKernelGGL(mcpt::atrous_global_kernel, dim3((unsigned)((W + 63) / 64), (unsigned)((H + 3) / 4)), dim3(256),
-                       0, stream, src, dst, guide, W, H, step, kc, kp);
+    hipLaunchKernelGGL((mcpt::atrous_global_kernel<GUIDED>), dim3((unsigned)((W + 63) / 64), (unsigned)((H + 3) / 4)),
+                       dim3(256), 0, stream, src, dst, guide, W, H, step, kc, kp, emap);
+}
+
+hipError_t mcpt_launch_atrous(const float4* src, float4* dst, const float4* guide, int W, int H, int step, float kc,
+                              float kp, const float2* emap, bool naive, hipStream_t stream) {
+  if (emap) launch_atrous<true>(src, dst, guide, W, H, step, kc, kp, emap, naive, stream);
+  else launch_atrous<false>(src, dst, guide, W, H, step, kc, kp, nullptr, naive, stream);
   return hipGetLastError();
 }

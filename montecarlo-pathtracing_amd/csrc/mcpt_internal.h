@@ -232,9 +232,22 @@ hipError_t mcpt_launch_guides(const mcpt::GuideParams& g, hipStream_t stream);
 // out[i] = (accum[3i .. 3i+2] / pass_count, 0): the à-trous filter's first input
 hipError_t mcpt_launch_average4(const float* accum, float4* out, long long n_px, int pass_count, hipStream_t stream);
 // one à-trous iteration over a full W x H frame; naive: every tap from global
-// memory whatever the step (the A/B baseline of the LDS kernels; same bits)
+// memory whatever the step (the A/B baseline of the LDS kernels; same bits).  emap null: kc is the
+// colour term's constant; else the noise-guided form: kc = k_color * 2^-s and
+// emap the per-pixel {se, r} of mcpt_launch_stats_error
 hipError_t mcpt_launch_atrous(const float4* src, float4* dst, const float4* guide, int W, int H, int step, float kc,
-                              float kp, bool naive, hipStream_t stream);
+                              float kp, const float2* emap, bool naive, hipStream_t stream);
+// noise statistics (mcpt_stats.hip): per local pixel one float4 {Yacc, S2, Ybase, 0}
+hipError_t mcpt_launch_stats_begin(const float* accum, float4* state, long long n_px, hipStream_t stream);
+hipError_t mcpt_launch_stats_update(const float* accum, float4* state, long long n_px, int n, hipStream_t stream);
+// zeroes rec (mcpt::kStatsRecWords u64: kStatsRecSlots partial records {n_above, sum_q, max_r's
+// bits} at a stride of one 128-byte line; the frame's record is their sum / max), then writes emap
+// and reduces into rec
+namespace mcpt {
+constexpr int kStatsRecSlots = 32, kStatsRecStride = 16, kStatsRecWords = kStatsRecSlots * kStatsRecStride;
+}
+hipError_t mcpt_launch_stats_error(const float4* state, float2* emap, long long n_px, long long passes, int batches,
+                                   float mu_floor, float threshold, unsigned long long* rec, hipStream_t stream);
 hipError_t mcpt_launch_render(const mcpt::RenderParams& p, bool count, hipStream_t stream);
 hipError_t mcpt_launch_combine(const mcpt::RenderParams& p, hipStream_t stream);
 hipError_t mcpt_iota(int* a, int n, hipStream_t stream);

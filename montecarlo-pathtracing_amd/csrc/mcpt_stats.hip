@@ -1,0 +1,141 @@
+// mcpt_stats.hip — per-pixel noise statistics of a progressive render and its convergence
+// metric (no reference equivalent: the reference accumulates and averages).
+//
+// The statistics are batch means over render calls: nothing here touches a render launch, the
+// kernels read the accumulator between calls on the context's stream.
+//  * stats_begin_kernel / stats_update_kernel: one lane per pixel; the pixel's state is one
+//    16-byte word {Yacc, S2, Ybase, 0}.  Traffic of an update: 12 B of accumulator and 16 B of
+//    state read, 16 B written.
+//  * error_kernel: one lane per pixel and grid step; {se, r} per pixel and the frame record
+//    (n_above, sum_q, max_r).  The record's sums are integers (q = trunc(r * 2^16), r <= 64) and
+//    max_r is reduced as the bit pattern of a non-negative float, so the order of the wave
+//    shuffles, the LDS step and the atomics does not show in the bits.  One set of atomics per
+//    workgroup; the grid is capped (kErrorMaxBlocks: a 4K frame issues ~6,000 atomics, not
+//    ~100,000) and the workgroups spread them over kStatsRecSlots partial records, one 128-byte
+//    line each, which the host adds (1080p: 18 us; with every workgroup's atomics on one record
+//    86 us: profiles/stats_bench.json, profiles/stats_bench_one_record.json).
+// All of it binary32 without contraction: + - * /, comparisons, sqrt_rn.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <algorithm>
+
+#include "mcpt_internal.h"
+#include "mcpt_math.h"
+
+namespace mcpt {
+
+// luminance of an accumulator pixel (the sums, not the averages)
+__device__ __forceinline__ float accum_luminance(const float* __restrict__ accum, long long i) {
+  return (0.2126f * accum[3 * i] + 0.7152f * accum[3 * i + 1]) + 0.0722f * accum[3 * i + 2];
+}
+
+__global__ __launch_bounds__(256) void stats_begin_kernel(const float* __restrict__ accum, float4* __restrict__ st,
+                                                          long long n_px) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_px) return;
+  const float y = accum_luminance(accum, i);
+  st[i] = make_float4(y, 0.0f, y, 0.0f);
+}
+
+// "the accumulator now holds n more passes than at the previous batch" (nf = (float)n)
+__global__ __launch_bounds__(256) void stats_update_kernel(const float* __restrict__ accum, float4* __restrict__ st,
+                                                           long long n_px, float nf) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_px) return;
+  float4 s = st[i];
+  const float ynow = accum_luminance(accum, i);
+  const float d = ynow - s.x;
+  s.y = s.y + (d * d) / nf;
+  s.x = ynow;
+  st[i] = s;
+}
+
+__device__ __forceinline__ bool finite32(float x) { return __builtin_fabsf(x) < __builtin_inff(); }   // (false for NaN)
+
+constexpr int kErrorMaxBlocks = 2048;   // 8 workgroups per CU of a 256-CU chip
+
+// rec: kStatsRecSlots partial records of kStatsRecStride words, workgroup b adds into slot
+// b % kStatsRecSlots: [0] n_above, [1] sum_q (64-bit adds), [2] max_r's bits (a 32-bit max on the
+// word's low half)
+__global__ __launch_bounds__(256) void error_kernel(const float4* __restrict__ st, float2* __restrict__ emap,
+                                                    long long n_px, float nf, float bm1f, float mu_floor,
+                                                    float threshold, unsigned long long* __restrict__ rec) {
+  __shared__ unsigned long long s_above[4], s_q[4];
+  __shared__ unsigned s_max[4];
+  // a lane's sums over its grid steps (q <= 2^22 per pixel, up to 2^31 / (2048 x 256) pixels per
+  // lane once the grid cap binds): 64-bit from the start
+  unsigned long long above = 0, qsum = 0;
+  unsigned rmax = 0;
+  const long long stride = (long long)gridDim.x * 256;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n_px; i += stride) {
+    const float4 s = st[i];
+    const float s1 = s.x - s.z;
+    float v = s.y - (s1 * s1) / nf;
+    v = (0.0f < v) ? v : 0.0f;
+    const float var = v / bm1f;
+    const float se = sqrt_rn(var / nf);
+    const float mu = s1 / nf;
+    float r = se / (gmax(0.0f, mu) + mu_floor);
+    if (!finite32(s.y) || !finite32(s1) || !(r <= 64.0f)) r = 64.0f;
+    emap[i] = make_float2(se, r);
+    above += (r > threshold) ? 1u : 0u;
+    qsum += (unsigned)(r * 65536.0f);
+    const unsigned rb = __float_as_uint(r);   // r >= 0: the bits order as the values
+    rmax = rb > rmax ? rb : rmax;
+  }
+  // idle lanes (past the frame's end) hold the sums' neutral elements and take part in the shuffles
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    above += __shfl_down(above, off, 64);
+    qsum += __shfl_down(qsum, off, 64);
+    const unsigned o = __shfl_down(rmax, off, 64);
+    rmax = o > rmax ? o : rmax;
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) {
+    s_above[wave] = above;
+    s_q[wave] = qsum;
+    s_max[wave] = rmax;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long a = 0, q = 0;
+    unsigned m = 0;
+    for (int w = 0; w < 4; ++w) {
+      a += s_above[w];
+      q += s_q[w];
+      m = s_max[w] > m ? s_max[w] : m;
+    }
+    unsigned long long* slot = rec + (size_t)(blockIdx.x % kStatsRecSlots) * kStatsRecStride;
+    if (a) atomicAdd(slot + 0, a);
+    if (q) atomicAdd(slot + 1, q);
+    if (m) atomicMax(reinterpret_cast<unsigned*>(slot + 2), m);
+  }
+}
+
+}  // namespace mcpt
+
+hipError_t mcpt_launch_stats_begin(const float* accum, float4* state, long long n_px, hipStream_t stream) {
+  if (n_px <= 0) return hipSuccess;
+  hipLaunchKernelGGL(mcpt::stats_begin_kernel, dim3((unsigned)((n_px + 255) / 256)), dim3(256), 0, stream, accum,
+                     state, n_px);
+  return hipGetLastError();
+}
+
+hipError_t mcpt_launch_stats_update(const float* accum, float4* state, long long n_px, int n, hipStream_t stream) {
+  if (n_px <= 0) return hipSuccess;
+  hipLaunchKernelGGL(mcpt::stats_update_kernel, dim3((unsigned)((n_px + 255) / 256)), dim3(256), 0, stream, accum,
+                     state, n_px, (float)n);
+  return hipGetLastError();
+}
+
+hipError_t mcpt_launch_stats_error(const float4* state, float2* emap, long long n_px, long long passes, int batches,
+                                   float mu_floor, float threshold, unsigned long long* rec, hipStream_t stream) {
+  hipError_t e = hipMemsetAsync(rec, 0, sizeof(unsigned long long) * mcpt::kStatsRecWords, stream);
+  if (e != hipSuccess || n_px <= 0) return e;
+  const long long blocks = (n_px + 255) / 256;
+  hipLaunchKernelGGL(mcpt::error_kernel, dim3((unsigned)std::min<long long>(blocks, mcpt::kErrorMaxBlocks)), dim3(256),
+                     0, stream, state, emap, n_px, (float)passes, (float)(batches - 1), mu_floor, threshold, rec);
+  return hipGetLastError();
+}

@@ -28,6 +28,7 @@ __all__ = [
     "MONTECARLO", "MAT", "MAT_TR", "EVENT_NAMES", "SCENE_KEYS",
     "TRAVERSAL_AUTO", "TRAVERSAL_LANE", "TRAVERSAL_WAVE", "TRAVERSAL_STREAM",
     "Transfo", "average", "write_pfm", "write_png", "material", "light", "Hit", "HIT_DTYPE",
+    "Convergence", "DENOISE_K_COLOR", "ERROR_MU_FLOOR",
 ]
 
 MONTECARLO, MAT, MAT_TR = 0, 1, 2
@@ -48,10 +49,23 @@ DEBUG_SLOTS = 64   # MCPT_DEBUG_SLOTS
 # the denoiser's default edge-stopping widths (chosen by the sweep of DESIGN.md §3.7)
 DENOISE_SIGMA_COLOR = 4.0
 DENOISE_SIGMA_PLANE = 1.0
+# the noise-guided filter's colour width in standard errors of the pixel (the sweep of DESIGN.md §3.8)
+DENOISE_K_COLOR = 64.0
+# the relative error's floor on the mean luminance: pixels darker than this are
+# measured against it, so that black pixels do not hold a render back
+ERROR_MU_FLOOR = 0.01
+NO_STATS = -8      # MCPT_ERR_NO_STATS
 
 
 class MCPTError(RuntimeError):
     pass
+
+
+class Convergence(ctypes.Structure):
+    """mcpt_convergence_t (include/mcpt.h): the frame record of a convergence query."""
+    _fields_ = [("n_px", ctypes.c_longlong), ("n_above", ctypes.c_longlong), ("sum_q", ctypes.c_ulonglong),
+                ("max_r", ctypes.c_float), ("mean_r", ctypes.c_double), ("passes", ctypes.c_longlong),
+                ("batches", ctypes.c_int)]
 
 
 class Hit(ctypes.Structure):
@@ -162,6 +176,14 @@ def _declare(L: ctypes.CDLL) -> None:
         "mcpt_last_denoise_ms": (i, [_vp, fp, fp]),
         "mcpt_denoise_iteration_ms": (i, [_vp, i, fp]),
         "mcpt_last_denoise_path": (i, [_vp, ip]),
+        "mcpt_stats_begin": (i, [_vp]),
+        "mcpt_stats_end": (i, [_vp]),
+        "mcpt_stats_add_batch": (i, [_vp, i]),
+        "mcpt_stats_info": (i, [_vp, ip, ctypes.POINTER(ctypes.c_longlong), ip]),
+        "mcpt_convergence": (i, [_vp, f, f, ctypes.POINTER(Convergence)]),
+        "mcpt_read_error_map": (i, [_vp, fp]),
+        "mcpt_denoise_guided": (i, [_vp, i, f, f]),
+        "mcpt_last_stats_ms": (i, [_vp, fp, fp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -656,6 +678,89 @@ class Renderer:
         m = ctypes.c_int()
         _check(lib().mcpt_last_denoise_path(self._h, ctypes.byref(m)), "mcpt_last_denoise_path")
         return m.value
+
+    # ---- noise statistics, convergence and the noise-guided filter (mcpt.h)
+    def stats_begin(self) -> None:
+        """mcpt_stats_begin: start a statistics window at the accumulator as it is (asynchronous);
+        from now on every render call is one batch."""
+        _check(lib().mcpt_stats_begin(self._h), "mcpt_stats_begin")
+
+    def stats_end(self) -> None:
+        """mcpt_stats_end: statistics off, their buffers freed."""
+        _check(lib().mcpt_stats_end(self._h), "mcpt_stats_end")
+
+    def stats_add_batch(self, n: int) -> None:
+        """mcpt_stats_add_batch: the accumulator holds n more passes than at the previous batch
+        (after write_accum / load_checkpoint / gather_rows; render calls declare theirs)."""
+        _check(lib().mcpt_stats_add_batch(self._h, int(n)), "mcpt_stats_add_batch")
+
+    def stats_info(self) -> dict:
+        """{"on", "passes", "batches"} of the statistics window."""
+        on, b, n = ctypes.c_int(), ctypes.c_int(), ctypes.c_longlong()
+        _check(lib().mcpt_stats_info(self._h, ctypes.byref(on), ctypes.byref(n), ctypes.byref(b)), "mcpt_stats_info")
+        return {"on": bool(on.value), "passes": n.value, "batches": b.value}
+
+    def convergence(self, threshold: float, mu_floor: float = ERROR_MU_FLOOR) -> dict:
+        """mcpt_convergence: the frame record {n_px, n_above (r > threshold), sum_q, max_r, mean_r,
+        passes, batches} of the local pixels' relative errors; writes the error map.  Synchronizes."""
+        rec = Convergence()
+        _check(lib().mcpt_convergence(self._h, float(threshold), float(mu_floor), ctypes.byref(rec)), "mcpt_convergence")
+        return {k: getattr(rec, k) for k, _ in Convergence._fields_}
+
+    def read_error_map(self) -> np.ndarray:
+        """(local rows, W, 2) f32: {standard error of the mean luminance, relative error r} of the
+        last convergence()."""
+        out = np.zeros((self.n_local_rows, self.W, 2), np.float32)
+        _check(lib().mcpt_read_error_map(self._h, _fp(out)), "mcpt_read_error_map")
+        return out
+
+    def denoise_guided(self, iterations: int = 5, k_color: float = DENOISE_K_COLOR,
+                       sigma_plane: float = DENOISE_SIGMA_PLANE) -> np.ndarray:
+        """mcpt_denoise_guided + mcpt_read_denoised: denoise() with the colour width per pixel,
+        k_color standard errors of that pixel (needs render_guides and a convergence() first)."""
+        _check(lib().mcpt_denoise_guided(self._h, int(iterations), float(k_color), float(sigma_plane)),
+               "mcpt_denoise_guided")
+        out = np.zeros((self.n_local_rows, self.W, 3), np.float32)
+        _check(lib().mcpt_read_denoised(self._h, _fp(out)), "mcpt_read_denoised")
+        return out
+
+    def last_stats_ms(self) -> Tuple[float, float]:
+        """(batch update ms, error kernel ms) of the last of each (0: none yet)."""
+        u, e = ctypes.c_float(), ctypes.c_float()
+        _check(lib().mcpt_last_stats_ms(self._h, ctypes.byref(u), ctypes.byref(e)), "mcpt_last_stats_ms")
+        return u.value, e.value
+
+    def render_until(self, invPV, invV, target_error: float, batch: int = 32, max_passes: int = 4096,
+                     check_every: int = 4, first_pass: int = 1, date: float = 0.0, bounces: int = 3,
+                     refract_ind: float = 1.0, variant: int = MONTECARLO, threshold: Optional[float] = None,
+                     mu_floor: float = ERROR_MU_FLOOR) -> dict:
+        """Render passes first_pass, first_pass + 1, ... in calls of `batch` passes until the mean
+        relative error is at most `target_error` or `max_passes` passes are rendered.  The
+        convergence is queried after every `check_every` calls (and at the cap), the calls in
+        between are queued without a wait, so that render lanes keep overlapping.  Begins a
+        statistics window unless one is on (then its batches count too).  Returns the last
+        convergence record plus "rendered" (this call's passes) and "converged"; `threshold`
+        (n_above's bound) defaults to target_error."""
+        if batch <= 0 or check_every <= 0 or max_passes <= 0 or not target_error > 0:
+            raise MCPTError("render_until: batch, check_every, max_passes and target_error must be positive")
+        if not self.stats_info()["on"]:
+            self.stats_begin()
+        thr = target_error if threshold is None else threshold
+        done, calls, rec = 0, 0, None
+        while done < max_passes:
+            n = min(batch, max_passes - done)
+            self.render(invPV, invV, first_pass + done, n, date, bounces, refract_ind, variant)
+            done += n
+            calls += 1
+            if (calls % check_every == 0 or done >= max_passes) and self.stats_info()["batches"] >= 2:
+                rec = self.convergence(thr, mu_floor)
+                if rec["mean_r"] <= target_error:
+                    break
+        if rec is None:
+            rec = self.convergence(thr, mu_floor)     # (fewer than two batches: MCPT_ERR_NO_STATS)
+        rec["rendered"] = done
+        rec["converged"] = rec["mean_r"] <= target_error
+        return rec
 
     def trace(self, origins, dirs, any_hit: bool = False, prim: int = -1) -> np.ndarray:
         """Ray queries (traverse_all_bvh / just_hit_bvh, or one primitive) + intersection_info.
