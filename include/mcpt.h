@@ -36,6 +36,7 @@ enum mcpt_status {
   MCPT_ERR_BAD_SCENE = -6,
   MCPT_ERR_NO_GUIDES = -7,   /* mcpt_denoise / mcpt_read_guides without current guide buffers */
   MCPT_ERR_NO_STATS = -8,    /* a statistics query with statistics off, fewer than two batches or no error map */
+  MCPT_ERR_NO_ADAPTIVE = -9, /* an adaptive-sampling call with the adaptive mode off (mcpt_adaptive_begin) */
 };
 
 /* integrator variants: the SrcLoader list of MontecarloGPU/montecarlo.cpp:27 */
@@ -393,6 +394,71 @@ int mcpt_convergence(mcpt_ctx* ctx, float threshold, float mu_floor, mcpt_conver
 int mcpt_read_error_map(mcpt_ctx* ctx, float* se_r2);
 int mcpt_denoise_guided(mcpt_ctx* ctx, int iterations, float k_color, float sigma_plane);
 int mcpt_last_stats_ms(mcpt_ctx* ctx, float* update_ms, float* error_ms);
+
+/* Adaptive sampling of 8x8 pixel blocks guided by the error map (no reference
+ * equivalent).  Opt-in, on top of the noise statistics; with the mode off nothing changes.
+ *
+ * A block is 8 local rows x 8 columns of the local grid (a wave of the render kernel):
+ * blocks_x = ceil(W / 8), blocks_y = ceil(local rows / 8), id = by * blocks_x + bx; any target, row
+ * shards included.  While the mode is on a block holds an active flag and the passes rendered into
+ * it since mcpt_adaptive_begin; a pixel's sample count is the accumulator's pass count at
+ * mcpt_adaptive_begin plus its block's passes.  Blocks only ever leave the active set, so an active
+ * block has received every pass so far and every pixel holds, bit for bit, what a uniform render
+ * of the same calls held after that pixel's sample count.  Device memory: 12 B per
+ * block, allocated by mcpt_adaptive_begin, freed by mcpt_adaptive_end, mcpt_stats_end, the next
+ * mcpt_set_target* (all of which turn the mode off) and mcpt_destroy.
+ *
+ * mcpt_adaptive_begin: needs statistics on (else MCPT_ERR_NO_STATS); every block active, zero
+ * passes; a block is not retired before it holds min_passes (>= 0) passes.  Asynchronous.
+ * mcpt_adaptive_select: for every active block the {se, r} of its pixels as mcpt_convergence
+ * computes them, written to the error map; the block stays active iff its largest r > threshold or
+ * it holds fewer than min_passes passes.  Retired blocks are not computed, keep their map entries
+ * and never return.  The record is mcpt_convergence's over all local pixels (fresh values of active
+ * blocks, stored ones of retired blocks) plus n_active_blocks, n_blocks and samples = the sum of
+ * all pixels' sample counts.  Arguments and preconditions as mcpt_convergence; synchronizes.
+ * mcpt_read_error_map reads the map.  mcpt_convergence itself is unchanged and knows nothing of
+ * retired blocks (their window sums stop growing while the window's pass count does not): with the
+ * adaptive mode on, use mcpt_adaptive_select.
+ * mcpt_read_active_blocks: the active block ids of the last select (all blocks before the first),
+ * ascending; *n = how many, at most `capacity` of them copied.
+ * mcpt_render_adaptive: mcpt_render for the active blocks only, on the context's stream; their pass
+ * counts and the context's pass count grow by n_passes, and the call is one statistics batch.  An
+ * empty list launches nothing, changes nothing and returns MCPT_OK.  The schedule (AUTO's trials,
+ * work-item order, render lanes, mcpt_last_render_ms) takes no part and is left as it was.
+ * A plain mcpt_render while the mode is on is allowed: it renders every pixel and adds n_passes to
+ * every block's count, retired ones too.
+ * mcpt_read_sample_counts: n_local ints, a pixel's sample count.  mcpt_read_resolved: n_local x 3
+ * f32, accum / (float)count per channel (mcpt_average's division with the pixel's own count).
+ * mcpt_adaptive_info: any pointer may be NULL (0 / 0 / 0 with the mode off).
+ * mcpt_last_adaptive_ms: device times (HIP events) of the last select (with its list scan) and the
+ * last adaptive render (with its combines); 0 for what has not run.  Waits for them.
+ * With the mode off the other calls return MCPT_ERR_NO_ADAPTIVE.
+ *
+ * Out of scope: mcpt_denoise*, mcpt_checkpoint_save, mcpt_gather_rows, mcpt_read_accum's pass count
+ * and mcpt_clear_accum / mcpt_write_accum know nothing of per-pixel counts (end the mode before
+ * replacing the accumulator).  Once a block has retired, mcpt_denoise and mcpt_denoise_guided
+ * return MCPT_ERR_INVALID_ARG instead of an image divided by the wrong count.  Checkpoints and
+ * multi-GPU gathers of adaptive frames are later work. */
+typedef struct mcpt_adaptive_t {
+  long long n_px, n_above;
+  unsigned long long sum_q;
+  float max_r;
+  double mean_r;
+  long long passes;
+  int batches;
+  long long n_active_blocks, n_blocks;
+  long long samples;
+} mcpt_adaptive_t;
+int mcpt_adaptive_begin(mcpt_ctx* ctx, int min_passes);
+int mcpt_adaptive_end(mcpt_ctx* ctx);
+int mcpt_adaptive_select(mcpt_ctx* ctx, float threshold, float mu_floor, mcpt_adaptive_t* out);
+int mcpt_read_active_blocks(mcpt_ctx* ctx, int* ids, int capacity, int* n);
+int mcpt_render_adaptive(mcpt_ctx* ctx, const float* invPV, const float* invV, int first_pass, int n_passes,
+                         float date, int bounces, float refract_ind, int variant);
+int mcpt_read_sample_counts(mcpt_ctx* ctx, int* counts);
+int mcpt_read_resolved(mcpt_ctx* ctx, float* rgb);
+int mcpt_adaptive_info(mcpt_ctx* ctx, int* on, long long* n_active, long long* n_blocks);
+int mcpt_last_adaptive_ms(mcpt_ctx* ctx, float* select_ms, float* render_ms);
 
 /* DrawSampling's point cloud (DrawSampling/draw_sampling.cpp:144-150, tp/sampling_base.vert
  * seeding, tp/hsphere.vert random_ray): point k = random_ray(normalize(normal), roughness)

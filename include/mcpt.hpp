@@ -477,6 +477,76 @@ class Renderer {
     if (rendered) *rendered = done;
     return rec;
   }
+  // adaptive sampling of 8x8 blocks (mcpt.h)
+  void adaptive_begin(int min_passes = 0) { check(mcpt_adaptive_begin(c_, min_passes), "mcpt_adaptive_begin"); }
+  void adaptive_end() { check(mcpt_adaptive_end(c_), "mcpt_adaptive_end"); }
+  mcpt_adaptive_t adaptive_select(float threshold, float mu_floor = kErrorMuFloor) {
+    mcpt_adaptive_t rec;
+    check(mcpt_adaptive_select(c_, threshold, mu_floor, &rec), "mcpt_adaptive_select");
+    return rec;
+  }
+  struct AdaptiveInfo { bool on; long long n_active, n_blocks; };
+  AdaptiveInfo adaptive_info() const {
+    int on = 0; long long a = 0, b = 0;
+    check(mcpt_adaptive_info(c_, &on, &a, &b), "mcpt_adaptive_info");
+    return AdaptiveInfo{on != 0, a, b};
+  }
+  // the active block ids, ascending
+  std::vector<int> read_active_blocks() const {
+    std::vector<int> ids((size_t)adaptive_info().n_blocks + 1);
+    int n = 0;
+    check(mcpt_read_active_blocks(c_, ids.data(), (int)ids.size(), &n), "mcpt_read_active_blocks");
+    ids.resize((size_t)n);
+    return ids;
+  }
+  void render_adaptive(const Camera& cam, int first_pass, int n_passes, float date, int bounces, float refract_ind,
+                       int variant = MCPT_MONTECARLO) {
+    check(mcpt_render_adaptive(c_, cam.invPV.m, cam.invV.m, first_pass, n_passes, date, bounces, refract_ind, variant),
+          "mcpt_render_adaptive");
+  }
+  // local pixels: every pixel's sample count / accum / (float)count
+  std::vector<int> read_sample_counts() const {
+    std::vector<int> n((size_t)rows_ * W_);
+    check(mcpt_read_sample_counts(c_, n.data()), "mcpt_read_sample_counts");
+    return n;
+  }
+  std::vector<float> read_resolved() const {
+    std::vector<float> img((size_t)rows_ * W_ * 3);
+    check(mcpt_read_resolved(c_, img.data()), "mcpt_read_resolved");
+    return img;
+  }
+  void last_adaptive_ms(float& select_ms, float& render_ms) const {
+    check(mcpt_last_adaptive_ms(c_, &select_ms, &render_ms), "mcpt_last_adaptive_ms");
+  }
+  // Begin a statistics window and the adaptive mode, render calls of `batch` passes for the active
+  // blocks only, select after every check_every calls (from the second on, and at the cap) until no
+  // block is active or max_passes are rendered.  The mode stays on (read_resolved, read_sample_counts).
+  mcpt_adaptive_t render_adaptive_until(const Camera& cam, float threshold, int batch = 32, int max_passes = 4096,
+                                        int min_passes = 0, int check_every = 1, int first_pass = 1,
+                                        float date = 0.0f, int bounces = 3, float refract_ind = 1.0f,
+                                        int variant = MCPT_MONTECARLO, int* rendered = nullptr,
+                                        float mu_floor = kErrorMuFloor) {
+    if (batch <= 0 || check_every <= 0 || max_passes <= 0 || !(threshold > 0.0f))
+      throw std::runtime_error("render_adaptive_until: batch, check_every, max_passes and threshold must be positive");
+    stats_begin();
+    adaptive_begin(min_passes);
+    mcpt_adaptive_t rec;
+    bool have = false;
+    int done = 0;
+    for (int calls = 1; done < max_passes; ++calls) {
+      const int n = batch < max_passes - done ? batch : max_passes - done;
+      render_adaptive(cam, first_pass + done, n, date, bounces, refract_ind, variant);
+      done += n;
+      if (calls >= 2 && (calls % check_every == 0 || done >= max_passes)) {
+        rec = adaptive_select(threshold, mu_floor);
+        have = true;
+        if (rec.n_active_blocks == 0) break;
+      }
+    }
+    if (!have) rec = adaptive_select(threshold, mu_floor);   // (fewer than two batches: MCPT_ERR_NO_STATS)
+    if (rendered) *rendered = done;
+    return rec;
+  }
   void set_traversal(int mode) { check(mcpt_set_traversal(c_, mode), "mcpt_set_traversal"); }
   // render lanes (consecutive launches overlapping each other's tails; same bits): on by default
   void set_render_lanes(bool on) { check(mcpt_set_render_lanes(c_, on ? 1 : 0), "mcpt_set_render_lanes"); }

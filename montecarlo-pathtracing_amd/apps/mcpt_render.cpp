@@ -43,6 +43,7 @@ struct Args {
   std::string aov;            // --aov PREFIX: PREFIX_normal.pfm, _albedo.pfm, _depth.pfm (+ _error.pfm with statistics)
   double target_error = 0.0;  // --target-error E: stop once the mean relative error <= E (--spp: the cap; 0: off)
   int denoise_guided = -1;    // --denoise-guided [N]: the noise-guided filter (-1: off; N defaults to 5)
+  bool adaptive = false;      // --adaptive: --target-error is the per-pixel threshold; retired 8x8 blocks stop receiving passes
 };
 
 bool parse_list(const char* v, std::vector<int>& out) {
@@ -71,6 +72,9 @@ void usage() {
                "                                      PREFIX_error.pfm = {se, r, 0} with noise statistics)\n"
                "                   [--target-error E]   (one device: render chunks of --chunk passes until the mean\n"
                "                                         relative error <= E, at most --spp passes)\n"
+               "                   [--adaptive]   (with --target-error: E is the per-pixel threshold on r; 8x8 blocks\n"
+               "                                   whose largest r <= E stop receiving passes; --aov also writes\n"
+               "                                   PREFIX_samples.pfm; the image is accum / each pixel's own count)\n"
                "                   [--denoise-guided [N]]   (one device: the a-trous filter with the colour width\n"
                "                                             from each pixel's standard error; >= 2 chunks)\n");
 }
@@ -83,6 +87,10 @@ bool parse(int argc, char** argv, Args& a) {
       a.denoise = 5;
       if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') a.denoise = std::atoi(argv[++i]);
       if (a.denoise > 8) return false;
+      continue;
+    }
+    if (k == "--adaptive") {
+      a.adaptive = true;
       continue;
     }
     if (k == "--denoise-guided") {
@@ -134,6 +142,10 @@ bool parse(int argc, char** argv, Args& a) {
   if (!a.devices.empty() && (!a.checkpoint.empty() || !a.resume.empty())) return false;   // one device only
   if (!a.devices.empty() && (a.target_error > 0.0 || a.denoise_guided >= 0)) return false;  // (statistics: one device)
   if (a.denoise >= 0 && a.denoise_guided >= 0) return false;                                // one filter
+  // adaptive sampling: one device, a threshold, no filter (per-pixel counts), no checkpoint
+  if (a.adaptive && (!(a.target_error > 0.0) || !a.devices.empty() || a.denoise >= 0 || a.denoise_guided >= 0 ||
+                     !a.checkpoint.empty() || !a.resume.empty()))
+    return false;
   return a.width > 0 && a.height > 0 && a.spp >= 0 && a.chunk > 0 && a.subsampling >= 0 && a.subsampling < 16;
 }
 
@@ -157,8 +169,14 @@ void post_process(const Args& a, mcpt::Renderer& r, const mcpt::Camera& cam, int
     mcpt::write_pfm(a.aov + "_albedo.pfm", albedo, W, H);
     mcpt::write_pfm(a.aov + "_depth.pfm", depth, W, H);
   }
+  if (a.adaptive && !a.aov.empty()) {   // every pixel's sample count
+    const std::vector<int> cnt = r.read_sample_counts();
+    std::vector<float> smp(cnt.size() * 3);
+    for (size_t i = 0; i < cnt.size(); ++i) smp[3 * i] = smp[3 * i + 1] = smp[3 * i + 2] = (float)cnt[i];
+    mcpt::write_pfm(a.aov + "_samples.pfm", smp, W, H);
+  }
   if (r.stats_info().batches >= 2) {   // noise statistics on: the error map (of the final state) and its filter
-    r.convergence(a.target_error > 0.0 ? (float)a.target_error : 0.05f);
+    if (!a.adaptive) r.convergence(a.target_error > 0.0 ? (float)a.target_error : 0.05f);   // (adaptive: the last select's map)
     if (!a.aov.empty()) {
       const std::vector<float> m = r.read_error_map();
       const size_t n = (size_t)W * H;
@@ -222,7 +240,24 @@ int main(int argc, char** argv) {
       mcpt_convergence_t rec{};
       bool have_rec = false, converged = false;
       int calls = 0;
-      for (int done = next - a.first_pass; done < a.spp && !converged; done += a.chunk) {
+      mcpt_adaptive_t arec{};
+      bool have_arec = false;
+      if (a.adaptive) r.adaptive_begin(0);
+      for (int done = 0; a.adaptive && done < a.spp && !converged; done += a.chunk) {
+        // adaptive sampling: the active blocks only, a select after every chunk from the second on
+        const int n = std::min(a.chunk, a.spp - done);
+        r.render_adaptive(cam, a.first_pass + done, n, a.date, a.bounces, a.ior, a.variant);
+        float sel = 0.0f, ren = 0.0f;
+        r.last_adaptive_ms(sel, ren);
+        kernel_ms += ren;
+        rendered = done + n;
+        if (++calls >= 2) {
+          arec = r.adaptive_select((float)a.target_error);
+          have_arec = true;
+          converged = arec.n_active_blocks == 0;
+        }
+      }
+      for (int done = next - a.first_pass; !a.adaptive && done < a.spp && !converged; done += a.chunk) {
         const int n = std::min(a.chunk, a.spp - done);
         r.render(cam, a.first_pass + done, n, a.date, a.bounces, a.ior, a.variant);
         kernel_ms += r.last_render_ms();
@@ -235,9 +270,26 @@ int main(int argc, char** argv) {
           converged = rec.mean_r <= a.target_error;
         }
       }
-      img = r.read_image();
+      img = a.adaptive ? r.read_resolved() : r.read_image();
       if (post) post_process(a, r, cam, W, H, img, guides_ms, filter_ms);
-      if (a.target_error > 0.0) {
+      if (a.adaptive) {
+        char buf[400];
+        if (have_arec)
+          std::snprintf(buf, sizeof(buf),
+                        ", \"adaptive\": true, \"target_error\": %g, \"converged\": %s, \"window_passes\": %lld, "
+                        "\"batches\": %d, \"mean_r\": %.6f, \"max_r\": %.6f, \"n_above\": %lld, \"n_px\": %lld, "
+                        "\"sum_q\": %llu, \"samples\": %lld, \"n_active_blocks\": %lld, \"n_blocks\": %lld, "
+                        "\"mean_spp\": %.4f",
+                        a.target_error, converged ? "true" : "false", arec.passes, arec.batches, arec.mean_r, arec.max_r,
+                        arec.n_above, arec.n_px, arec.sum_q, arec.samples, arec.n_active_blocks, arec.n_blocks,
+                        arec.n_px > 0 ? (double)arec.samples / (double)arec.n_px : 0.0);
+        else   // fewer than two chunks: no select, every block active
+          std::snprintf(buf, sizeof(buf),
+                        ", \"adaptive\": true, \"target_error\": %g, \"converged\": false, \"mean_r\": null, "
+                        "\"samples\": %lld, \"n_active_blocks\": %lld, \"mean_spp\": %.4f",
+                        a.target_error, (long long)W * H * rendered, r.adaptive_info().n_active, (double)rendered);
+        shard_json += buf;
+      } else if (a.target_error > 0.0) {
         char buf[320];
         if (have_rec)
           std::snprintf(buf, sizeof(buf),

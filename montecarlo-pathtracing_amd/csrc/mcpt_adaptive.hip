@@ -1,0 +1,248 @@
+// mcpt_adaptive.hip — adaptive sampling of 8x8 pixel blocks guided by the error map (DESIGN.md
+// §3.9; no reference equivalent: the reference renders every pixel in every pass).
+//
+// A block is the render kernel's wave: 8 local rows x 8 columns of the local grid, id = by *
+// blocks_x + bx.  While the mode is on a block holds an active flag and the passes rendered into it
+// since mcpt_adaptive_begin; blocks only ever leave the active set.
+//  * select_kernel: one wave per block (grid capped, waves step over the blocks).  An active block's
+//    pixels get §3.8's {se, r} from the statistics state (pixel_error, mcpt_stats_err.h: the error
+//    kernel's arithmetic) written to the error map; the block stays active iff its largest r exceeds
+//    the threshold or it holds fewer than min_passes passes.  A retired block's pixels are not
+//    computed: their stored map entries enter the frame record.  The record's sums are integers and
+//    max_r a bit pattern, reduced per wave, per workgroup and into kStatsRecSlots partial records as
+//    the error kernel's are: the bits do not depend on the order.
+//  * compact_kernel: the active block ids, ascending, by a single-workgroup scan over the flags
+//    (ballots inside a wave, the waves' counts through LDS, a running base): no atomic append, so
+//    the list does not depend on timing.  4K has 129,600 blocks: 127 steps of 1,024.
+//  * combine_list_kernel: one wave per listed block adds the block's segment sums to the
+//    accumulator in chunk order (combine_kernel's sequence per pixel); unlisted pixels' segment
+//    slots are unwritten and are not read.
+//  * add_passes / counts / resolve: the per-block pass counts, the per-pixel sample counts p0 +
+//    passes[block], and accum / (float)count per channel (mcpt_average's single division).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <algorithm>
+
+#include "mcpt_internal.h"
+#include "mcpt_math.h"
+#include "mcpt_stats_err.h"
+
+namespace mcpt {
+
+constexpr int kSelectMaxBlocks = 2048;   // workgroups of four waves (the error kernel's grid cap)
+
+__global__ __launch_bounds__(256) void adaptive_reset_kernel(AdaptiveTarget t, int* __restrict__ list,
+                                                             int* __restrict__ count) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b == 0) count[0] = t.n_blocks;
+  if (b >= t.n_blocks) return;
+  t.flags[b] = 1;
+  t.passes[b] = 0;
+  list[b] = b;
+}
+
+__global__ __launch_bounds__(256) void select_kernel(AdaptiveTarget t, const float4* __restrict__ st,
+                                                     float2* __restrict__ emap, float nf, float bm1f, float mu_floor,
+                                                     float threshold, int min_passes,
+                                                     unsigned long long* __restrict__ rec) {
+  __shared__ unsigned long long s_sum[4][4];   // per wave: n_above, sum_q, samples, active blocks
+  __shared__ unsigned s_max[4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  unsigned long long above = 0, qsum = 0;   // this lane's pixels
+  unsigned rmax = 0;
+  unsigned long long samples = 0, n_act = 0;   // this wave's blocks (lane 0 counts)
+  for (long long blk = (long long)blockIdx.x * 4 + wave; blk < t.n_blocks; blk += (long long)gridDim.x * 4) {
+    const int bx = (int)(blk % t.blocks_x), by = (int)(blk / t.blocks_x);
+    const int x = bx * 8 + (lane & 7), lr = by * 8 + (lane >> 3);
+    const bool in = x < t.W && lr < t.n_local_rows;
+    const long long i = (long long)lr * t.W + x;
+    const bool act = t.flags[blk] != 0;   // (wave-uniform)
+    const int passes = t.passes[blk];
+    float r = 0.0f;
+    if (in) {
+      if (act) {
+        const float2 e = pixel_error(st[i], nf, bm1f, mu_floor);
+        emap[i] = e;
+        r = e.y;
+      } else {
+        r = emap[i].y;   // as written when the block retired
+      }
+      above += (r > threshold) ? 1u : 0u;
+      qsum += error_q(r);
+    }
+    unsigned bmax = __float_as_uint(r);   // r >= 0: the bits order as the values (idle lanes: 0)
+    rmax = bmax > rmax ? bmax : rmax;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      const unsigned o = __shfl_xor(bmax, off, 64);
+      bmax = o > bmax ? o : bmax;
+    }
+    const bool stay = act && (__uint_as_float(bmax) > threshold || passes < min_passes);
+    const unsigned n_in = (unsigned)__popcll(__ballot(in));
+    if (lane == 0) {
+      if (act) t.flags[blk] = stay ? 1 : 0;
+      samples += (unsigned long long)n_in * (unsigned long long)((long long)t.p0 + passes);
+      n_act += stay ? 1u : 0u;
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    above += __shfl_down(above, off, 64);
+    qsum += __shfl_down(qsum, off, 64);
+    const unsigned o = __shfl_down(rmax, off, 64);
+    rmax = o > rmax ? o : rmax;
+  }
+  if (lane == 0) {
+    s_sum[wave][0] = above; s_sum[wave][1] = qsum; s_sum[wave][2] = samples; s_sum[wave][3] = n_act;
+    s_max[wave] = rmax;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long v[4] = {0, 0, 0, 0};
+    unsigned m = 0;
+    for (int w = 0; w < 4; ++w) {
+      for (int k = 0; k < 4; ++k) v[k] += s_sum[w][k];
+      m = s_max[w] > m ? s_max[w] : m;
+    }
+    unsigned long long* slot = rec + (size_t)(blockIdx.x % kStatsRecSlots) * kStatsRecStride;
+    if (v[0]) atomicAdd(slot + 0, v[0]);
+    if (v[1]) atomicAdd(slot + 1, v[1]);
+    if (m) atomicMax(reinterpret_cast<unsigned*>(slot + 2), m);
+    if (v[2]) atomicAdd(slot + 3, v[2]);
+    if (v[3]) atomicAdd(slot + 4, v[3]);
+  }
+}
+
+// one workgroup of 16 waves; step k scans flags [1024 k, 1024 k + 1024)
+__global__ __launch_bounds__(1024) void compact_kernel(const int* __restrict__ flags, int n, int* __restrict__ list,
+                                                       int* __restrict__ count) {
+  __shared__ int s_wave[16];
+  __shared__ int s_base;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (threadIdx.x == 0) s_base = 0;
+  __syncthreads();
+  for (int b0 = 0; b0 < n; b0 += 1024) {
+    const int b = b0 + (int)threadIdx.x;
+    const bool f = b < n && flags[b] != 0;
+    const unsigned long long m = __ballot(f);
+    if (lane == 0) s_wave[wave] = __popcll(m);
+    __syncthreads();
+    int at = s_base + __popcll(m & ((1ull << lane) - 1ull));
+    for (int w = 0; w < wave; ++w) at += s_wave[w];
+    if (f) list[at] = b;   // at < the flagged blocks so far <= n
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      int s = 0;
+      for (int w = 0; w < 16; ++w) s += s_wave[w];
+      s_base += s;
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) count[0] = s_base;
+}
+
+__global__ __launch_bounds__(256) void add_passes_kernel(int* __restrict__ passes, const int* __restrict__ list,
+                                                         int n, int n_blocks, int add) {
+  const int k = blockIdx.x * 256 + threadIdx.x;
+  if (k >= n) return;
+  const int b = list ? list[k] : k;
+  if (b >= 0 && b < n_blocks) passes[b] += add;
+}
+
+__device__ __forceinline__ int pixel_count(const AdaptiveTarget& t, long long i) {
+  const int lr = (int)(i / t.W), x = (int)(i - (long long)lr * t.W);
+  return t.p0 + t.passes[(lr >> 3) * t.blocks_x + (x >> 3)];
+}
+
+__global__ __launch_bounds__(256) void counts_kernel(AdaptiveTarget t, int* __restrict__ counts, long long n_px) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_px) return;
+  counts[i] = pixel_count(t, i);
+}
+
+__global__ __launch_bounds__(256) void resolve_kernel(AdaptiveTarget t, const float* __restrict__ accum,
+                                                      float* __restrict__ out, long long n_px) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_px) return;
+  const float nb = (float)pixel_count(t, i);
+  out[3 * i] = accum[3 * i] / nb; out[3 * i + 1] = accum[3 * i + 1] / nb; out[3 * i + 2] = accum[3 * i + 2] / nb;
+}
+
+__global__ __launch_bounds__(256) void combine_list_kernel(float* __restrict__ accum, const float* __restrict__ partial,
+                                                           long long n_px, int n_seg, int W, int n_local_rows,
+                                                           int blocks_x, int n_blocks, const int* __restrict__ list,
+                                                           int n_list, unsigned long long* ev) {
+  const int lane = threadIdx.x & 63;
+  const long long li = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (li >= n_list) return;
+  const int blk = list[li];
+  if (!idx_ok(ev, CK_LIST, blk, n_blocks)) return;
+  const int x = (blk % blocks_x) * 8 + (lane & 7), lr = (blk / blocks_x) * 8 + (lane >> 3);
+  if (x >= W || lr >= n_local_rows) return;
+  const long long i = (long long)lr * W + x;
+  float a0 = accum[i * 3], a1 = accum[i * 3 + 1], a2 = accum[i * 3 + 2];
+  for (int s = 0; s < n_seg; ++s) {
+    const float* q = partial + ((size_t)s * n_px + i) * 3;
+    a0 = a0 + q[0]; a1 = a1 + q[1]; a2 = a2 + q[2];
+  }
+  accum[i * 3] = a0; accum[i * 3 + 1] = a1; accum[i * 3 + 2] = a2;
+}
+
+}  // namespace mcpt
+
+static unsigned grid256(long long n) { return (unsigned)((n + 255) / 256); }
+
+hipError_t mcpt_launch_adaptive_reset(const mcpt::AdaptiveTarget& t, int* list, int* count, hipStream_t stream) {
+  hipLaunchKernelGGL(mcpt::adaptive_reset_kernel, dim3(std::max(1u, grid256(t.n_blocks))), dim3(256), 0, stream, t,
+                     list, count);
+  return hipGetLastError();
+}
+
+hipError_t mcpt_launch_adaptive_select(const mcpt::AdaptiveTarget& t, const float4* state, float2* emap,
+                                       long long passes, int batches, float mu_floor, float threshold, int min_passes,
+                                       unsigned long long* rec, hipStream_t stream) {
+  hipError_t e = hipMemsetAsync(rec, 0, sizeof(unsigned long long) * mcpt::kStatsRecWords, stream);
+  if (e != hipSuccess || t.n_blocks <= 0) return e;
+  const long long groups = ((long long)t.n_blocks + 3) / 4;
+  hipLaunchKernelGGL(mcpt::select_kernel, dim3((unsigned)std::min<long long>(groups, mcpt::kSelectMaxBlocks)),
+                     dim3(256), 0, stream, t, state, emap, (float)passes, (float)(batches - 1), mu_floor, threshold,
+                     min_passes, rec);
+  return hipGetLastError();
+}
+
+hipError_t mcpt_launch_adaptive_compact(const mcpt::AdaptiveTarget& t, int* list, int* count, hipStream_t stream) {
+  hipLaunchKernelGGL(mcpt::compact_kernel, dim3(1), dim3(1024), 0, stream, t.flags, t.n_blocks, list, count);
+  return hipGetLastError();
+}
+
+hipError_t mcpt_launch_adaptive_add_passes(const mcpt::AdaptiveTarget& t, const int* list, int n_list, int n,
+                                           hipStream_t stream) {
+  const int k = list ? n_list : t.n_blocks;
+  if (k <= 0) return hipSuccess;
+  hipLaunchKernelGGL(mcpt::add_passes_kernel, dim3(grid256(k)), dim3(256), 0, stream, t.passes, list, k, t.n_blocks, n);
+  return hipGetLastError();
+}
+
+hipError_t mcpt_launch_adaptive_counts(const mcpt::AdaptiveTarget& t, int* counts, hipStream_t stream) {
+  const long long n = (long long)t.n_local_rows * t.W;
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(mcpt::counts_kernel, dim3(grid256(n)), dim3(256), 0, stream, t, counts, n);
+  return hipGetLastError();
+}
+
+hipError_t mcpt_launch_adaptive_resolve(const mcpt::AdaptiveTarget& t, const float* accum, float* out,
+                                        hipStream_t stream) {
+  const long long n = (long long)t.n_local_rows * t.W;
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(mcpt::resolve_kernel, dim3(grid256(n)), dim3(256), 0, stream, t, accum, out, n);
+  return hipGetLastError();
+}
+
+hipError_t mcpt_launch_combine_list(const mcpt::RenderParams& p, hipStream_t stream) {
+  if (p.n_segments <= 1 || p.n_list <= 0) return hipSuccess;   // (one segment: the render added it itself)
+  hipLaunchKernelGGL(mcpt::combine_list_kernel, dim3((unsigned)(((long long)p.n_list + 3) / 4)), dim3(256), 0, stream,
+                     p.accum, p.partial, p.n_local_px, p.n_segments, p.W, p.n_local_rows, p.blocks_x, p.n_blocks, p.list,
+                     p.n_list, p.events);
+  return hipGetLastError();
+}

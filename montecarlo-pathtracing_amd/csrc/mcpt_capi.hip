@@ -206,6 +206,19 @@ struct mcpt_ctx {
   bool emap_valid = false;          // d_emap was written in this window
   bool stats_update_timed = false, stats_error_timed = false;
   hipEvent_t stats_ev[4] = {};      // around the last batch update [0, 1] and the last error kernel [2, 3]
+  // adaptive sampling of 8x8 blocks (mcpt_adaptive.hip): 12 B per block, allocated
+  // by mcpt_adaptive_begin, freed by mcpt_adaptive_end, mcpt_stats_end, the next mcpt_set_target*
+  // and mcpt_destroy
+  bool ad_on = false;
+  int* d_ad_flags = nullptr;        // per block: 1 active, 0 retired
+  int* d_ad_passes = nullptr;       // per block: passes since mcpt_adaptive_begin
+  int* d_ad_list = nullptr;         // the active block ids, ascending; [n_blocks]: the list's length
+  int ad_blocks_x = 0, ad_n_blocks = 0;
+  int ad_n_list = 0;                // the list's length (read back by the last select)
+  int ad_p0 = 0;                    // the accumulator's pass count at mcpt_adaptive_begin
+  int ad_min_passes = 0;
+  bool ad_select_timed = false, ad_render_timed = false;
+  hipEvent_t ad_ev[4] = {};         // around the last select [0, 1] and the last adaptive render [2, 3]
   int next_lane = 0;                // the lane of the next sub-launch
   int overlap = 1;                  // MCPT_OVERLAP (0: every launch in order on `stream`)
   int prev_lane = -1;               // the lane of the previous sub-launch if it was a lane launch, else -1
@@ -420,6 +433,7 @@ const char* mcpt_error_string(int status) {
                        : status == MCPT_ERR_BAD_SCENE ? "malformed scene buffers"
                        : status == MCPT_ERR_NO_GUIDES ? "no current guide buffers"
                        : status == MCPT_ERR_NO_STATS  ? "no noise statistics"
+                       : status == MCPT_ERR_NO_ADAPTIVE ? "adaptive mode is off"
                                                       : "error";
     std::snprintf(g_detail, sizeof(g_detail), "%s (%s)", base, g_last_error);
     return g_detail;
@@ -434,6 +448,7 @@ const char* mcpt_error_string(int status) {
     case MCPT_ERR_BAD_SCENE: return "malformed scene buffers";
     case MCPT_ERR_NO_GUIDES: return "no current guide buffers (call mcpt_render_guides)";
     case MCPT_ERR_NO_STATS: return "no noise statistics (mcpt_stats_begin, two batches, mcpt_convergence)";
+    case MCPT_ERR_NO_ADAPTIVE: return "adaptive mode is off (mcpt_adaptive_begin)";
     default: return "unknown status";
   }
 }
@@ -530,6 +545,13 @@ static void free_stats(mcpt_ctx* c) {
   c->stats_update_timed = false; c->stats_error_timed = false;
 }
 
+static void free_adaptive(mcpt_ctx* c) {
+  (void)hipFree(c->d_ad_flags); (void)hipFree(c->d_ad_passes); (void)hipFree(c->d_ad_list);
+  c->d_ad_flags = nullptr; c->d_ad_passes = nullptr; c->d_ad_list = nullptr;
+  c->ad_on = false; c->ad_n_blocks = 0; c->ad_n_list = 0;
+  c->ad_select_timed = false; c->ad_render_timed = false;
+}
+
 static void free_scene(mcpt_ctx* c) {
   (void)hipFree(c->d_nodes); (void)hipFree(c->d_leaves); (void)hipFree(c->d_ptype); (void)hipFree(c->d_prims);
   c->d_nodes = nullptr; c->d_leaves = nullptr; c->d_ptype = nullptr; c->d_prims = nullptr;
@@ -547,6 +569,8 @@ int mcpt_destroy(mcpt_ctx* c) {
   for (hipEvent_t e : c->dn_ev) if (e) (void)hipEventDestroy(e);
   free_stats(c);
   for (hipEvent_t e : c->stats_ev) if (e) (void)hipEventDestroy(e);
+  free_adaptive(c);
+  for (hipEvent_t e : c->ad_ev) if (e) (void)hipEventDestroy(e);
   (void)hipFree(c->d_accum);
   (void)hipFree(c->d_rows);
   (void)hipFree(c->d_events);
@@ -818,6 +842,7 @@ static int set_target_rows(mcpt_ctx* c, int W, int H, const int* rows, int n_row
   HIP_OR_RETURN(hipStreamSynchronize(c->stream));
   free_denoise(c);   // (sized by the target; allocated again by the next guides / denoise call)
   free_stats(c);     // (statistics off: a new target begins again)
+  free_adaptive(c);  // (adaptive mode off: its blocks are the old target's)
   size_t bytes = (size_t)n_rows * W * 3 * sizeof(float);
   if (bytes != c->accum_bytes) {
     (void)hipFree(c->d_accum);
@@ -1171,17 +1196,15 @@ static hipError_t stats_batch(mcpt_ctx* c, int n) {
   return hipSuccess;
 }
 
-static int launch(mcpt_ctx* c, const float* invPV, const float* invV, int first_pass, int n_passes, float date,
-                  int bounces, float refract_ind, int variant, bool count, unsigned long long* events) {
-  if (!c || !invPV || !invV || n_passes < 0 || variant < 0 || variant > 2)
-    return set_err(MCPT_ERR_INVALID_ARG, "mcpt_render: bad arguments");
-  if (!c->has_scene) return set_err(MCPT_ERR_NO_SCENE, "no scene uploaded");
-  if (!c->has_target) return set_err(MCPT_ERR_NO_TARGET, "no render target");
-  if (c->n_meshes == 0)
-    for (int id : c->mesh_ids)
-      if (id >= 0) return set_err(MCPT_ERR_BAD_SCENE, "mesh instances present: call mcpt_upload_meshes");
-  HIP_OR_RETURN(hipSetDevice(c->device));
-  mcpt::RenderParams p;
+static mcpt::AdaptiveTarget adaptive_target(const mcpt_ctx* c) {
+  mcpt::AdaptiveTarget t;
+  t.W = c->W; t.n_local_rows = c->n_local_rows; t.blocks_x = c->ad_blocks_x; t.n_blocks = c->ad_n_blocks;
+  t.flags = c->d_ad_flags; t.passes = c->d_ad_passes; t.p0 = c->ad_p0;
+  return t;
+}
+
+// a render launch's scene, target and camera fields (launch(), adaptive_launch())
+static void scene_params(const mcpt_ctx* c, const float* invPV, const float* invV, mcpt::RenderParams& p) {
   std::memset(&p, 0, sizeof(p));
   p.nodes = c->d_nodes; p.leaves = c->d_leaves; p.ptype = c->d_ptype; p.prims = c->d_prims;
   p.accum = c->d_accum; p.events = c->d_events;
@@ -1195,6 +1218,38 @@ static int launch(mcpt_ctx* c, const float* invPV, const float* invV, int first_
   }
   p.minfo = c->d_minfo; p.mpairs = c->d_mpairs; p.mleaftris = c->d_mleaftris; p.mtris = c->d_mtris;
   p.mverts = c->d_mverts; p.mnorms = c->d_mnorms; p.n_meshes = c->n_meshes; p.flat_face = c->flat_face;
+  p.tile_w = mcpt::tile_w_for(c->n_meshes > 0, p.lds_scene_bytes);
+  p.n_local_px = (long long)c->n_local_rows * c->W;
+}
+
+// ... and its pass range and wave-uniform constants
+static void pass_params(int first_pass, int n_passes, float date, int bounces, float refract_ind, int variant,
+                        mcpt::RenderParams& p) {
+  p.first_pass = first_pass; p.n_passes = n_passes; p.bounces = bounces; p.variant = variant;
+  p.date = date; p.ior = refract_ind;
+  p.inv_ior = 1.0f / refract_ind;
+  float r0 = (refract_ind - 1.0f) / (refract_ind + 1.0f);   // schlick tp/montecarlo.frag:93-94
+  p.schlick_r0 = r0 * r0;
+  p.schlick_1mr0 = 1.0f - p.schlick_r0;
+  p.ior_sq = refract_ind * refract_ind;
+  p.inv_ior_sq = p.inv_ior * p.inv_ior;
+  const float fmax = mcpt::kFLTMAX, nx = std::nextafter(fmax, INFINITY);   // cull_bound_sq(FLT_MAX)
+  const double m = ((double)fmax + (double)nx) * 0.5;
+  p.cull2_max = m * m;
+}
+
+static int launch(mcpt_ctx* c, const float* invPV, const float* invV, int first_pass, int n_passes, float date,
+                  int bounces, float refract_ind, int variant, bool count, unsigned long long* events) {
+  if (!c || !invPV || !invV || n_passes < 0 || variant < 0 || variant > 2)
+    return set_err(MCPT_ERR_INVALID_ARG, "mcpt_render: bad arguments");
+  if (!c->has_scene) return set_err(MCPT_ERR_NO_SCENE, "no scene uploaded");
+  if (!c->has_target) return set_err(MCPT_ERR_NO_TARGET, "no render target");
+  if (c->n_meshes == 0)
+    for (int id : c->mesh_ids)
+      if (id >= 0) return set_err(MCPT_ERR_BAD_SCENE, "mesh instances present: call mcpt_upload_meshes");
+  HIP_OR_RETURN(hipSetDevice(c->device));
+  mcpt::RenderParams p;
+  scene_params(c, invPV, invV, p);
   {
     // AUTO: the trial before the last call is collected now (its render has ended while the last
     // call's runs); all of them first when this call's shape differs from theirs
@@ -1204,7 +1259,6 @@ static int launch(mcpt_ctx* c, const float* invPV, const float* invV, int first_
     HIP_OR_RETURN(collect_tuning(c, (other || count) ? 0 : 1));
   }
   // (the counting build is not timed: AUTO counts with the per-lane walk)
-  p.tile_w = mcpt::tile_w_for(c->n_meshes > 0, p.lds_scene_bytes);
   p.n_tiles = ((c->W + p.tile_w - 1) / p.tile_w) * ((c->n_local_rows + mcpt::kTileH - 1) / mcpt::kTileH);
   auto fdiv = [](int a, int b) { return (a >= 0) ? a / b : -((-a + b - 1) / b); };
   const long long total_seg = n_passes > 0 ? fdiv(first_pass + n_passes - 2, mcpt::kPassChunk) -
@@ -1233,20 +1287,7 @@ static int launch(mcpt_ctx* c, const float* invPV, const float* invV, int first_
   // pass segments per work item: candidate 3 of AUTO runs two; MCPT_SEG_PER_ITEM overrides
   const int env_seg = env_int("MCPT_SEG_PER_ITEM", 0);
   p.seg_per_item = env_seg > 0 ? env_seg : cand_seg_per_item(cand);
-  p.first_pass = first_pass; p.n_passes = n_passes; p.bounces = bounces; p.variant = variant;
-  p.date = date; p.ior = refract_ind;
-  p.inv_ior = 1.0f / refract_ind;
-  {
-    float r0 = (refract_ind - 1.0f) / (refract_ind + 1.0f);   // schlick tp/montecarlo.frag:93-94
-    p.schlick_r0 = r0 * r0;
-    p.schlick_1mr0 = 1.0f - p.schlick_r0;
-    p.ior_sq = refract_ind * refract_ind;
-    p.inv_ior_sq = p.inv_ior * p.inv_ior;
-    const float fmax = mcpt::kFLTMAX, nx = std::nextafter(fmax, INFINITY);   // cull_bound_sq(FLT_MAX)
-    const double m = ((double)fmax + (double)nx) * 0.5;
-    p.cull2_max = m * m;
-  }
-  p.n_local_px = (long long)c->n_local_rows * c->W;
+  pass_params(first_pass, n_passes, date, bounces, refract_ind, variant, p);
   // The call's pass range is cut at accumulation-chunk boundaries into sub-launches of at
   // most max_seg segments, so that the segment-sum buffer stays within partial_budget and
   // the grid within 2^32 work-items (an 84,000-pass 4K call is ~2,600 segments: 261 GB of
@@ -1485,6 +1526,9 @@ static int launch(mcpt_ctx* c, const float* invPV, const float* invV, int first_
   c->pass_split = split ? 1 : 0;
   c->timed = true;
   c->pass_count += n_passes;
+  // adaptive mode on: a plain render reaches every pixel, retired blocks included
+  if (c->ad_on && n_passes > 0)
+    HIP_OR_RETURN(mcpt_launch_adaptive_add_passes(adaptive_target(c), nullptr, 0, n_passes, c->stream));
   // noise statistics on: the call is one batch, behind its last combine
   if (c->stats_on && n_passes > 0) HIP_OR_RETURN(stats_batch(c, n_passes));
   if (count) {
@@ -1778,6 +1822,8 @@ static int denoise_run(mcpt_ctx* c, int iterations, float sigma_color, float sig
   for (int i = 0; full && i < c->n_local_rows; ++i) full = c->rows[(size_t)i] == i;
   if (!full) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_denoise: needs a full-frame target (gather the shards first)");
   if (c->pass_count <= 0) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_denoise: the accumulator holds no passes");
+  if (c->ad_on && c->ad_n_list < c->ad_n_blocks)
+    return set_err(MCPT_ERR_INVALID_ARG, "mcpt_denoise: adaptive mode has retired blocks (per-pixel sample counts)");
   if (!c->guides_valid) return set_err(MCPT_ERR_NO_GUIDES, "mcpt_denoise: no guides rendered for this target and scene");
   if (guided && !(c->stats_on && c->emap_valid))
     return set_err(MCPT_ERR_NO_STATS, "mcpt_denoise_guided: no error map (mcpt_convergence) of the current statistics");
@@ -1847,6 +1893,7 @@ int mcpt_stats_end(mcpt_ctx* c) {
   HIP_OR_RETURN(hipSetDevice(c->device));
   if (c->d_conv) HIP_OR_RETURN(hipStreamSynchronize(c->stream));   // (queued updates still use the buffers)
   free_stats(c);
+  free_adaptive(c);   // (the adaptive mode selects from the statistics: off with them)
   return MCPT_OK;
 }
 
@@ -1928,6 +1975,238 @@ int mcpt_last_stats_ms(mcpt_ctx* c, float* update_ms, float* error_ms) {
     if (c->stats_error_timed) {
       HIP_OR_RETURN(hipEventSynchronize(c->stats_ev[3]));
       HIP_OR_RETURN(hipEventElapsedTime(error_ms, c->stats_ev[2], c->stats_ev[3]));
+    }
+  }
+  return MCPT_OK;
+}
+
+// ---- adaptive sampling of 8x8 blocks (mcpt_adaptive.hip)
+int mcpt_adaptive_begin(mcpt_ctx* c, int min_passes) {
+  if (!c || min_passes < 0) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_adaptive_begin: min_passes must not be negative");
+  if (!c->has_target) return set_err(MCPT_ERR_NO_TARGET, "no render target");
+  if (!c->stats_on) return set_err(MCPT_ERR_NO_STATS, "mcpt_adaptive_begin: statistics are off (mcpt_stats_begin)");
+  HIP_OR_RETURN(hipSetDevice(c->device));
+  const int bx = (c->W + 7) / 8, by = (c->n_local_rows + 7) / 8;
+  if (!c->d_ad_flags) {
+    const size_t n = (size_t)std::max(bx * by, 1);
+    hipError_t e = hipMalloc(&c->d_ad_flags, n * sizeof(int));
+    if (e == hipSuccess) e = hipMalloc(&c->d_ad_passes, n * sizeof(int));
+    if (e == hipSuccess) e = hipMalloc(&c->d_ad_list, (n + 1) * sizeof(int));
+    if (e != hipSuccess) {
+      free_adaptive(c);
+      return set_err(MCPT_ERR_HIP, "mcpt_adaptive_begin: hipMalloc", e);
+    }
+  }
+  c->ad_blocks_x = bx;
+  c->ad_n_blocks = bx * by;
+  c->ad_p0 = c->pass_count;
+  c->ad_min_passes = min_passes;
+  HIP_OR_RETURN(mcpt_launch_adaptive_reset(adaptive_target(c), c->d_ad_list, c->d_ad_list + c->ad_n_blocks, c->stream));
+  c->ad_n_list = c->ad_n_blocks;
+  c->ad_on = true;
+  return MCPT_OK;
+}
+
+int mcpt_adaptive_end(mcpt_ctx* c) {
+  if (!c) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  HIP_OR_RETURN(hipSetDevice(c->device));
+  if (c->d_ad_flags) HIP_OR_RETURN(hipStreamSynchronize(c->stream));   // (queued launches still read the list)
+  free_adaptive(c);
+  return MCPT_OK;
+}
+
+int mcpt_adaptive_info(mcpt_ctx* c, int* on, long long* n_active, long long* n_blocks) {
+  if (!c) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  if (on) *on = c->ad_on ? 1 : 0;
+  if (n_active) *n_active = c->ad_on ? c->ad_n_list : 0;
+  if (n_blocks) *n_blocks = c->ad_on ? c->ad_n_blocks : 0;
+  return MCPT_OK;
+}
+
+int mcpt_adaptive_select(mcpt_ctx* c, float threshold, float mu_floor, mcpt_adaptive_t* out) {
+  if (!c || !out) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  if (!c->ad_on) return set_err(MCPT_ERR_NO_ADAPTIVE, "mcpt_adaptive_select: adaptive mode is off (mcpt_adaptive_begin)");
+  if (!(threshold > 0.0f) || !(mu_floor > 0.0f) || !std::isfinite(threshold) || !std::isfinite(mu_floor))
+    return set_err(MCPT_ERR_INVALID_ARG, "mcpt_adaptive_select: threshold and mu_floor must be positive and finite");
+  if (!c->stats_on) return set_err(MCPT_ERR_NO_STATS, "mcpt_adaptive_select: statistics are off (mcpt_stats_begin)");
+  if (c->stats_batches < 2) return set_err(MCPT_ERR_NO_STATS, "mcpt_adaptive_select: needs two batches or more");
+  HIP_OR_RETURN(hipSetDevice(c->device));
+  HIP_OR_RETURN(ensure_timing_events(c->ad_ev, 2));
+  const mcpt::AdaptiveTarget t = adaptive_target(c);
+  int* d_count = c->d_ad_list + c->ad_n_blocks;
+  HIP_OR_RETURN(hipEventRecord(c->ad_ev[0], c->stream));
+  HIP_OR_RETURN(mcpt_launch_adaptive_select(t, c->d_stats, c->d_emap, c->stats_passes, c->stats_batches, mu_floor,
+                                            threshold, c->ad_min_passes, c->d_conv, c->stream));
+  HIP_OR_RETURN(mcpt_launch_adaptive_compact(t, c->d_ad_list, d_count, c->stream));
+  HIP_OR_RETURN(hipEventRecord(c->ad_ev[1], c->stream));
+  c->ad_select_timed = true;
+  c->emap_valid = true;
+  unsigned long long part[mcpt::kStatsRecWords] = {};
+  int n_list = 0;
+  HIP_OR_RETURN(hipMemcpyAsync(part, c->d_conv, sizeof(part), hipMemcpyDeviceToHost, c->stream));
+  HIP_OR_RETURN(hipMemcpyAsync(&n_list, d_count, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIP_OR_RETURN(hipStreamSynchronize(c->stream));
+  unsigned long long h[5] = {0, 0, 0, 0, 0};   // the partial records add (max for max_r's bits)
+  for (int s = 0; s < mcpt::kStatsRecSlots; ++s) {
+    const unsigned long long* q = part + (size_t)s * mcpt::kStatsRecStride;
+    h[0] += q[0];
+    h[1] += q[1];
+    h[2] = std::max(h[2], q[2] & 0xffffffffull);
+    h[3] += q[3];
+    h[4] += q[4];
+  }
+  if (n_list < 0 || n_list > c->ad_n_blocks || (unsigned long long)n_list != h[4])
+    return set_err(MCPT_ERR_HIP, "mcpt_adaptive_select: the active list and the block flags disagree");
+  c->ad_n_list = n_list;
+  const long long n = (long long)c->n_local_rows * c->W;
+  out->n_px = n;
+  out->n_above = (long long)h[0];
+  out->sum_q = h[1];
+  const unsigned mb = (unsigned)(h[2] & 0xffffffffull);
+  std::memcpy(&out->max_r, &mb, sizeof(float));
+  out->mean_r = n > 0 ? (double)h[1] / 65536.0 / (double)n : 0.0;
+  out->passes = c->stats_passes;
+  out->batches = c->stats_batches;
+  out->n_active_blocks = n_list;
+  out->n_blocks = c->ad_n_blocks;
+  out->samples = (long long)h[3];
+  return MCPT_OK;
+}
+
+int mcpt_read_active_blocks(mcpt_ctx* c, int* ids, int capacity, int* n) {
+  if (!c || !n || (capacity > 0 && !ids) || capacity < 0) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  if (!c->ad_on) return set_err(MCPT_ERR_NO_ADAPTIVE, "mcpt_read_active_blocks: adaptive mode is off (mcpt_adaptive_begin)");
+  HIP_OR_RETURN(hipSetDevice(c->device));
+  *n = c->ad_n_list;
+  const int k = std::min(capacity, c->ad_n_list);
+  if (k > 0) HIP_OR_RETURN(hipMemcpyAsync(ids, c->d_ad_list, sizeof(int) * (size_t)k, hipMemcpyDeviceToHost, c->stream));
+  HIP_OR_RETURN(hipStreamSynchronize(c->stream));
+  return MCPT_OK;
+}
+
+// The listed blocks' passes first_pass .. first_pass + n_passes - 1 on the context's stream (ordered
+// after the render lanes): the scene's per-lane kernel's LIST twin, one segment per item, dispatch
+// order.  No part in AUTO's trials, the item-cost sort, the render lanes or the timing ring.
+int mcpt_render_adaptive(mcpt_ctx* c, const float* invPV, const float* invV, int first_pass, int n_passes, float date,
+                         int bounces, float refract_ind, int variant) {
+  if (!c || !invPV || !invV || n_passes < 0 || variant < 0 || variant > 2)
+    return set_err(MCPT_ERR_INVALID_ARG, "mcpt_render_adaptive: bad arguments");
+  if (!c->ad_on) return set_err(MCPT_ERR_NO_ADAPTIVE, "mcpt_render_adaptive: adaptive mode is off (mcpt_adaptive_begin)");
+  if (!c->has_scene) return set_err(MCPT_ERR_NO_SCENE, "no scene uploaded");
+  if (!c->has_target) return set_err(MCPT_ERR_NO_TARGET, "no render target");
+  if (c->n_meshes == 0)
+    for (int id : c->mesh_ids)
+      if (id >= 0) return set_err(MCPT_ERR_BAD_SCENE, "mesh instances present: call mcpt_upload_meshes");
+  if (c->ad_n_list == 0 || n_passes == 0) return MCPT_OK;   // every block retired: nothing to launch
+  HIP_OR_RETURN(hipSetDevice(c->device));
+  mcpt::RenderParams p;
+  scene_params(c, invPV, invV, p);
+  pass_params(first_pass, n_passes, date, bounces, refract_ind, variant, p);
+  p.walk_exit = resolve_walk_exit(c);
+  p.leaf_batch = resolve_leaf_batch(c);
+  p.walk_min_done = 1;
+  p.seg_per_item = 1;
+  p.list = c->d_ad_list;
+  p.n_list = c->ad_n_list;
+  p.blocks_x = c->ad_blocks_x;
+  p.n_blocks = c->ad_n_blocks;
+  const int per_group = p.tile_w / 8;
+  p.n_tiles = (p.n_list + per_group - 1) / per_group;   // workgroup groups of the list
+  auto fdiv = [](int a, int b) { return (a >= 0) ? a / b : -((-a + b - 1) / b); };
+  const long long seg_bytes = p.n_local_px * 3 * (long long)sizeof(float);
+  const long long max_items = (1LL << 32) / (p.tile_w * mcpt::kTileH) - 1;
+  long long max_seg = seg_bytes > 0 ? (long long)(c->partial_budget / (size_t)seg_bytes) : (1LL << 30);
+  max_seg = std::max(1LL, std::min(max_seg, max_items / p.n_tiles));
+  HIP_OR_RETURN(ensure_timing_events(c->ad_ev + 2, 2));
+  mcpt_ctx::Lane& L = c->lanes[0];   // its segment-sum buffer (free: `stream` is ordered after the lanes' work)
+  HIP_OR_RETURN(hipEventRecord(c->ad_ev[2], c->stream));
+  int k = 0;   // sub-launches at chunk boundaries, as launch() cuts them (segment-sum budget, grid size)
+  for (long long lo = first_pass, end = (long long)first_pass + n_passes; lo < end; ++k) {
+    const long long c0 = fdiv((int)(lo - 1), mcpt::kPassChunk);
+    const long long hi = std::min(end, (c0 + max_seg) * mcpt::kPassChunk + 1);
+    p.first_pass = (int)lo;
+    p.n_passes = (int)(hi - lo);
+    p.n_segments = fdiv((int)(hi - 2), mcpt::kPassChunk) - (int)c0 + 1;
+    p.n_items = (int)((long long)p.n_tiles * p.n_segments);
+    if (p.n_segments > 1 && (size_t)p.n_segments * (size_t)seg_bytes > L.partial_bytes) {
+      const size_t need = (size_t)p.n_segments * (size_t)seg_bytes;
+      HIP_OR_RETURN(hipStreamSynchronize(c->stream));   // (ordered after every lane's work)
+      (void)hipFree(L.d_partial);
+      L.d_partial = nullptr;
+      L.partial_bytes = 0;
+      HIP_OR_RETURN(hipMalloc(&L.d_partial, need));
+      L.partial_bytes = need;
+    }
+    p.partial = L.d_partial;
+    HIP_OR_RETURN(mcpt_launch_render_list(p, c->stream));
+    HIP_OR_RETURN(mcpt_launch_combine_list(p, c->stream));
+    L.freed_stale = true;   // (the lane's next launch waits for `stream`'s work so far)
+#ifdef MCPT_CHECKED
+    {
+      const int st = checked_sub_launch(c, k, -1, p);
+      if (st != MCPT_OK) return st;
+    }
+#endif
+    lo = hi;
+  }
+  (void)k;
+  HIP_OR_RETURN(hipEventRecord(c->ad_ev[3], c->stream));
+  c->ad_render_timed = true;
+  HIP_OR_RETURN(mcpt_launch_adaptive_add_passes(adaptive_target(c), c->d_ad_list, c->ad_n_list, n_passes, c->stream));
+  c->pass_count += n_passes;   // the active blocks' count: the largest
+  if (c->stats_on) HIP_OR_RETURN(stats_batch(c, n_passes));
+  return MCPT_OK;
+}
+
+int mcpt_read_sample_counts(mcpt_ctx* c, int* counts) {
+  if (!c || !counts) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  if (!c->ad_on) return set_err(MCPT_ERR_NO_ADAPTIVE, "mcpt_read_sample_counts: adaptive mode is off (mcpt_adaptive_begin)");
+  HIP_OR_RETURN(hipSetDevice(c->device));
+  const size_t n = (size_t)c->n_local_rows * c->W;
+  if (n) {
+    int* d = nullptr;
+    HIP_OR_RETURN(hipMalloc(&d, n * sizeof(int)));
+    hipError_t e = mcpt_launch_adaptive_counts(adaptive_target(c), d, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(counts, d, n * sizeof(int), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    (void)hipFree(d);
+    if (e != hipSuccess) return set_err(MCPT_ERR_HIP, "mcpt_read_sample_counts", e);
+  }
+  return MCPT_OK;
+}
+
+int mcpt_read_resolved(mcpt_ctx* c, float* rgb) {
+  if (!c || !rgb) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  if (!c->ad_on) return set_err(MCPT_ERR_NO_ADAPTIVE, "mcpt_read_resolved: adaptive mode is off (mcpt_adaptive_begin)");
+  HIP_OR_RETURN(hipSetDevice(c->device));
+  const size_t n = (size_t)c->n_local_rows * c->W;
+  if (n) {
+    float* d = nullptr;
+    HIP_OR_RETURN(hipMalloc(&d, n * 3 * sizeof(float)));
+    hipError_t e = mcpt_launch_adaptive_resolve(adaptive_target(c), c->d_accum, d, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(rgb, d, n * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    (void)hipFree(d);
+    if (e != hipSuccess) return set_err(MCPT_ERR_HIP, "mcpt_read_resolved", e);
+  }
+  return MCPT_OK;
+}
+
+int mcpt_last_adaptive_ms(mcpt_ctx* c, float* select_ms, float* render_ms) {
+  if (!c) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  HIP_OR_RETURN(hipSetDevice(c->device));
+  if (select_ms) {
+    *select_ms = 0.0f;
+    if (c->ad_select_timed) {
+      HIP_OR_RETURN(hipEventSynchronize(c->ad_ev[1]));
+      HIP_OR_RETURN(hipEventElapsedTime(select_ms, c->ad_ev[0], c->ad_ev[1]));
+    }
+  }
+  if (render_ms) {
+    *render_ms = 0.0f;
+    if (c->ad_render_timed) {
+      HIP_OR_RETURN(hipEventSynchronize(c->ad_ev[3]));
+      HIP_OR_RETURN(hipEventElapsedTime(render_ms, c->ad_ev[2], c->ad_ev[3]));
     }
   }
   return MCPT_OK;

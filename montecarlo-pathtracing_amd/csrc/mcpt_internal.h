@@ -139,6 +139,11 @@ struct RenderParams {
   int check_inject;             // checked build only (MCPT_CHECKED_INJECT=1): test every workgroup id
                                 // against n_items as round 5's tail-piece form read item_perm[b]
   double cull2_max;
+  // adaptive launches (render_kernel<.., LIST>): wave w of workgroup group g renders
+  // the 8x8 block list[g * (tile_w / 8) + w] (block id = by * blocks_x + bx over the local grid);
+  // waves past n_list are idle.  n_tiles = the workgroup groups; null in every other launch
+  const int* list;
+  int n_list, blocks_x, n_blocks;
 };
 
 // Stream schedule (MCPT_TRAVERSAL_STREAM): wavefront path tracing in two
@@ -250,6 +255,38 @@ hipError_t mcpt_launch_stats_error(const float4* state, float2* emap, long long 
                                    float mu_floor, float threshold, unsigned long long* rec, hipStream_t stream);
 hipError_t mcpt_launch_render(const mcpt::RenderParams& p, bool count, hipStream_t stream);
 hipError_t mcpt_launch_combine(const mcpt::RenderParams& p, hipStream_t stream);
+// adaptive sampling of 8x8 blocks (mcpt_adaptive.hip).  Per block an active flag
+// and the passes rendered into it since mcpt_adaptive_begin; the list holds the active block ids,
+// ascending, its length in count[0].
+namespace mcpt {
+// the select kernel's partial records: kStatsRecSlots x kStatsRecStride words as the error kernel's,
+// [0] n_above, [1] sum_q, [2] max_r's bits, [3] samples, [4] active blocks
+struct AdaptiveTarget {
+  int W, n_local_rows, blocks_x, n_blocks;
+  int* flags;                   // n_blocks: 1 active, 0 retired
+  int* passes;                  // n_blocks: passes since mcpt_adaptive_begin
+  int p0;                       // the accumulator's pass count at mcpt_adaptive_begin
+};
+}  // namespace mcpt
+// the LIST twin of the launch's per-lane kernel (p.list, p.n_list; one segment per item)
+hipError_t mcpt_launch_render_list(const mcpt::RenderParams& p, hipStream_t stream);
+// accum += seg_0 + seg_1 + ... in chunk order for the pixels of the listed blocks, one wave per block
+hipError_t mcpt_launch_combine_list(const mcpt::RenderParams& p, hipStream_t stream);
+hipError_t mcpt_launch_adaptive_reset(const mcpt::AdaptiveTarget& t, int* list, int* count, hipStream_t stream);
+// zeroes rec, then for every active block {se, r} of its pixels into emap and its new flag; every
+// block's share of the record from fresh (active) or stored (retired) map values
+hipError_t mcpt_launch_adaptive_select(const mcpt::AdaptiveTarget& t, const float4* state, float2* emap,
+                                       long long passes, int batches, float mu_floor, float threshold, int min_passes,
+                                       unsigned long long* rec, hipStream_t stream);
+// list = the ids of the flagged blocks, ascending; count[0] = how many (an ordered scan)
+hipError_t mcpt_launch_adaptive_compact(const mcpt::AdaptiveTarget& t, int* list, int* count, hipStream_t stream);
+// passes[b] += n for the listed blocks (list null: for every block)
+hipError_t mcpt_launch_adaptive_add_passes(const mcpt::AdaptiveTarget& t, const int* list, int n_list, int n,
+                                           hipStream_t stream);
+// per local pixel: its sample count p0 + passes[its block] / accum / (float)that count
+hipError_t mcpt_launch_adaptive_counts(const mcpt::AdaptiveTarget& t, int* counts, hipStream_t stream);
+hipError_t mcpt_launch_adaptive_resolve(const mcpt::AdaptiveTarget& t, const float* accum, float* out,
+                                        hipStream_t stream);
 hipError_t mcpt_iota(int* a, int n, hipStream_t stream);
 hipError_t mcpt_split_count(const unsigned* cost_sorted, int n, int capacity, int split_max, int* out,
                             unsigned long long* dbg, hipStream_t stream);
@@ -277,6 +314,7 @@ enum CheckSite {
   CK_SEGMENT,         // segment slot of partial (< n_segments)
   CK_PIXEL,           // local pixel of accum / partial (< n_local_px)
   CK_COMBINE_SPLIT,   // combine_items_kernel: split index read from split_of (< split_max)
+  CK_LIST,            // adaptive launches: the list index and the block id read from it (< n_blocks)
   CK_COUNT
 };
 #ifdef MCPT_CHECKED

@@ -64,7 +64,11 @@ constexpr int kMinWavesMesh = 5;
 // record they fit 72 VGPRs and 7 waves hide more of the dependent node loads (scene 8 +4 %,
 // scene 3 +5 %: profiles/r02_ab4_spill_free.jsonl; 6 / 8 waves re-measured in round 4: -1.9 / -6.1 %)
 constexpr int kMinWavesL2 = 7;
-template <bool COUNT, bool WAVE, bool MESH, bool LDSS, bool SUSPEND, int TW>
+// LIST (adaptive launches; !COUNT && !WAVE only): the workgroup's waves render the
+// 8x8 blocks p.list names, not the blocks of one tile — "tile" is then the workgroup's group of
+// TW / 8 list entries, and only a wave's block origin differs.  One segment per item, no item
+// order, tail pieces, split items, pass stealing or pass split.
+template <bool COUNT, bool WAVE, bool MESH, bool LDSS, bool SUSPEND, int TW, bool LIST = false>
 __global__ __launch_bounds__(TW * kTileH, MESH && !WAVE ? kMinWavesMesh
                                            : (!WAVE && !LDSS ? kMinWavesL2 : kMinWaves)) void render_kernel(
     RenderParams p) {
@@ -76,7 +80,7 @@ __global__ __launch_bounds__(TW * kTileH, MESH && !WAVE ? kMinWavesMesh
   // and chunks of 4 / 32 items per XCD change nothing; profiles/r05_ab_xcd_item_order.jsonl)
   // the launch's work-item order (mcpt_order.hip): costliest items of an earlier launch first;
   // in the mesh kernels the costliest of them split in kSplitPieces pass ranges (piece >= 0)
-  constexpr bool kSplit = MESH && !WAVE && !COUNT;
+  constexpr bool kSplit = MESH && !WAVE && !COUNT && !LIST;   // (LIST: no split items, no pass stealing)
   int item, piece = -1, sj = -1;
   // (idx_ok: the checked build's bounds tests, mcpt_internal.h; true in the shipped build.  The
   // workgroup-uniform ones return the whole workgroup before the LDS staging barrier.)
@@ -140,11 +144,23 @@ __global__ __launch_bounds__(TW * kTileH, MESH && !WAVE ? kMinWavesMesh
   }
   int seg = seg_lo;
   const int tiles_x = (p.W + TW - 1) / TW;
-  const int bx0 = (tile % tiles_x) * TW + (wave % (TW / 8)) * 8;   // this wave's 8x8 block
-  const int by0 = (tile / tiles_x) * kTileH + (wave / (TW / 8)) * 8;
+  int bx0 = (tile % tiles_x) * TW + (wave % (TW / 8)) * 8;   // this wave's 8x8 block
+  int by0 = (tile / tiles_x) * kTileH + (wave / (TW / 8)) * 8;
+  bool listed = true;
+  if constexpr (LIST) {
+    // a wave past the list's end (or, checked build, with an entry out of range) has no block: not
+    // live, and it still reaches the staging barrier
+    static_assert(!COUNT && !WAVE, "LIST: the per-lane render kernels only");
+    const long long li = (long long)tile * (TW / 8) + wave;
+    listed = li < p.n_list && idx_ok(p.events, CK_LIST, li, p.n_blocks);
+    const int blk = listed ? p.list[li] : 0;
+    listed = listed && idx_ok(p.events, CK_LIST, blk, p.n_blocks);
+    bx0 = (blk % p.blocks_x) * 8;
+    by0 = (blk / p.blocks_x) * 8;
+  }
   const int x = bx0 + (lane & 7);
   const int lr = by0 + (lane >> 3);
-  const bool live = x < p.W && lr < p.n_local_rows;   // (no early return: LDS staging barrier)
+  const bool live = x < p.W && lr < p.n_local_rows && listed;   // (no early return: LDS staging barrier)
   const int cbase = floordiv(p.first_pass - 1, kPassChunk);   // chunk of the launch's first pass
   const int c0 = cbase + seg_lo;
   int pass_begin = max(p.first_pass, c0 * kPassChunk + 1);
@@ -857,6 +873,31 @@ hipError_t mcpt_launch_render(const mcpt::RenderParams& p, bool count, hipStream
   }
 #undef MCPT_RENDER_CW
 #undef MCPT_RENDER
+  return hipGetLastError();
+}
+
+// adaptive launches: the LIST twin of the kernel mcpt_launch_render runs for per-lane walks
+hipError_t mcpt_launch_render_list(const mcpt::RenderParams& p, hipStream_t stream) {
+  const long long items = (long long)p.n_tiles * p.n_segments;
+  if (items <= 0 || p.n_list <= 0) return hipSuccess;
+  const bool mesh = p.n_meshes > 0, lds = p.lds_scene_bytes > 0;
+  if (!p.list || p.wave_traversal || p.seg_per_item != 1 || p.pass_split || p.item_perm || p.tail_m || p.split_of ||
+      p.steal_vals || p.n_items != items || p.tile_w != mcpt::tile_w_for(mesh, p.lds_scene_bytes) ||
+      (long long)p.n_tiles * (p.tile_w / 8) < p.n_list)
+    return hipErrorInvalidValue;
+  dim3 block(p.tile_w * mcpt::kTileH), grid((unsigned)items);
+  const size_t shm = lds ? (size_t)p.lds_scene_bytes : 0;
+#define MCPT_RENDER_LIST(M, L, S, T) \
+  hipLaunchKernelGGL((mcpt::render_kernel<false, false, M, L, S, T, true>), grid, block, shm, stream, p)
+#define MCPT_RENDER_LIST_S(S)                                          \
+  if (mesh && lds) MCPT_RENDER_LIST(true, true, S, 8);                 \
+  else if (mesh) MCPT_RENDER_LIST(true, false, S, 8);                  \
+  else if (lds && p.tile_w == 16) MCPT_RENDER_LIST(false, true, S, 16); \
+  else if (lds) MCPT_RENDER_LIST(false, true, S, 32);                  \
+  else MCPT_RENDER_LIST(false, false, S, 16)
+  if (p.walk_exit > 0 || p.leaf_batch > 0) { MCPT_RENDER_LIST_S(true); } else { MCPT_RENDER_LIST_S(false); }
+#undef MCPT_RENDER_LIST_S
+#undef MCPT_RENDER_LIST
   return hipGetLastError();
 }
 

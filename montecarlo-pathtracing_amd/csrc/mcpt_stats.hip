@@ -22,6 +22,7 @@
 
 #include "mcpt_internal.h"
 #include "mcpt_math.h"
+#include "mcpt_stats_err.h"
 
 namespace mcpt {
 
@@ -51,8 +52,6 @@ __global__ __launch_bounds__(256) void stats_update_kernel(const float* __restri
   st[i] = s;
 }
 
-__device__ __forceinline__ bool finite32(float x) { return __builtin_fabsf(x) < __builtin_inff(); }   // (false for NaN)
-
 constexpr int kErrorMaxBlocks = 2048;   // 8 workgroups per CU of a 256-CU chip
 
 // rec: kStatsRecSlots partial records of kStatsRecStride words, workgroup b adds into slot
@@ -69,18 +68,11 @@ __global__ __launch_bounds__(256) void error_kernel(const float4* __restrict__ s
   unsigned rmax = 0;
   const long long stride = (long long)gridDim.x * 256;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n_px; i += stride) {
-    const float4 s = st[i];
-    const float s1 = s.x - s.z;
-    float v = s.y - (s1 * s1) / nf;
-    v = (0.0f < v) ? v : 0.0f;
-    const float var = v / bm1f;
-    const float se = sqrt_rn(var / nf);
-    const float mu = s1 / nf;
-    float r = se / (gmax(0.0f, mu) + mu_floor);
-    if (!finite32(s.y) || !finite32(s1) || !(r <= 64.0f)) r = 64.0f;
-    emap[i] = make_float2(se, r);
+    const float2 e = pixel_error(st[i], nf, bm1f, mu_floor);   // {se, r} (mcpt_stats_err.h)
+    const float r = e.y;
+    emap[i] = e;
     above += (r > threshold) ? 1u : 0u;
-    qsum += (unsigned)(r * 65536.0f);
+    qsum += error_q(r);
     const unsigned rb = __float_as_uint(r);   // r >= 0: the bits order as the values
     rmax = rb > rmax ? rb : rmax;
   }

@@ -55,6 +55,7 @@ DENOISE_K_COLOR = 64.0
 # measured against it, so that black pixels do not hold a render back
 ERROR_MU_FLOOR = 0.01
 NO_STATS = -8      # MCPT_ERR_NO_STATS
+NO_ADAPTIVE = -9   # MCPT_ERR_NO_ADAPTIVE
 
 
 class MCPTError(RuntimeError):
@@ -66,6 +67,12 @@ class Convergence(ctypes.Structure):
     _fields_ = [("n_px", ctypes.c_longlong), ("n_above", ctypes.c_longlong), ("sum_q", ctypes.c_ulonglong),
                 ("max_r", ctypes.c_float), ("mean_r", ctypes.c_double), ("passes", ctypes.c_longlong),
                 ("batches", ctypes.c_int)]
+
+
+class Adaptive(ctypes.Structure):
+    """mcpt_adaptive_t (include/mcpt.h): the frame record of an adaptive select."""
+    _fields_ = Convergence._fields_ + [("n_active_blocks", ctypes.c_longlong), ("n_blocks", ctypes.c_longlong),
+                                       ("samples", ctypes.c_longlong)]
 
 
 class Hit(ctypes.Structure):
@@ -184,6 +191,15 @@ def _declare(L: ctypes.CDLL) -> None:
         "mcpt_read_error_map": (i, [_vp, fp]),
         "mcpt_denoise_guided": (i, [_vp, i, f, f]),
         "mcpt_last_stats_ms": (i, [_vp, fp, fp]),
+        "mcpt_adaptive_begin": (i, [_vp, i]),
+        "mcpt_adaptive_end": (i, [_vp]),
+        "mcpt_adaptive_select": (i, [_vp, f, f, ctypes.POINTER(Adaptive)]),
+        "mcpt_read_active_blocks": (i, [_vp, ip, i, ip]),
+        "mcpt_render_adaptive": (i, [_vp, fp, fp, i, i, f, i, f, i]),
+        "mcpt_read_sample_counts": (i, [_vp, ip]),
+        "mcpt_read_resolved": (i, [_vp, fp]),
+        "mcpt_adaptive_info": (i, [_vp, ip, ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_longlong)]),
+        "mcpt_last_adaptive_ms": (i, [_vp, fp, fp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -760,6 +776,91 @@ class Renderer:
             rec = self.convergence(thr, mu_floor)     # (fewer than two batches: MCPT_ERR_NO_STATS)
         rec["rendered"] = done
         rec["converged"] = rec["mean_r"] <= target_error
+        return rec
+
+    # ---- adaptive sampling of 8x8 blocks (mcpt.h)
+    def adaptive_begin(self, min_passes: int = 0) -> None:
+        """mcpt_adaptive_begin: every 8x8 block active with zero passes (needs statistics on)."""
+        _check(lib().mcpt_adaptive_begin(self._h, int(min_passes)), "mcpt_adaptive_begin")
+
+    def adaptive_end(self) -> None:
+        """mcpt_adaptive_end: adaptive mode off, its state freed."""
+        _check(lib().mcpt_adaptive_end(self._h), "mcpt_adaptive_end")
+
+    def adaptive_select(self, threshold: float, mu_floor: float = ERROR_MU_FLOOR) -> dict:
+        """mcpt_adaptive_select: retire the active blocks whose largest r <= threshold (and that hold
+        min_passes); convergence()'s record over all local pixels plus n_active_blocks, n_blocks and
+        samples.  Synchronizes."""
+        rec = Adaptive()
+        _check(lib().mcpt_adaptive_select(self._h, float(threshold), float(mu_floor), ctypes.byref(rec)),
+               "mcpt_adaptive_select")
+        return {k: getattr(rec, k) for k, _ in Adaptive._fields_}
+
+    def adaptive_info(self) -> dict:
+        """{"on", "n_active", "n_blocks"} of the adaptive mode."""
+        on, a, b = ctypes.c_int(), ctypes.c_longlong(), ctypes.c_longlong()
+        _check(lib().mcpt_adaptive_info(self._h, ctypes.byref(on), ctypes.byref(a), ctypes.byref(b)), "mcpt_adaptive_info")
+        return {"on": bool(on.value), "n_active": a.value, "n_blocks": b.value}
+
+    def read_active_blocks(self) -> np.ndarray:
+        """The active block ids (by * ceil(W / 8) + bx over the local grid), ascending."""
+        out = np.zeros(max(self.adaptive_info()["n_blocks"], 1), np.int32)
+        n = ctypes.c_int()
+        _check(lib().mcpt_read_active_blocks(self._h, _ip(out), int(out.size), ctypes.byref(n)), "mcpt_read_active_blocks")
+        return out[:n.value].copy()
+
+    def render_adaptive(self, invPV, invV, first_pass: int, n_passes: int, date: float = 0.0,
+                        bounces: int = 3, refract_ind: float = 1.0, variant: int = MONTECARLO) -> None:
+        """mcpt_render_adaptive: render() for the active blocks only."""
+        a, b = _f32(invPV, 16), _f32(invV, 16)
+        _check(lib().mcpt_render_adaptive(self._h, _fp(a), _fp(b), int(first_pass), int(n_passes), float(date),
+                                          int(bounces), float(refract_ind), int(variant)), "mcpt_render_adaptive")
+
+    def read_sample_counts(self) -> np.ndarray:
+        """(local rows, W) i32: every pixel's sample count."""
+        out = np.zeros((self.n_local_rows, self.W), np.int32)
+        _check(lib().mcpt_read_sample_counts(self._h, _ip(out)), "mcpt_read_sample_counts")
+        return out
+
+    def read_resolved(self) -> np.ndarray:
+        """(local rows, W, 3) f32: accum / (float)count with every pixel's own sample count."""
+        out = np.zeros((self.n_local_rows, self.W, 3), np.float32)
+        _check(lib().mcpt_read_resolved(self._h, _fp(out)), "mcpt_read_resolved")
+        return out
+
+    def last_adaptive_ms(self) -> Tuple[float, float]:
+        """(select ms, adaptive render ms) of the last of each (0: none yet)."""
+        a, b = ctypes.c_float(), ctypes.c_float()
+        _check(lib().mcpt_last_adaptive_ms(self._h, ctypes.byref(a), ctypes.byref(b)), "mcpt_last_adaptive_ms")
+        return a.value, b.value
+
+    def render_adaptive_until(self, invPV, invV, threshold: float, batch: int = 32, max_passes: int = 4096,
+                              min_passes: int = 0, check_every: int = 1, first_pass: int = 1, date: float = 0.0,
+                              bounces: int = 3, refract_ind: float = 1.0, variant: int = MONTECARLO,
+                              mu_floor: float = ERROR_MU_FLOOR) -> dict:
+        """Begin a statistics window and the adaptive mode, then render passes first_pass,
+        first_pass + 1, ... in calls of `batch` passes for the active blocks only, selecting after
+        every `check_every` calls (from the second batch on, and at the cap), until no block is
+        active or `max_passes` passes are rendered.  Returns the last select's record plus
+        "rendered" (the passes the longest-lived blocks received); the mode stays on, so that
+        read_resolved() and read_sample_counts() serve the result."""
+        if batch <= 0 or check_every <= 0 or max_passes <= 0 or not threshold > 0:
+            raise MCPTError("render_adaptive_until: batch, check_every, max_passes and threshold must be positive")
+        self.stats_begin()
+        self.adaptive_begin(min_passes)
+        done, calls, rec = 0, 0, None
+        while done < max_passes:
+            n = min(batch, max_passes - done)
+            self.render_adaptive(invPV, invV, first_pass + done, n, date, bounces, refract_ind, variant)
+            done += n
+            calls += 1
+            if calls >= 2 and (calls % check_every == 0 or done >= max_passes):
+                rec = self.adaptive_select(threshold, mu_floor)
+                if rec["n_active_blocks"] == 0:
+                    break
+        if rec is None:
+            rec = self.adaptive_select(threshold, mu_floor)     # (fewer than two batches: MCPT_ERR_NO_STATS)
+        rec["rendered"] = done
         return rec
 
     def trace(self, origins, dirs, any_hit: bool = False, prim: int = -1) -> np.ndarray:

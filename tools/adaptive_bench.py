@@ -1,0 +1,164 @@
+#!/usr/bin/env python3
+"""Measurements of the adaptive sampling of 8x8 blocks -> profiles/adaptive_bench.json.
+
+    python tools/adaptive_bench.py [--out profiles/adaptive_bench.json] [--reps 9]
+
+(a) select: device time of mcpt_adaptive_select (select kernel + list scan) at 1080p and 4K against
+    its byte floor (16 B of state read, 8 B of map written per active pixel, 12 B per block).
+(b) list path: mcpt_render_adaptive with every block active against mcpt_render of the same passes in
+    dispatch order (MCPT_ITEM_ORDER=0), render lanes off, per-lane traversal, one segment per item —
+    the plain twin of the same kernel — interleaved, device times, medians and spread.
+(d) scenes 1, 6, 8 at 480x270: RMSE of the resolved adaptive image against the scene's own 2,048-spp
+    render (other passes), beside a uniform render of the same sample count and of the same wall time.
+Medians of `reps` runs after warm-ups; the spread is (max - min) / median."""
+import argparse
+import json
+import os
+import sys
+import time
+
+os.environ["MCPT_ITEM_ORDER"] = "0"      # (b)'s twin: dispatch order, one segment per item
+os.environ["MCPT_SEG_PER_ITEM"] = "1"
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(REPO, "montecarlo-pathtracing_amd"))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402,F401  (HIP runtime first)
+import mcpt  # noqa: E402
+
+
+def med(v):
+    v = sorted(v)
+    m = v[len(v) // 2]
+    return {"median": m, "min": v[0], "max": v[-1], "spread": (v[-1] - v[0]) / m if m else 0.0, "n": len(v)}
+
+
+def setup(r, scene, W, H):
+    r.upload_scene(mcpt.Scene.reference(scene))
+    r.set_target(W, H)
+    return mcpt.camera_canonical(W, H)
+
+
+def bench_select(r, reps):
+    out = []
+    for W, H in ((1920, 1080), (3840, 2160)):
+        cam = setup(r, 6, W, H)
+        r.stats_begin()
+        r.adaptive_begin(0)
+        r.render_adaptive(cam[0], cam[1], 1, 8, 0.0, 8)
+        r.render_adaptive(cam[0], cam[1], 9, 8, 0.0, 8)
+        ms = []
+        for k in range(reps + 3):
+            r.adaptive_select(1e-6)            # (nothing above r = 0 retires: the active set stays)
+            if k >= 3:
+                ms.append(r.last_adaptive_ms()[0])
+        info = r.adaptive_info()
+        px_active = info["n_active"] * 64      # (an upper bound at partial blocks)
+        floor_bytes = px_active * (16 + 8) + (W * H - min(W * H, px_active)) * 8 + info["n_blocks"] * 12
+        m = med(ms)
+        out.append({"W": W, "H": H, "n_blocks": info["n_blocks"], "n_active": info["n_active"], "select_ms": m,
+                    "floor_bytes": floor_bytes, "floor_ms_at_8TBs": floor_bytes / 8e12 * 1e3,
+                    "achieved_GBs": floor_bytes / (m["median"] * 1e-3) / 1e9})
+        r.adaptive_end()
+    return out
+
+
+def bench_list_path(r, reps):
+    out = []
+    r.set_traversal(mcpt.TRAVERSAL_LANE)
+    r.set_render_lanes(False)
+    for scene, W, H, n in ((6, 1920, 1080, 64), (8, 1920, 1080, 32), (1, 1920, 1080, 64)):
+        cam = setup(r, scene, W, H)
+        r.stats_begin()
+        r.adaptive_begin(0)
+        plain, listed, first = [], [], 1
+        for k in range(reps + 2):
+            r.render(cam[0], cam[1], first, n, 0.0, 8)
+            a = sum(r.last_kernel_ms())
+            first += n
+            r.render_adaptive(cam[0], cam[1], first, n, 0.0, 8)
+            b = r.last_adaptive_ms()[1]
+            first += n
+            if k >= 2:
+                plain.append(a)
+                listed.append(b)
+        assert r.adaptive_info()["n_active"] == r.adaptive_info()["n_blocks"]
+        p, q = med(plain), med(listed)
+        out.append({"scene": scene, "W": W, "H": H, "passes": n, "bounces": 8, "plain_ms": p, "list_ms": q,
+                    "ratio": q["median"] / p["median"]})
+        r.adaptive_end()
+    r.set_traversal(mcpt.TRAVERSAL_AUTO)
+    r.set_render_lanes(True)
+    return out
+
+
+def rmse(a, b):
+    return float(np.sqrt(np.mean((a.astype(np.float64) - b.astype(np.float64)) ** 2)))
+
+
+def timed_uniform(r, cam, spp, bounces):
+    r.clear_accum()
+    r.synchronize()
+    t0 = time.perf_counter()
+    done = 0
+    while done < spp:
+        n = min(32, spp - done)
+        r.render(cam[0], cam[1], 1 + done, n, 0.0, bounces)
+        done += n
+    acc, n = r.read_accum()
+    return acc / np.float32(n), (time.perf_counter() - t0) * 1e3
+
+
+def bench_point(r, thresholds):
+    out = []
+    W, H, B = 480, 270, 8
+    for scene in (1, 6, 8):
+        cam = setup(r, scene, W, H)
+        r.render(cam[0], cam[1], 100001, 2048, 0.0, B)       # the reference: other passes
+        acc, n = r.read_accum()
+        ref = acc / np.float32(n)
+        timed_uniform(r, cam, 64, B)                          # warm-up (schedule trials)
+        timed_uniform(r, cam, 64, B)
+        for thr in thresholds:
+            r.set_target(W, H)
+            r.synchronize()
+            t0 = time.perf_counter()
+            rec = r.render_adaptive_until(cam[0], cam[1], thr, batch=32, max_passes=1024, min_passes=64, bounces=B)
+            img = r.read_resolved()
+            t_ad = (time.perf_counter() - t0) * 1e3
+            r.adaptive_end()
+            r.stats_end()
+            mean_spp = rec["samples"] / rec["n_px"]
+            spp_eq = max(1, int(round(mean_spp)))
+            u_eq, t_eq = timed_uniform(r, cam, spp_eq, B)
+            spp_t = max(1, int(round(spp_eq * t_ad / t_eq)))
+            u_t, t_t = timed_uniform(r, cam, spp_t, B)
+            out.append({"scene": scene, "W": W, "H": H, "bounces": B, "threshold": thr, "rendered": rec["rendered"],
+                        "mean_spp": mean_spp, "n_active_blocks_at_end": rec["n_active_blocks"],
+                        "adaptive_rmse": rmse(img, ref), "adaptive_wall_ms": t_ad,
+                        "uniform_same_samples": {"spp": spp_eq, "rmse": rmse(u_eq, ref), "wall_ms": t_eq},
+                        "uniform_same_time": {"spp": spp_t, "rmse": rmse(u_t, ref), "wall_ms": t_t}})
+            print(json.dumps(out[-1]), flush=True)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "adaptive_bench.json"))
+    ap.add_argument("--reps", type=int, default=9)
+    ap.add_argument("--thresholds", default="0.2,0.1,0.05")
+    a = ap.parse_args()
+    r = mcpt.Renderer(0)
+    try:
+        res = {"device": torch.cuda.get_device_name(0), "reps": a.reps,
+               "select": bench_select(r, a.reps), "list_path": bench_list_path(r, a.reps),
+               "point": bench_point(r, [float(x) for x in a.thresholds.split(",")])}
+    finally:
+        r.close()
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps({k: res[k] for k in ("select", "list_path")}, indent=1))
+
+
+if __name__ == "__main__":
+    main()
