@@ -1,0 +1,476 @@
+// mcpt_capi_post.hip — C ABI, device half: what runs on a rendered accumulator (guide buffers and
+// the à-trous denoiser, noise statistics and the convergence metric, adaptive sampling).
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+#include "mcpt_ctx.h"
+
+namespace plan = mcpt::plan;
+
+// One batch of the noise statistics: "the accumulator now holds n more passes than
+// at the previous batch", enqueued on the context's stream (which is ordered after every queued
+// render's combine), no host wait.
+hipError_t stats_batch(mcpt_ctx* c, int n) {
+  hipError_t e = ensure_timing_events(c->stats_ev, 2);
+  if (e == hipSuccess) e = hipEventRecord(c->stats_ev[0], c->stream);
+  if (e == hipSuccess)
+    e = mcpt_launch_stats_update(c->d_accum, c->d_stats, (long long)c->n_local_rows * c->W, n, c->stream);
+  if (e == hipSuccess) e = hipEventRecord(c->stats_ev[1], c->stream);
+  if (e != hipSuccess) return e;
+  c->stats_passes += n;
+  c->stats_batches += 1;
+  c->stats_update_timed = true;
+  return hipSuccess;
+}
+
+// the frame's record from the kStatsRecSlots partial records of the error / select kernels: the
+// words add (max for word 2, max_r's bits)
+static void reduce_stats_records(const unsigned long long* part, int n_words, unsigned long long* h) {
+  for (int s = 0; s < mcpt::kStatsRecSlots; ++s) {
+    const unsigned long long* q = part + (size_t)s * mcpt::kStatsRecStride;
+    for (int w = 0; w < n_words; ++w) h[w] = w == 2 ? std::max(h[2], q[2] & 0xffffffffull) : h[w] + q[w];
+  }
+}
+// ... into the leading fields mcpt_convergence_t and mcpt_adaptive_t share
+template <class Rec>
+static void fill_frame_record(const mcpt_ctx* c, const unsigned long long* h, Rec* out) {
+  const long long n = (long long)c->n_local_rows * c->W;
+  out->n_px = n;
+  out->n_above = (long long)h[0];
+  out->sum_q = h[1];
+  const unsigned mb = (unsigned)(h[2] & 0xffffffffull);
+  std::memcpy(&out->max_r, &mb, sizeof(float));
+  out->mean_r = n > 0 ? (double)h[1] / 65536.0 / (double)n : 0.0;
+  out->passes = c->stats_passes;
+  out->batches = c->stats_batches;
+}
+// elapsed ms of an optional event pair into *out (null: not asked for): 0 unless the pair was recorded
+static int pair_ms(bool timed, hipEvent_t ev_a, hipEvent_t ev_b, float* out) {
+  if (!out) return MCPT_OK;
+  *out = 0.0f;
+  if (timed) {
+    HIP_OR_RETURN(hipEventSynchronize(ev_b));
+    HIP_OR_RETURN(hipEventElapsedTime(out, ev_a, ev_b));
+  }
+  return MCPT_OK;
+}
+
+extern "C" {
+
+// ---- guide buffers and the à-trous denoiser (mcpt_denoise.hip)
+// the kernel of the filter's steps 1 and 2 when MCPT_DENOISE_NAIVE is unset: 0 the LDS-tile
+// kernels, 1 the global-tap kernel (the A/B: tools/denoise_bench.py, profiles/denoise_bench.json)
+constexpr int kAtrousNaiveDefault = 0;
+static hipError_t ensure_denoise_buffers(mcpt_ctx* c) {
+  if (c->d_guide) return hipSuccess;
+  const size_t n = (size_t)c->n_local_rows * c->W;
+  if (!n) return hipSuccess;
+  hipError_t e = hipMalloc(&c->d_guide, n * 2 * sizeof(float4));
+  if (e == hipSuccess) e = hipMalloc(&c->d_albedo, n * sizeof(float4));
+  if (e == hipSuccess) e = hipMalloc(&c->d_dn[0], n * sizeof(float4));
+  if (e == hipSuccess) e = hipMalloc(&c->d_dn[1], n * sizeof(float4));
+  if (e != hipSuccess) free_denoise(c);
+  return e;
+}
+int mcpt_render_guides(mcpt_ctx* c, const float* invPV, const float* invV) {
+  OK_OR_RETURN(check_renderable(c, invPV && invV, "mcpt_render_guides"));
+  HIP_OR_RETURN(hipSetDevice(c->device));
+  HIP_OR_RETURN(ensure_denoise_buffers(c));
+  HIP_OR_RETURN(ensure_timing_events(c->guide_ev, 2));
+  mcpt::GuideParams g;
+  std::memset(&g, 0, sizeof(g));
+  scene_params(c, invPV, invV, g.r);   // (guide_kernel reads none of accum, events, lds_scene_bytes, tile_w)
+  g.guide = c->d_guide; g.albedo = c->d_albedo;
+  HIP_OR_RETURN(hipEventRecord(c->guide_ev[0], c->stream));
+  HIP_OR_RETURN(mcpt_launch_guides(g, c->stream));
+  HIP_OR_RETURN(hipEventRecord(c->guide_ev[1], c->stream));
+  c->guides_valid = true;
+  c->guides_timed = true;
+  return MCPT_OK;
+}
+
+int mcpt_read_guides(mcpt_ctx* c, float* guide8, float* albedo4) {
+  if (!c) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  if (!c->has_target) return mcpt_err_bare(MCPT_ERR_NO_TARGET);
+  if (!c->guides_valid) return set_err(MCPT_ERR_NO_GUIDES, "mcpt_read_guides: no guides rendered for this target and scene");
+  HIP_OR_RETURN(hipSetDevice(c->device));
+  const size_t n = (size_t)c->n_local_rows * c->W;
+  if (guide8 && n)
+    HIP_OR_RETURN(hipMemcpyAsync(guide8, c->d_guide, n * 2 * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+  if (albedo4 && n)
+    HIP_OR_RETURN(hipMemcpyAsync(albedo4, c->d_albedo, n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+  HIP_OR_RETURN(hipStreamSynchronize(c->stream));
+  return MCPT_OK;
+}
+
+// mcpt_denoise (guided false: sigma_color is the global width) and mcpt_denoise_guided (guided
+// true: sigma_color is k_color, the width per pixel k_color * 2^-s * se from the error map)
+static int denoise_run(mcpt_ctx* c, int iterations, float sigma_color, float sigma_plane, bool guided) {
+  if (!c || iterations < 0 || iterations > 8) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_denoise: iterations not in 0..8");
+  if (!(sigma_color > 0.0f) || !(sigma_plane > 0.0f) || !std::isfinite(sigma_color) || !std::isfinite(sigma_plane))
+    return set_err(MCPT_ERR_INVALID_ARG, "mcpt_denoise: sigmas must be positive and finite");
+  if (!c->has_target) return set_err(MCPT_ERR_NO_TARGET, "no render target");
+  bool full = c->n_local_rows == c->H;
+  for (int i = 0; full && i < c->n_local_rows; ++i) full = c->rows[(size_t)i] == i;
+  if (!full) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_denoise: needs a full-frame target (gather the shards first)");
+  if (c->pass_count <= 0) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_denoise: the accumulator holds no passes");
+  if (c->ad_on && c->ad_n_list < c->ad_n_blocks)
+    return set_err(MCPT_ERR_INVALID_ARG, "mcpt_denoise: adaptive mode has retired blocks (per-pixel sample counts)");
+  if (!c->guides_valid) return set_err(MCPT_ERR_NO_GUIDES, "mcpt_denoise: no guides rendered for this target and scene");
+  if (guided && !(c->stats_on && c->emap_valid))
+    return set_err(MCPT_ERR_NO_STATS, "mcpt_denoise_guided: no error map (mcpt_convergence) of the current statistics");
+  HIP_OR_RETURN(hipSetDevice(c->device));
+  HIP_OR_RETURN(ensure_denoise_buffers(c));
+  HIP_OR_RETURN(ensure_timing_events(c->dn_ev, 10));
+  // which kernel runs steps 1 and 2 (same bits): MCPT_DENOISE_NAIVE=1 the
+  // global-tap kernel, =0 the LDS-tile kernels, unset the measured default
+  const bool naive = env_int("MCPT_DENOISE_NAIVE", kAtrousNaiveDefault) != 0;
+  int lds_mask = 0;
+  const long long n = (long long)c->H * c->W;
+  // (the context's stream is ordered after all queued renders: their combines run on it)
+  HIP_OR_RETURN(hipEventRecord(c->dn_ev[9], c->stream));
+  HIP_OR_RETURN(mcpt_launch_average4(c->d_accum, c->d_dn[0], n, c->pass_count, c->stream));
+  HIP_OR_RETURN(hipEventRecord(c->dn_ev[0], c->stream));
+  for (int s = 0; s < iterations; ++s) {
+    const int step = 1 << s;
+    // the iteration's constants in binary32: 2^-s and step are exact factors
+    const float sc = sigma_color * std::ldexp(1.0f, -s);
+    const float sp = sigma_plane * (float)step;
+    // (guided: the kernel forms kc per pixel from sc = k_color * 2^-s and the pixel's se, §3.8)
+    const float kc = guided ? sc : 1.0f / (sc * sc), kp = 1.0f / (sp * sp);
+    HIP_OR_RETURN(mcpt_launch_atrous(c->d_dn[s & 1], c->d_dn[(s + 1) & 1], c->d_guide, c->W, c->H, step, kc, kp,
+                                     guided ? c->d_emap : nullptr, naive, c->stream));
+    HIP_OR_RETURN(hipEventRecord(c->dn_ev[s + 1], c->stream));
+    if (!naive && step <= 2) lds_mask |= 1 << s;
+  }
+  c->dn_lds_mask = lds_mask;
+  c->dn_result = iterations & 1;
+  c->dn_iters = iterations;
+  return MCPT_OK;
+}
+
+int mcpt_denoise(mcpt_ctx* c, int iterations, float sigma_color, float sigma_plane) {
+  return denoise_run(c, iterations, sigma_color, sigma_plane, false);
+}
+
+int mcpt_denoise_guided(mcpt_ctx* c, int iterations, float k_color, float sigma_plane) {
+  return denoise_run(c, iterations, k_color, sigma_plane, true);
+}
+
+// ---- noise statistics and the convergence metric (mcpt_stats.hip)
+int mcpt_stats_begin(mcpt_ctx* c) {
+  if (!c) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  if (!c->has_target) return set_err(MCPT_ERR_NO_TARGET, "no render target");
+  HIP_OR_RETURN(hipSetDevice(c->device));
+  const size_t n = (size_t)c->n_local_rows * c->W;
+  if (!c->d_conv) {
+    hipError_t e = hipMalloc(&c->d_conv, sizeof(unsigned long long) * mcpt::kStatsRecWords);
+    if (e == hipSuccess && n) e = hipMalloc(&c->d_stats, n * sizeof(float4));
+    if (e == hipSuccess && n) e = hipMalloc(&c->d_emap, n * sizeof(float2));
+    if (e != hipSuccess) {
+      free_stats(c);
+      return set_err(MCPT_ERR_HIP, "mcpt_stats_begin: hipMalloc", e);
+    }
+  }
+  HIP_OR_RETURN(mcpt_launch_stats_begin(c->d_accum, c->d_stats, (long long)n, c->stream));
+  c->stats_on = true;
+  c->stats_passes = 0;
+  c->stats_batches = 0;
+  c->emap_valid = false;
+  return MCPT_OK;
+}
+
+int mcpt_stats_end(mcpt_ctx* c) {
+  if (!c) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  HIP_OR_RETURN(hipSetDevice(c->device));
+  if (c->d_conv) HIP_OR_RETURN(hipStreamSynchronize(c->stream));   // (queued updates still use the buffers)
+  free_stats(c);
+  free_adaptive(c);   // (the adaptive mode selects from the statistics: off with them)
+  return MCPT_OK;
+}
+
+int mcpt_stats_add_batch(mcpt_ctx* c, int n) {
+  if (!c || n <= 0) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_stats_add_batch: a batch holds at least one pass");
+  if (!c->stats_on) return set_err(MCPT_ERR_NO_STATS, "mcpt_stats_add_batch: statistics are off (mcpt_stats_begin)");
+  HIP_OR_RETURN(hipSetDevice(c->device));
+  HIP_OR_RETURN(stats_batch(c, n));
+  return MCPT_OK;
+}
+
+int mcpt_stats_info(mcpt_ctx* c, int* on, long long* passes, int* batches) {
+  if (!c) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  if (on) *on = c->stats_on ? 1 : 0;
+  if (passes) *passes = c->stats_passes;
+  if (batches) *batches = c->stats_batches;
+  return MCPT_OK;
+}
+
+int mcpt_convergence(mcpt_ctx* c, float threshold, float mu_floor, mcpt_convergence_t* out) {
+  if (!c || !out) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  if (!(threshold > 0.0f) || !(mu_floor > 0.0f) || !std::isfinite(threshold) || !std::isfinite(mu_floor))
+    return set_err(MCPT_ERR_INVALID_ARG, "mcpt_convergence: threshold and mu_floor must be positive and finite");
+  if (!c->stats_on) return set_err(MCPT_ERR_NO_STATS, "mcpt_convergence: statistics are off (mcpt_stats_begin)");
+  if (c->stats_batches < 2) return set_err(MCPT_ERR_NO_STATS, "mcpt_convergence: needs two batches or more");
+  HIP_OR_RETURN(hipSetDevice(c->device));
+  HIP_OR_RETURN(ensure_timing_events(c->stats_ev + 2, 2));
+  const long long n = (long long)c->n_local_rows * c->W;
+  HIP_OR_RETURN(hipEventRecord(c->stats_ev[2], c->stream));
+  HIP_OR_RETURN(mcpt_launch_stats_error(c->d_stats, c->d_emap, n, c->stats_passes, c->stats_batches, mu_floor,
+                                        threshold, c->d_conv, c->stream));
+  HIP_OR_RETURN(hipEventRecord(c->stats_ev[3], c->stream));
+  c->stats_error_timed = true;
+  c->emap_valid = true;
+  unsigned long long part[mcpt::kStatsRecWords] = {};
+  HIP_OR_RETURN(hipMemcpyAsync(part, c->d_conv, sizeof(part), hipMemcpyDeviceToHost, c->stream));
+  HIP_OR_RETURN(hipStreamSynchronize(c->stream));
+  unsigned long long h[3] = {0, 0, 0};
+  reduce_stats_records(part, 3, h);
+  fill_frame_record(c, h, out);
+  return MCPT_OK;
+}
+
+int mcpt_read_error_map(mcpt_ctx* c, float* se_r2) {
+  if (!c || !se_r2) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  if (!c->stats_on || c->stats_batches < 2 || !c->emap_valid)
+    return set_err(MCPT_ERR_NO_STATS, "mcpt_read_error_map: no mcpt_convergence of the current statistics");
+  HIP_OR_RETURN(hipSetDevice(c->device));
+  const size_t n = (size_t)c->n_local_rows * c->W;
+  if (n) HIP_OR_RETURN(hipMemcpyAsync(se_r2, c->d_emap, n * sizeof(float2), hipMemcpyDeviceToHost, c->stream));
+  HIP_OR_RETURN(hipStreamSynchronize(c->stream));
+  return MCPT_OK;
+}
+
+int mcpt_last_stats_ms(mcpt_ctx* c, float* update_ms, float* error_ms) {
+  if (!c) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  HIP_OR_RETURN(hipSetDevice(c->device));
+  OK_OR_RETURN(pair_ms(c->stats_update_timed, c->stats_ev[0], c->stats_ev[1], update_ms));
+  return pair_ms(c->stats_error_timed, c->stats_ev[2], c->stats_ev[3], error_ms);
+}
+
+// ---- adaptive sampling of 8x8 blocks (mcpt_adaptive.hip)
+int mcpt_adaptive_begin(mcpt_ctx* c, int min_passes) {
+  if (!c || min_passes < 0) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_adaptive_begin: min_passes must not be negative");
+  if (!c->has_target) return set_err(MCPT_ERR_NO_TARGET, "no render target");
+  if (!c->stats_on) return set_err(MCPT_ERR_NO_STATS, "mcpt_adaptive_begin: statistics are off (mcpt_stats_begin)");
+  HIP_OR_RETURN(hipSetDevice(c->device));
+  const int bx = (c->W + 7) / 8, by = (c->n_local_rows + 7) / 8;
+  if (!c->d_ad_flags) {
+    const size_t n = (size_t)std::max(bx * by, 1);
+    hipError_t e = hipMalloc(&c->d_ad_flags, n * sizeof(int));
+    if (e == hipSuccess) e = hipMalloc(&c->d_ad_passes, n * sizeof(int));
+    if (e == hipSuccess) e = hipMalloc(&c->d_ad_list, (n + 1) * sizeof(int));
+    if (e != hipSuccess) {
+      free_adaptive(c);
+      return set_err(MCPT_ERR_HIP, "mcpt_adaptive_begin: hipMalloc", e);
+    }
+  }
+  c->ad_blocks_x = bx;
+  c->ad_n_blocks = bx * by;
+  c->ad_p0 = c->pass_count;
+  c->ad_min_passes = min_passes;
+  HIP_OR_RETURN(mcpt_launch_adaptive_reset(adaptive_target(c), c->d_ad_list, c->d_ad_list + c->ad_n_blocks, c->stream));
+  c->ad_n_list = c->ad_n_blocks;
+  c->ad_on = true;
+  return MCPT_OK;
+}
+
+int mcpt_adaptive_end(mcpt_ctx* c) {
+  if (!c) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  HIP_OR_RETURN(hipSetDevice(c->device));
+  if (c->d_ad_flags) HIP_OR_RETURN(hipStreamSynchronize(c->stream));   // (queued launches still read the list)
+  free_adaptive(c);
+  return MCPT_OK;
+}
+
+int mcpt_adaptive_info(mcpt_ctx* c, int* on, long long* n_active, long long* n_blocks) {
+  if (!c) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  if (on) *on = c->ad_on ? 1 : 0;
+  if (n_active) *n_active = c->ad_on ? c->ad_n_list : 0;
+  if (n_blocks) *n_blocks = c->ad_on ? c->ad_n_blocks : 0;
+  return MCPT_OK;
+}
+
+int mcpt_adaptive_select(mcpt_ctx* c, float threshold, float mu_floor, mcpt_adaptive_t* out) {
+  if (!c || !out) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  if (!c->ad_on) return set_err(MCPT_ERR_NO_ADAPTIVE, "mcpt_adaptive_select: adaptive mode is off (mcpt_adaptive_begin)");
+  if (!(threshold > 0.0f) || !(mu_floor > 0.0f) || !std::isfinite(threshold) || !std::isfinite(mu_floor))
+    return set_err(MCPT_ERR_INVALID_ARG, "mcpt_adaptive_select: threshold and mu_floor must be positive and finite");
+  if (!c->stats_on) return set_err(MCPT_ERR_NO_STATS, "mcpt_adaptive_select: statistics are off (mcpt_stats_begin)");
+  if (c->stats_batches < 2) return set_err(MCPT_ERR_NO_STATS, "mcpt_adaptive_select: needs two batches or more");
+  HIP_OR_RETURN(hipSetDevice(c->device));
+  HIP_OR_RETURN(ensure_timing_events(c->ad_ev, 2));
+  const mcpt::AdaptiveTarget t = adaptive_target(c);
+  int* d_count = c->d_ad_list + c->ad_n_blocks;
+  HIP_OR_RETURN(hipEventRecord(c->ad_ev[0], c->stream));
+  HIP_OR_RETURN(mcpt_launch_adaptive_select(t, c->d_stats, c->d_emap, c->stats_passes, c->stats_batches, mu_floor,
+                                            threshold, c->ad_min_passes, c->d_conv, c->stream));
+  HIP_OR_RETURN(mcpt_launch_adaptive_compact(t, c->d_ad_list, d_count, c->stream));
+  HIP_OR_RETURN(hipEventRecord(c->ad_ev[1], c->stream));
+  c->ad_select_timed = true;
+  c->emap_valid = true;
+  unsigned long long part[mcpt::kStatsRecWords] = {};
+  int n_list = 0;
+  HIP_OR_RETURN(hipMemcpyAsync(part, c->d_conv, sizeof(part), hipMemcpyDeviceToHost, c->stream));
+  HIP_OR_RETURN(hipMemcpyAsync(&n_list, d_count, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIP_OR_RETURN(hipStreamSynchronize(c->stream));
+  unsigned long long h[5] = {0, 0, 0, 0, 0};
+  reduce_stats_records(part, 5, h);
+  if (n_list < 0 || n_list > c->ad_n_blocks || (unsigned long long)n_list != h[4])
+    return set_err(MCPT_ERR_HIP, "mcpt_adaptive_select: the active list and the block flags disagree");
+  c->ad_n_list = n_list;
+  fill_frame_record(c, h, out);
+  out->n_active_blocks = n_list;
+  out->n_blocks = c->ad_n_blocks;
+  out->samples = (long long)h[3];
+  return MCPT_OK;
+}
+
+int mcpt_read_active_blocks(mcpt_ctx* c, int* ids, int capacity, int* n) {
+  if (!c || !n || (capacity > 0 && !ids) || capacity < 0) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  if (!c->ad_on) return set_err(MCPT_ERR_NO_ADAPTIVE, "mcpt_read_active_blocks: adaptive mode is off (mcpt_adaptive_begin)");
+  HIP_OR_RETURN(hipSetDevice(c->device));
+  *n = c->ad_n_list;
+  const int k = std::min(capacity, c->ad_n_list);
+  if (k > 0) HIP_OR_RETURN(hipMemcpyAsync(ids, c->d_ad_list, sizeof(int) * (size_t)k, hipMemcpyDeviceToHost, c->stream));
+  HIP_OR_RETURN(hipStreamSynchronize(c->stream));
+  return MCPT_OK;
+}
+
+// The listed blocks' passes first_pass .. first_pass + n_passes - 1 on the context's stream (ordered
+// after the render lanes): the scene's per-lane kernel's LIST twin, one segment per item, dispatch
+// order.  No part in AUTO's trials, the item-cost sort, the render lanes or the timing ring.
+int mcpt_render_adaptive(mcpt_ctx* c, const float* invPV, const float* invV, int first_pass, int n_passes, float date,
+                         int bounces, float refract_ind, int variant) {
+  const bool args_ok = invPV && invV && n_passes >= 0 && variant >= 0 && variant <= 2;
+  if (c && args_ok && !c->ad_on)
+    return set_err(MCPT_ERR_NO_ADAPTIVE, "mcpt_render_adaptive: adaptive mode is off (mcpt_adaptive_begin)");
+  OK_OR_RETURN(check_renderable(c, args_ok, "mcpt_render_adaptive"));
+  if (c->ad_n_list == 0 || n_passes == 0) return MCPT_OK;   // every block retired: nothing to launch
+  HIP_OR_RETURN(hipSetDevice(c->device));
+  mcpt::RenderParams p;
+  scene_params(c, invPV, invV, p);
+  pass_params(first_pass, n_passes, date, bounces, refract_ind, variant, p);
+  p.walk_exit = plan::resolve_walk_exit(c->walk_exit, c->n_meshes, c->depth);
+  p.leaf_batch = plan::resolve_leaf_batch(c->leaf_batch, c->depth);
+  p.walk_min_done = 1;
+  p.seg_per_item = 1;
+  p.list = c->d_ad_list;
+  p.n_list = c->ad_n_list;
+  p.blocks_x = c->ad_blocks_x;
+  p.n_blocks = c->ad_n_blocks;
+  const int per_group = p.tile_w / 8;
+  p.n_tiles = (p.n_list + per_group - 1) / per_group;   // workgroup groups of the list
+  plan::LimitsIn lin;   // (no spare workgroups, no pass stealing)
+  lin.n_local_px = p.n_local_px; lin.n_tiles = p.n_tiles; lin.tile_w = p.tile_w; lin.n_cu = c->n_cu;
+  lin.partial_budget = c->partial_budget; lin.mesh = c->n_meshes > 0; lin.steal = false; lin.spare = false;
+  const long long max_seg = plan::limits(lin).max_seg;
+  const size_t seg_bytes = (size_t)p.n_local_px * 3 * sizeof(float);
+  HIP_OR_RETURN(ensure_timing_events(c->ad_ev + 2, 2));
+  mcpt_ctx::Lane& L = c->lanes[0];   // its segment-sum buffer (free: `stream` is ordered after the lanes' work)
+  HIP_OR_RETURN(hipEventRecord(c->ad_ev[2], c->stream));
+  // sub-launches at chunk boundaries, as launch() cuts them (segment-sum budget, grid size)
+  plan::SubLaunch sub;
+  int k = 0;
+  for (long long lo = first_pass, end = (long long)first_pass + n_passes; lo < end; lo = sub.end(), ++k) {
+    sub = plan::next_sub_launch(lo, end, max_seg, false);
+    p.first_pass = sub.first_pass; p.n_passes = sub.n_passes; p.n_segments = sub.n_segments;
+    p.n_items = (int)((long long)p.n_tiles * p.n_segments);
+    if (p.n_segments > 1) OK_OR_RETURN(ensure_lane_bytes(c, L.d_partial, L.partial_bytes, (size_t)p.n_segments * seg_bytes));
+    p.partial = L.d_partial;
+    HIP_OR_RETURN(mcpt_launch_render_list(p, c->stream));
+    HIP_OR_RETURN(mcpt_launch_combine_list(p, c->stream));
+    L.freed_stale = true;   // (the lane's next launch waits for `stream`'s work so far)
+#ifdef MCPT_CHECKED
+    OK_OR_RETURN(checked_sub_launch(c, k, -1, p));
+#endif
+  }
+  (void)k;
+  HIP_OR_RETURN(hipEventRecord(c->ad_ev[3], c->stream));
+  c->ad_render_timed = true;
+  HIP_OR_RETURN(mcpt_launch_adaptive_add_passes(adaptive_target(c), c->d_ad_list, c->ad_n_list, n_passes, c->stream));
+  c->pass_count += n_passes;   // the active blocks' count: the largest
+  if (c->stats_on) HIP_OR_RETURN(stats_batch(c, n_passes));
+  return MCPT_OK;
+}
+
+int mcpt_read_sample_counts(mcpt_ctx* c, int* counts) {
+  if (!c || !counts) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  if (!c->ad_on) return set_err(MCPT_ERR_NO_ADAPTIVE, "mcpt_read_sample_counts: adaptive mode is off (mcpt_adaptive_begin)");
+  HIP_OR_RETURN(hipSetDevice(c->device));
+  const size_t n = (size_t)c->n_local_rows * c->W;
+  if (n) {
+    int* d = nullptr;
+    HIP_OR_RETURN(hipMalloc(&d, n * sizeof(int)));
+    hipError_t e = mcpt_launch_adaptive_counts(adaptive_target(c), d, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(counts, d, n * sizeof(int), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    (void)hipFree(d);
+    if (e != hipSuccess) return set_err(MCPT_ERR_HIP, "mcpt_read_sample_counts", e);
+  }
+  return MCPT_OK;
+}
+
+int mcpt_read_resolved(mcpt_ctx* c, float* rgb) {
+  if (!c || !rgb) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  if (!c->ad_on) return set_err(MCPT_ERR_NO_ADAPTIVE, "mcpt_read_resolved: adaptive mode is off (mcpt_adaptive_begin)");
+  HIP_OR_RETURN(hipSetDevice(c->device));
+  const size_t n = (size_t)c->n_local_rows * c->W;
+  if (n) {
+    float* d = nullptr;
+    HIP_OR_RETURN(hipMalloc(&d, n * 3 * sizeof(float)));
+    hipError_t e = mcpt_launch_adaptive_resolve(adaptive_target(c), c->d_accum, d, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(rgb, d, n * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    (void)hipFree(d);
+    if (e != hipSuccess) return set_err(MCPT_ERR_HIP, "mcpt_read_resolved", e);
+  }
+  return MCPT_OK;
+}
+
+int mcpt_last_adaptive_ms(mcpt_ctx* c, float* select_ms, float* render_ms) {
+  if (!c) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  HIP_OR_RETURN(hipSetDevice(c->device));
+  OK_OR_RETURN(pair_ms(c->ad_select_timed, c->ad_ev[0], c->ad_ev[1], select_ms));
+  return pair_ms(c->ad_render_timed, c->ad_ev[2], c->ad_ev[3], render_ms);
+}
+
+int mcpt_read_denoised(mcpt_ctx* c, float* rgb_out) {
+  if (!c || !rgb_out) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  if (!c->has_target) return mcpt_err_bare(MCPT_ERR_NO_TARGET);
+  if (c->dn_result < 0) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_read_denoised: no mcpt_denoise on this target yet");
+  HIP_OR_RETURN(hipSetDevice(c->device));
+  const size_t n = (size_t)c->n_local_rows * c->W;
+  std::vector<float4> h(n);
+  if (n) HIP_OR_RETURN(hipMemcpyAsync(h.data(), c->d_dn[c->dn_result], n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+  HIP_OR_RETURN(hipStreamSynchronize(c->stream));
+  for (size_t i = 0; i < n; ++i) {
+    rgb_out[3 * i] = h[i].x; rgb_out[3 * i + 1] = h[i].y; rgb_out[3 * i + 2] = h[i].z;
+  }
+  return MCPT_OK;
+}
+
+int mcpt_last_denoise_ms(mcpt_ctx* c, float* guides_ms, float* filter_ms) {
+  if (!c) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  HIP_OR_RETURN(hipSetDevice(c->device));
+  OK_OR_RETURN(pair_ms(c->guides_timed, c->guide_ev[0], c->guide_ev[1], guides_ms));
+  // (the average and every iteration)
+  return pair_ms(c->dn_iters >= 0, c->dn_ev[9], c->dn_ev[std::max(c->dn_iters, 0)], filter_ms);
+}
+
+int mcpt_last_denoise_path(mcpt_ctx* c, int* lds_mask) {
+  if (!c || !lds_mask || c->dn_iters < 0) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  *lds_mask = c->dn_lds_mask;
+  return MCPT_OK;
+}
+
+int mcpt_denoise_iteration_ms(mcpt_ctx* c, int iteration, float* ms) {
+  if (!c || !ms || iteration < -1 || iteration >= c->dn_iters) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  HIP_OR_RETURN(hipSetDevice(c->device));
+  hipEvent_t a = iteration < 0 ? c->dn_ev[9] : c->dn_ev[iteration], b = c->dn_ev[iteration + 1];
+  HIP_OR_RETURN(hipEventSynchronize(b));
+  HIP_OR_RETURN(hipEventElapsedTime(ms, a, b));
+  return MCPT_OK;
+}
+
+}  // extern "C"

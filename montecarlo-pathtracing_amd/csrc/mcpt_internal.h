@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "mcpt_plan.h"
 
 // an error return without a detail (mcpt_capi.hip): drops the calling thread's unread detail of an
 // earlier failure, so mcpt_error_string never attaches it to this one
@@ -32,22 +33,11 @@ constexpr int kEventBytes[EV_COUNT] = {
 //   node  : 3 × float4  (centre.xyz,0) (halfwidth.xyz,0) (1/halfwidth.xyz,0)
 //   prim  : 8 × float4  inverse rows 0..2, transform rows 0..2, colour, material
 constexpr int kNodeF4 = 3;
-// accumulation chunk of the arithmetic contract: passes are summed from 0
-// inside each chunk of kPassChunk consecutive absolute pass numbers, chunk sums added to
-// the accumulator in chunk order
-constexpr int kPassChunk = 32;
-constexpr int kSplitPieces = 4;   // pass ranges of a split work item (RenderParams::split_n)
 constexpr size_t kBlockTimeSlots = size_t(8) << 20;   // diagnostic build: per-wave clock pairs
 constexpr size_t kBlockTimeBase = 64;                   // after the debug slots (= MCPT_DEBUG_SLOTS)
 // largest scene render_kernel stages into LDS: 160 KB / 7 workgroups - 19 KB of per-pixel rows
 constexpr int kLdsSceneBytes = 3584;
 constexpr int kPrimF4 = 8;
-// work-item tile (pixels): a work item is a kTileW x kTileH pixel tile for one pass chunk, one
-// lane per pixel, made of 8x8-pixel waves side by side: 32x8 = four waves in one 8-row strip, so
-// in a row-band shard (8-row bands) all waves of a workgroup lie in one band of the image (16x16
-// tiles: the slowest 8-GPU shard 2.4-4.1 % slower, profiles/r01_ab33_tile_shape.jsonl)
-constexpr int kTileW = 32, kTileH = 8;
-constexpr int kTileThreads = kTileW * kTileH;   // the widest tile (LDS-scene kernels)
 static_assert(kTileW % 8 == 0 && kTileH % 8 == 0 && kTileThreads <= 1024, "tiles are made of 8x8 waves");
 // Tile width of a render launch: a workgroup holds its LDS (per-pixel rows, staged scene) until
 // its LAST wave ends, so the waves that end early leave their slots idle when no further

@@ -34,7 +34,7 @@ __all__ = [
 MONTECARLO, MAT, MAT_TR = 0, 1, 2
 TRAVERSAL_AUTO, TRAVERSAL_LANE, TRAVERSAL_WAVE, TRAVERSAL_STREAM = 0, 1, 2, 3
 # launches of one shape AUTO spends on its timing trials before it settles (up to five candidate
-# schedules, each timed twice: mcpt_capi.hip kTuneRounds; a trial's time is read when the call
+# schedules, each timed twice: mcpt_plan.h kTuneRounds; a trial's time is read when the call
 # after the next one starts, so the decision comes two calls after the last trial); callers that
 # measure run these first
 AUTO_TRIALS = 12
