@@ -207,6 +207,22 @@ int mcpt_copy_accum_device(mcpt_ctx* ctx, void* dst_dev_ptr, size_t bytes);
  * Multi-process (torch.distributed) callers gather mcpt_accum_device_ptr with RCCL instead.
  * Asynchronous; mcpt_read_accum(frame) synchronizes. */
 int mcpt_gather_rows(mcpt_ctx* frame, mcpt_ctx* const* shards, int n_shards);
+/* mcpt_gather_rows for shards with per-pixel sample counts (adaptive sampling): the
+ * same peer copies, stream ordering in both directions and device / event restore, but the shards
+ * may hold different pass counts and each shard's counts travel with its rows into `frame`'s count
+ * plane (one int32 per pixel, 4 B/px, allocated by the first counted gather after a
+ * mcpt_set_target* and freed by the next mcpt_set_target* / mcpt_destroy).  A shard with the
+ * adaptive mode on contributes its pixels' counts (mcpt_read_sample_counts' values), a shard with
+ * the mode off its pass count for all its pixels; frame's pass count becomes the largest shard pass
+ * count.  Every row of `frame` (a full-frame target in row order) must be held by exactly one
+ * shard, else MCPT_ERR_INVALID_ARG: no pixel is left with count 0.  Afterwards `frame` has
+ * per-pixel counts: mcpt_read_sample_counts and mcpt_read_resolved serve the plane and
+ * mcpt_denoise_resolved filters the frame (mcpt_denoise_resolved_guided returns MCPT_ERR_NO_STATS:
+ * the shards' error maps do not travel).  The plane stays valid until frame's accumulator changes:
+ * mcpt_set_target*, mcpt_clear_accum, mcpt_write_accum, mcpt_checkpoint_load, mcpt_gather_rows and
+ * any mcpt_render* into `frame` invalidate it.  Out of scope: the multi-process (torch.distributed
+ * / RCCL) gather carries no counts. */
+int mcpt_gather_rows_counted(mcpt_ctx* frame, mcpt_ctx* const* shards, int n_shards);
 
 /* Select the traversal strategy (mcpt_traversal) for later renders; default AUTO.  AUTO times
  * its schedule candidates on the first launches of >= 2^24 samples after a scene upload — the
@@ -355,10 +371,10 @@ int mcpt_last_denoise_path(mcpt_ctx* ctx, int* lds_mask);
  * asynchronous); from then on every mcpt_render / mcpt_render_counted of n_passes > 0 appends one
  * batch of its n_passes, enqueued on the context's stream behind the call's last combine without a
  * host wait, whatever the schedule and however many launches the call runs.  mcpt_clear_accum,
- * mcpt_write_accum, mcpt_checkpoint_load and mcpt_gather_rows do not touch the statistics: after
+ * mcpt_write_accum, mcpt_checkpoint_load and mcpt_gather_rows* do not touch the statistics: after
  * them the caller declares the accumulator's n new passes as a batch (mcpt_stats_add_batch, n > 0;
- * asynchronous) or begins again.  Checkpoints do not store statistics: a resumed render begins a
- * new window.
+ * asynchronous) or begins again.  mcpt_checkpoint_save's files do not store statistics: a render
+ * resumed from one begins a new window (mcpt_adaptive_checkpoint_save's do).
  *
  * mcpt_convergence: per local pixel the standard error `se` of the window's mean luminance and the
  * relative error r = se / (max(0, mean) + mu_floor), clamped to 64 (an overflowed pixel counts 64),
@@ -434,11 +450,30 @@ int mcpt_last_stats_ms(mcpt_ctx* ctx, float* update_ms, float* error_ms);
  * last adaptive render (with its combines); 0 for what has not run.  Waits for them.
  * With the mode off the other calls return MCPT_ERR_NO_ADAPTIVE.
  *
- * Out of scope: mcpt_denoise*, mcpt_checkpoint_save, mcpt_gather_rows, mcpt_read_accum's pass count
- * and mcpt_clear_accum / mcpt_write_accum know nothing of per-pixel counts (end the mode before
- * replacing the accumulator).  Once a block has retired, mcpt_denoise and mcpt_denoise_guided
- * return MCPT_ERR_INVALID_ARG instead of an image divided by the wrong count.  Checkpoints and
- * multi-GPU gathers of adaptive frames are later work. */
+ * mcpt_denoise, mcpt_denoise_guided, mcpt_checkpoint_save, mcpt_gather_rows, mcpt_read_accum's pass
+ * count and mcpt_clear_accum / mcpt_write_accum know nothing of per-pixel counts (end the mode
+ * before replacing the accumulator).  Once a block has retired, mcpt_denoise and mcpt_denoise_guided
+ * return MCPT_ERR_INVALID_ARG instead of an image divided by the wrong count; the forms below
+ * filter, checkpoint and gather frames with per-pixel counts.
+ *
+ * A context HAS PER-PIXEL SAMPLE COUNTS when (a) the adaptive mode is on (the count of a pixel is
+ * the pass count at mcpt_adaptive_begin plus its block's passes) or (b) a counted gather has filled
+ * its count plane (mcpt_gather_rows_counted).  The resolved colour of a pixel is accum /
+ * (float)count per channel, mcpt_read_resolved's bits; mcpt_read_sample_counts and
+ * mcpt_read_resolved serve both cases (MCPT_ERR_NO_ADAPTIVE with neither).
+ *
+ * mcpt_denoise_resolved / mcpt_denoise_resolved_guided: mcpt_denoise / mcpt_denoise_guided with the
+ * resolved colour as the input image in place of accum / pass_count; the same preconditions
+ * (full-frame target in row order, current guides, 0..8 iterations, positive finite sigmas), the
+ * same filter kernels and the same result buffers (mcpt_read_denoised, mcpt_last_denoise_ms,
+ * mcpt_denoise_iteration_ms with -1 the resolve step, mcpt_last_denoise_path).  A context without
+ * per-pixel counts returns MCPT_ERR_NO_ADAPTIVE.  The guided form needs the error map of the
+ * current window (the last mcpt_adaptive_select's), else MCPT_ERR_NO_STATS; on a gathered frame
+ * (case b) it always returns MCPT_ERR_NO_STATS.  With no block retired the resolved forms give
+ * mcpt_denoise's bits.
+ *
+ * Out of scope, the only remaining gap: the multi-process gather (torch.distributed / RCCL,
+ * mcpt/dist.py) carries no counts. */
 typedef struct mcpt_adaptive_t {
   long long n_px, n_above;
   unsigned long long sum_q;
@@ -459,6 +494,8 @@ int mcpt_read_sample_counts(mcpt_ctx* ctx, int* counts);
 int mcpt_read_resolved(mcpt_ctx* ctx, float* rgb);
 int mcpt_adaptive_info(mcpt_ctx* ctx, int* on, long long* n_active, long long* n_blocks);
 int mcpt_last_adaptive_ms(mcpt_ctx* ctx, float* select_ms, float* render_ms);
+int mcpt_denoise_resolved(mcpt_ctx* ctx, int iterations, float sigma_color, float sigma_plane);
+int mcpt_denoise_resolved_guided(mcpt_ctx* ctx, int iterations, float k_color, float sigma_plane);
 
 /* DrawSampling's point cloud (DrawSampling/draw_sampling.cpp:144-150, tp/sampling_base.vert
  * seeding, tp/hsphere.vert random_ray): point k = random_ray(normalize(normal), roughness)
@@ -584,6 +621,52 @@ int mcpt_checkpoint_write(const char* path, const float* rgb, int W, int rows, i
  * (round 3, no identity) too. */
 int mcpt_checkpoint_read(const char* path, float* rgb_out, long long capacity, int* W, int* rows, int* pass_count,
                          int* next_pass, char* tag_out);
+
+/* Checkpoint / resume of an ADAPTIVE render: the accumulator together with the
+ * statistics window, the error map and the blocks' state, so that a long adaptive render can stop
+ * and continue.  The guarantee: after mcpt_adaptive_checkpoint_load the same sequence of
+ * mcpt_render_adaptive / mcpt_adaptive_select calls produces the same records, active lists, error
+ * maps, sample counts and sums, bit for bit, as the uninterrupted render.
+ * Layout, little endian, no padding: "MCPTCKA1"; int32 W, rows, pass_count, next_pass, tag bytes, H;
+ * uint64 row-list hash; int32 p0 (the pass count at mcpt_adaptive_begin), min_passes; int64 passes
+ * and int32 batches of the statistics window; int32 1 if the error map is valid; int32 n_blocks,
+ * blocks_x; the tag; per block the active flag (n_blocks int32), then the passes (n_blocks int32);
+ * per pixel the accumulator (rows x W x 3 f32), the statistics state {Yacc, S2, Ybase, 0} (x 4
+ * f32) and the error map {se, r} (x 2 f32).  Written as mcpt_checkpoint_write writes (temporary
+ * file unique to the writer, fsync, rename, directory fsync).  The two formats do not cross-load:
+ * mcpt_checkpoint_read / _load return MCPT_ERR_INVALID_ARG for an "MCPTCKA1" file and the adaptive
+ * reader and loader for an "MCPTCKP1/2" file. */
+typedef struct mcpt_adaptive_checkpoint_t {
+  int W, rows, pass_count, next_pass, H;
+  unsigned long long rows_hash;   /* H = rows_hash = 0: no target identity */
+  int p0, min_passes;
+  long long stats_passes;
+  int stats_batches, emap_valid;
+  int n_blocks, blocks_x;         /* ceil(W / 8) * ceil(rows / 8), ceil(W / 8) */
+} mcpt_adaptive_checkpoint_t;
+/* Needs the adaptive mode on (else MCPT_ERR_NO_ADAPTIVE).  Synchronizes the context's stream. */
+extern int mcpt_adaptive_checkpoint_save(mcpt_ctx* ctx, const char* path, int next_pass, const char* tag);
+/* Loads a file written by mcpt_adaptive_checkpoint_save for THIS target (W, local rows, H and row
+ * ids must match, and `tag` when it is not NULL; MCPT_ERR_INVALID_ARG otherwise, with
+ * mcpt_checkpoint_load's details): sets the accumulator and pass count, turns statistics and the
+ * adaptive mode on in the saved state (their buffers as mcpt_stats_begin / mcpt_adaptive_begin
+ * allocate them, the active list rebuilt from the flags) and returns the next call's first pass in
+ * *next_pass (may be NULL).  Synchronizes. */
+extern int mcpt_adaptive_checkpoint_load(mcpt_ctx* ctx, const char* path, const char* tag, int* next_pass);
+/* File-level access without a context, plain arrays: block_active and block_passes hold
+ * hdr->n_blocks ints, accum / stats4 / emap2 hold rows x W x 3 / 4 / 2 floats.  The header must be
+ * consistent (positive sizes, n_blocks and blocks_x of W x rows), else MCPT_ERR_INVALID_ARG. */
+extern int mcpt_adaptive_checkpoint_write(const char* path, const mcpt_adaptive_checkpoint_t* hdr, const char* tag,
+                                   const int* block_active, const int* block_passes, const float* accum,
+                                   const float* stats4, const float* emap2);
+/* Reads the header into *hdr (may be NULL) and the tag into tag_out (MCPT_CHECKPOINT_TAG_MAX bytes;
+ * may be NULL).  The five arrays are read when all are given (all NULL: header only): at most
+ * block_capacity blocks and pixel_capacity pixels.  MCPT_ERR_INVALID_ARG for a missing, foreign or
+ * truncated file (the file's length must be the one its header implies), an inconsistent header,
+ * or arrays larger than the capacities. */
+extern int mcpt_adaptive_checkpoint_read(const char* path, mcpt_adaptive_checkpoint_t* hdr, char* tag_out, int* block_active,
+                                  int* block_passes, long long block_capacity, float* accum, float* stats4,
+                                  float* emap2, long long pixel_capacity);
 
 #ifdef __cplusplus
 }

@@ -547,6 +547,41 @@ class Renderer {
     if (rendered) *rendered = done;
     return rec;
   }
+  // frames with per-pixel sample counts (adaptive mode on, or after gather_rows_counted; mcpt.h,
+  // DESIGN.md §3.9): denoise / denoise_guided over the resolved colour accum / (float)count
+  std::vector<float> denoise_resolved(int iterations = 5, float sigma_color = kDenoiseSigmaColor,
+                                      float sigma_plane = kDenoiseSigmaPlane) {
+    check(mcpt_denoise_resolved(c_, iterations, sigma_color, sigma_plane), "mcpt_denoise_resolved");
+    std::vector<float> img((size_t)rows_ * W_ * 3);
+    check(mcpt_read_denoised(c_, img.data()), "mcpt_read_denoised");
+    return img;
+  }
+  std::vector<float> denoise_resolved_guided(int iterations = 5, float k_color = kDenoiseKColor,
+                                             float sigma_plane = kDenoiseSigmaPlane) {
+    check(mcpt_denoise_resolved_guided(c_, iterations, k_color, sigma_plane), "mcpt_denoise_resolved_guided");
+    std::vector<float> img((size_t)rows_ * W_ * 3);
+    check(mcpt_read_denoised(c_, img.data()), "mcpt_read_denoised");
+    return img;
+  }
+  // checkpoint / resume of an adaptive render (mcpt_adaptive_checkpoint_save / _load): the sums with
+  // the statistics window, the error map and the blocks' state; the load turns statistics and the
+  // adaptive mode on in the saved state and returns the next first pass
+  void save_adaptive_checkpoint(const std::string& path, int next_pass, const std::string& tag) const {
+    check(mcpt_adaptive_checkpoint_save(c_, path.c_str(), next_pass, tag.c_str()), "mcpt_adaptive_checkpoint_save");
+  }
+  int load_adaptive_checkpoint(const std::string& path, const std::string& tag) {
+    int next = 0;
+    check(mcpt_adaptive_checkpoint_load(c_, path.c_str(), tag.c_str(), &next), "mcpt_adaptive_checkpoint_load");
+    return next;
+  }
+  // gather_rows for shards with per-pixel counts or different pass counts (mcpt_gather_rows_counted):
+  // every frame row from exactly one shard; read_sample_counts / read_resolved / denoise_resolved
+  // then serve this renderer
+  void gather_rows_counted(const std::vector<const Renderer*>& shards) {
+    std::vector<mcpt_ctx*> h;
+    for (const Renderer* r : shards) h.push_back(r->c_);
+    check(mcpt_gather_rows_counted(c_, h.data(), (int)h.size()), "mcpt_gather_rows_counted");
+  }
   void set_traversal(int mode) { check(mcpt_set_traversal(c_, mode), "mcpt_set_traversal"); }
   // render lanes (consecutive launches overlapping each other's tails; same bits): on by default
   void set_render_lanes(bool on) { check(mcpt_set_render_lanes(c_, on ? 1 : 0), "mcpt_set_render_lanes"); }

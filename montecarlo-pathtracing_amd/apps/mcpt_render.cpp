@@ -19,6 +19,8 @@
 //   mcpt_render --scene 8 --width 1920 --height 1080 --spp 512 --bounces 12 --devices 0,1,2,3,4,5,6,7
 //   mcpt_render --scene 6 --spp 16 --denoise --aov s6 --out s6_denoised.png   (a-trous filter + guide AOVs)
 //   mcpt_render --scene 6 --spp 4096 --chunk 32 --target-error 0.02 --out s6.png   (stop at 2 % mean relative error)
+//   mcpt_render --scene 6 --spp 4096 --chunk 32 --adaptive --target-error 0.05 --denoise 3 --checkpoint s6.ckpt
+//   mcpt_render --scene 6 --spp 4096 --chunk 32 --adaptive --target-error 0.05 --devices 0,1,2,3 --aov s6
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -74,7 +76,9 @@ void usage() {
                "                                         relative error <= E, at most --spp passes)\n"
                "                   [--adaptive]   (with --target-error: E is the per-pixel threshold on r; 8x8 blocks\n"
                "                                   whose largest r <= E stop receiving passes; --aov also writes\n"
-               "                                   PREFIX_samples.pfm; the image is accum / each pixel's own count)\n"
+               "                                   PREFIX_samples.pfm; the image is accum / each pixel's own count;\n"
+               "                                   with --devices every shard selects on its own rows; --denoise,\n"
+               "                                   --checkpoint and --resume use the per-pixel-count forms)\n"
                "                   [--denoise-guided [N]]   (one device: the a-trous filter with the colour width\n"
                "                                             from each pixel's standard error; >= 2 chunks)\n");
 }
@@ -140,13 +144,25 @@ bool parse(int argc, char** argv, Args& a) {
     }
   }
   if (!a.devices.empty() && (!a.checkpoint.empty() || !a.resume.empty())) return false;   // one device only
-  if (!a.devices.empty() && (a.target_error > 0.0 || a.denoise_guided >= 0)) return false;  // (statistics: one device)
+  // (the frame's statistics: one device; adaptive shards keep their own, whose error maps do not travel)
+  if (!a.devices.empty() && ((a.target_error > 0.0 && !a.adaptive) || a.denoise_guided >= 0)) return false;
   if (a.denoise >= 0 && a.denoise_guided >= 0) return false;                                // one filter
-  // adaptive sampling: one device, a threshold, no filter (per-pixel counts), no checkpoint
-  if (a.adaptive && (!(a.target_error > 0.0) || !a.devices.empty() || a.denoise >= 0 || a.denoise_guided >= 0 ||
-                     !a.checkpoint.empty() || !a.resume.empty()))
-    return false;
+  if (a.adaptive && !(a.target_error > 0.0)) return false;   // adaptive sampling needs its threshold
   return a.width > 0 && a.height > 0 && a.spp >= 0 && a.chunk > 0 && a.subsampling >= 0 && a.subsampling < 16;
+}
+
+// the adaptive part of the JSON line from a select's record (a frame's, or the shards' combined)
+std::string adaptive_json(double target_error, bool converged, const mcpt_adaptive_t& rec) {
+  char buf[400];
+  std::snprintf(buf, sizeof(buf),
+                ", \"adaptive\": true, \"target_error\": %g, \"converged\": %s, \"window_passes\": %lld, "
+                "\"batches\": %d, \"mean_r\": %.6f, \"max_r\": %.6f, \"n_above\": %lld, \"n_px\": %lld, "
+                "\"sum_q\": %llu, \"samples\": %lld, \"n_active_blocks\": %lld, \"n_blocks\": %lld, "
+                "\"mean_spp\": %.4f",
+                target_error, converged ? "true" : "false", rec.passes, rec.batches, rec.mean_r, rec.max_r, rec.n_above,
+                rec.n_px, rec.sum_q, rec.samples, rec.n_active_blocks, rec.n_blocks,
+                rec.n_px > 0 ? (double)rec.samples / (double)rec.n_px : 0.0);
+  return buf;
 }
 
 // --denoise / --aov on the context that holds the whole frame: the guide buffers, the AOV files,
@@ -188,8 +204,10 @@ void post_process(const Args& a, mcpt::Renderer& r, const mcpt::Camera& cam, int
       mcpt::write_pfm(a.aov + "_error.pfm", err, W, H);
     }
   }
-  if (a.denoise >= 0) img = r.denoise(a.denoise);
-  if (a.denoise_guided >= 0) img = r.denoise_guided(a.denoise_guided);   // (fewer than two chunks: an error)
+  // (adaptive: every pixel divided by its own count)
+  if (a.denoise >= 0) img = a.adaptive ? r.denoise_resolved(a.denoise) : r.denoise(a.denoise);
+  if (a.denoise_guided >= 0)   // (fewer than two chunks: an error)
+    img = a.adaptive ? r.denoise_resolved_guided(a.denoise_guided) : r.denoise_guided(a.denoise_guided);
   float gm = 0.0f, fm = 0.0f;
   r.last_denoise_ms(gm, fm);
   guides_ms = gm; filter_ms = fm;
@@ -225,25 +243,34 @@ int main(int argc, char** argv) {
       // checkpoint / resume: --spp counts the whole render's passes (first_pass .. first_pass +
       // spp - 1); a resumed run continues at the checkpoint's next pass with its sums loaded,
       // and the tag makes a resume with other render parameters fail
-      char tag[256];
+      char tag[320];
       // (the chunk too: a call that splits a 32-pass accumulation chunk adds its own partial sum,
       // so the resumed bits equal the uninterrupted run's only with the same call boundaries)
-      std::snprintf(tag, sizeof(tag),
-                    "scene=%d W=%d H=%d bounces=%d ior=%a light=%a date=%a variant=%d first=%d chunk=%d", a.scene, W,
-                    H, a.bounces, a.ior, a.light, a.date, a.variant, a.first_pass, a.chunk);
+      int len = std::snprintf(tag, sizeof(tag),
+                              "scene=%d W=%d H=%d bounces=%d ior=%a light=%a date=%a variant=%d first=%d chunk=%d", a.scene,
+                              W, H, a.bounces, a.ior, a.light, a.date, a.variant, a.first_pass, a.chunk);
+      // (adaptive: the threshold decides which blocks the later chunks reach)
+      if (a.adaptive) std::snprintf(tag + len, sizeof(tag) - (size_t)len, " adaptive=%a", a.target_error);
+      const bool resumed_adaptive = a.adaptive && !a.resume.empty();
       int next = a.first_pass;
-      if (!a.resume.empty()) next = r.load_checkpoint(a.resume, tag);
+      if (resumed_adaptive) next = r.load_adaptive_checkpoint(a.resume, tag);   // (statistics and the mode on, as saved)
+      else if (!a.resume.empty()) next = r.load_checkpoint(a.resume, tag);
       const auto t0 = std::chrono::steady_clock::now();
-      // noise statistics: a window from here (a resumed render begins a new one), a batch per chunk;
-      // --target-error asks every 4 chunks and after the last
-      if (stats) r.stats_begin();
+      // noise statistics: a window from here (a resumed plain render begins a new one), a batch per
+      // chunk; --target-error asks every 4 chunks and after the last
+      if (stats && !resumed_adaptive) r.stats_begin();
       mcpt_convergence_t rec{};
       bool have_rec = false, converged = false;
       int calls = 0;
       mcpt_adaptive_t arec{};
       bool have_arec = false;
-      if (a.adaptive) r.adaptive_begin(0);
-      for (int done = 0; a.adaptive && done < a.spp && !converged; done += a.chunk) {
+      if (a.adaptive && !resumed_adaptive) r.adaptive_begin(0);
+      if (resumed_adaptive) {   // the chunks so far were one batch each; a select has run from the second on
+        calls = r.stats_info().batches;
+        converged = calls >= 2 && r.adaptive_info().n_active == 0;
+        rendered = next - a.first_pass;
+      }
+      for (int done = next - a.first_pass; a.adaptive && done < a.spp && !converged; done += a.chunk) {
         // adaptive sampling: the active blocks only, a select after every chunk from the second on
         const int n = std::min(a.chunk, a.spp - done);
         r.render_adaptive(cam, a.first_pass + done, n, a.date, a.bounces, a.ior, a.variant);
@@ -256,6 +283,8 @@ int main(int argc, char** argv) {
           have_arec = true;
           converged = arec.n_active_blocks == 0;
         }
+        // (after the chunk's select: the resumed run continues with the next chunk's render)
+        if (!a.checkpoint.empty()) r.save_adaptive_checkpoint(a.checkpoint, a.first_pass + done + n, tag);
       }
       for (int done = next - a.first_pass; !a.adaptive && done < a.spp && !converged; done += a.chunk) {
         const int n = std::min(a.chunk, a.spp - done);
@@ -274,21 +303,18 @@ int main(int argc, char** argv) {
       if (post) post_process(a, r, cam, W, H, img, guides_ms, filter_ms);
       if (a.adaptive) {
         char buf[400];
-        if (have_arec)
+        if (have_arec) {
+          shard_json += adaptive_json(a.target_error, converged, arec);
+        } else {   // no select in this run (fewer than two chunks, or a resume with nothing left to do)
+          long long samples = 0;
+          for (int c : r.read_sample_counts()) samples += c;
           std::snprintf(buf, sizeof(buf),
-                        ", \"adaptive\": true, \"target_error\": %g, \"converged\": %s, \"window_passes\": %lld, "
-                        "\"batches\": %d, \"mean_r\": %.6f, \"max_r\": %.6f, \"n_above\": %lld, \"n_px\": %lld, "
-                        "\"sum_q\": %llu, \"samples\": %lld, \"n_active_blocks\": %lld, \"n_blocks\": %lld, "
-                        "\"mean_spp\": %.4f",
-                        a.target_error, converged ? "true" : "false", arec.passes, arec.batches, arec.mean_r, arec.max_r,
-                        arec.n_above, arec.n_px, arec.sum_q, arec.samples, arec.n_active_blocks, arec.n_blocks,
-                        arec.n_px > 0 ? (double)arec.samples / (double)arec.n_px : 0.0);
-        else   // fewer than two chunks: no select, every block active
-          std::snprintf(buf, sizeof(buf),
-                        ", \"adaptive\": true, \"target_error\": %g, \"converged\": false, \"mean_r\": null, "
+                        ", \"adaptive\": true, \"target_error\": %g, \"converged\": %s, \"mean_r\": null, "
                         "\"samples\": %lld, \"n_active_blocks\": %lld, \"mean_spp\": %.4f",
-                        a.target_error, (long long)W * H * rendered, r.adaptive_info().n_active, (double)rendered);
-        shard_json += buf;
+                        a.target_error, converged ? "true" : "false", samples, r.adaptive_info().n_active,
+                        (double)samples / ((double)W * H));
+          shard_json += buf;
+        }
       } else if (a.target_error > 0.0) {
         char buf[320];
         if (have_rec)
@@ -318,15 +344,37 @@ int main(int argc, char** argv) {
       if (post) frame.upload(scene);   // the guides are traced on the frame context
       std::vector<double> shard_ms((size_t)N, 0.0);
       std::vector<std::string> errors((size_t)N);
+      // adaptive: every shard's own statistics window and select / render loop on its rows
+      std::vector<mcpt_adaptive_t> shard_rec((size_t)N);
+      std::vector<int> shard_selects((size_t)N, 0), shard_passes((size_t)N, 0);
       const auto t0 = std::chrono::steady_clock::now();
       std::vector<std::thread> workers;
       for (int k = 0; k < N; ++k)
         workers.emplace_back([&, k]() {
           try {
-            for (int done = 0; done < a.spp; done += a.chunk) {
+            mcpt::Renderer& s = *shards[(size_t)k];
+            if (a.adaptive) {
+              s.stats_begin();
+              s.adaptive_begin(0);
+            }
+            bool shard_done = false;   // its list is empty
+            for (int done = 0, calls = 0; a.adaptive && done < a.spp && !shard_done; done += a.chunk) {
               const int n = std::min(a.chunk, a.spp - done);
-              shards[(size_t)k]->render(cam, a.first_pass + done, n, a.date, a.bounces, a.ior, a.variant);
-              shard_ms[(size_t)k] += shards[(size_t)k]->last_render_ms();   // (synchronizes this shard)
+              s.render_adaptive(cam, a.first_pass + done, n, a.date, a.bounces, a.ior, a.variant);
+              float sel = 0.0f, ren = 0.0f;
+              s.last_adaptive_ms(sel, ren);   // (synchronizes this shard)
+              shard_ms[(size_t)k] += ren;
+              shard_passes[(size_t)k] = done + n;
+              if (++calls >= 2) {
+                shard_rec[(size_t)k] = s.adaptive_select((float)a.target_error);
+                ++shard_selects[(size_t)k];
+                shard_done = shard_rec[(size_t)k].n_active_blocks == 0;
+              }
+            }
+            for (int done = 0; !a.adaptive && done < a.spp; done += a.chunk) {
+              const int n = std::min(a.chunk, a.spp - done);
+              s.render(cam, a.first_pass + done, n, a.date, a.bounces, a.ior, a.variant);
+              shard_ms[(size_t)k] += s.last_render_ms();   // (synchronizes this shard)
             }
           } catch (const std::exception& e) {
             errors[(size_t)k] = e.what();
@@ -338,8 +386,13 @@ int main(int argc, char** argv) {
       const auto t1 = std::chrono::steady_clock::now();
       std::vector<const mcpt::Renderer*> views;
       for (const auto& r : shards) views.push_back(r.get());
-      frame.gather_rows(views);
-      img = frame.read_image();
+      if (a.adaptive) {   // the shards' counts travel with their rows
+        frame.gather_rows_counted(views);
+        img = frame.read_resolved();
+      } else {
+        frame.gather_rows(views);
+        img = frame.read_image();
+      }
       if (post) post_process(a, frame, cam, W, H, img, guides_ms, filter_ms);
       const auto t2 = std::chrono::steady_clock::now();
       wall_ms = std::chrono::duration<double, std::milli>(t2 - t0).count();
@@ -356,6 +409,31 @@ int main(int argc, char** argv) {
       char buf[64];
       std::snprintf(buf, sizeof(buf), "], \"gather_ms\": %.3f", gather_ms);
       shard_json += buf;
+      if (a.adaptive) {
+        // the shards' records combined: the sums add, max_r is the largest; the window is the longest
+        mcpt_adaptive_t all{};
+        bool every = true;
+        rendered = 0;
+        for (int k = 0; k < N; ++k) {
+          const mcpt_adaptive_t& q = shard_rec[(size_t)k];
+          every = every && shard_selects[(size_t)k] > 0;
+          rendered = std::max(rendered, shard_passes[(size_t)k]);
+          all.n_px += q.n_px; all.n_above += q.n_above; all.sum_q += q.sum_q; all.samples += q.samples;
+          all.n_active_blocks += q.n_active_blocks; all.n_blocks += q.n_blocks;
+          all.max_r = std::max(all.max_r, q.max_r);
+          all.passes = std::max(all.passes, q.passes);
+          all.batches = std::max(all.batches, q.batches);
+        }
+        all.mean_r = all.n_px > 0 ? (double)all.sum_q / 65536.0 / (double)all.n_px : 0.0;
+        if (every) {
+          shard_json += adaptive_json(a.target_error, all.n_active_blocks == 0, all);
+        } else {   // fewer than two chunks: no select
+          char nb[160];
+          std::snprintf(nb, sizeof(nb), ", \"adaptive\": true, \"target_error\": %g, \"converged\": false, \"mean_r\": null",
+                        a.target_error);
+          shard_json += nb;
+        }
+      }
     }
     if (!a.pfm.empty()) mcpt::write_pfm(a.pfm, img, W, H);
     if (!a.png.empty()) mcpt::write_png(a.png, img, W, H);

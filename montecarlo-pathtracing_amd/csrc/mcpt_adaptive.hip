@@ -169,6 +169,29 @@ __global__ __launch_bounds__(256) void resolve_kernel(AdaptiveTarget t, const fl
   out[3 * i] = accum[3 * i] / nb; out[3 * i + 1] = accum[3 * i + 1] / nb; out[3 * i + 2] = accum[3 * i + 2] / nb;
 }
 
+// The filter's first input from a frame with per-pixel counts (average4_kernel's twin, DESIGN.md
+// §3.9): accum / (float)count per channel as float4 (rgb, 0), one lane per pixel, one 16-byte store.
+// The count comes from the count plane of a counted gather (plane non-null: 4 B per pixel) or from
+// the block arrays (4 B per block, 64 lanes of a row run share at most ceil(64 / 8) + 1 words).
+__global__ __launch_bounds__(256) void resolve4_kernel(AdaptiveTarget t, const int* __restrict__ plane,
+                                                       const float* __restrict__ accum, float4* __restrict__ out,
+                                                       long long n_px) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_px) return;
+  const float nb = (float)(plane ? plane[i] : pixel_count(t, i));
+  out[i] = make_float4(accum[3 * i] / nb, accum[3 * i + 1] / nb, accum[3 * i + 2] / nb, 0.0f);
+}
+
+// mcpt_read_resolved of a gathered frame: resolve_kernel with the count plane's counts
+__global__ __launch_bounds__(256) void resolve_plane_kernel(const int* __restrict__ plane,
+                                                            const float* __restrict__ accum, float* __restrict__ out,
+                                                            long long n_px) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_px) return;
+  const float nb = (float)plane[i];
+  out[3 * i] = accum[3 * i] / nb; out[3 * i + 1] = accum[3 * i + 1] / nb; out[3 * i + 2] = accum[3 * i + 2] / nb;
+}
+
 __global__ __launch_bounds__(256) void combine_list_kernel(float* __restrict__ accum, const float* __restrict__ partial,
                                                            long long n_px, int n_seg, int W, int n_local_rows,
                                                            int blocks_x, int n_blocks, const int* __restrict__ list,
@@ -236,6 +259,21 @@ hipError_t mcpt_launch_adaptive_resolve(const mcpt::AdaptiveTarget& t, const flo
   const long long n = (long long)t.n_local_rows * t.W;
   if (n <= 0) return hipSuccess;
   hipLaunchKernelGGL(mcpt::resolve_kernel, dim3(grid256(n)), dim3(256), 0, stream, t, accum, out, n);
+  return hipGetLastError();
+}
+
+hipError_t mcpt_launch_resolve4(const mcpt::AdaptiveTarget& t, const int* plane, const float* accum, float4* out,
+                                hipStream_t stream) {
+  const long long n = (long long)t.n_local_rows * t.W;
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(mcpt::resolve4_kernel, dim3(grid256(n)), dim3(256), 0, stream, t, plane, accum, out, n);
+  return hipGetLastError();
+}
+
+hipError_t mcpt_launch_resolve_plane(const int* plane, const float* accum, float* out, long long n_px,
+                                     hipStream_t stream) {
+  if (n_px <= 0) return hipSuccess;
+  hipLaunchKernelGGL(mcpt::resolve_plane_kernel, dim3(grid256(n_px)), dim3(256), 0, stream, plane, accum, out, n_px);
   return hipGetLastError();
 }
 

@@ -240,6 +240,7 @@ int mcpt_destroy(mcpt_ctx* c) {
   for (hipEvent_t e : c->stats_ev) if (e) (void)hipEventDestroy(e);
   free_adaptive(c);
   for (hipEvent_t e : c->ad_ev) if (e) (void)hipEventDestroy(e);
+  free_count_plane(c);
   (void)hipFree(c->d_accum);
   (void)hipFree(c->d_rows);
   (void)hipFree(c->d_events);
@@ -512,6 +513,7 @@ static int set_target_rows(mcpt_ctx* c, int W, int H, const int* rows, int n_row
   free_denoise(c);   // (sized by the target; allocated again by the next guides / denoise call)
   free_stats(c);     // (statistics off: a new target begins again)
   free_adaptive(c);  // (adaptive mode off: its blocks are the old target's)
+  free_count_plane(c);   // (a gathered frame's counts are the old target's)
   size_t bytes = (size_t)n_rows * W * 3 * sizeof(float);
   if (bytes != c->accum_bytes) {
     (void)hipFree(c->d_accum);
@@ -600,6 +602,7 @@ int mcpt_clear_accum(mcpt_ctx* c) {
   HIP_OR_RETURN(hipSetDevice(c->device));
   if (c->accum_bytes) HIP_OR_RETURN(hipMemsetAsync(c->d_accum, 0, c->accum_bytes, c->stream));
   c->pass_count = 0;
+  c->plane_valid = false;
   return MCPT_OK;
 }
 
@@ -975,6 +978,7 @@ static int sort_order(mcpt_ctx* c, mcpt_ctx::Lane& L, hipStream_t ws, const plan
 static int launch(mcpt_ctx* c, const float* invPV, const float* invV, int first_pass, int n_passes, float date,
                   int bounces, float refract_ind, int variant, bool count, unsigned long long* events) {
   OK_OR_RETURN(check_renderable(c, invPV && invV && n_passes >= 0 && variant >= 0 && variant <= 2, "mcpt_render"));
+  c->plane_valid = false;   // (a gathered frame's counts do not describe what is rendered into it)
   HIP_OR_RETURN(hipSetDevice(c->device));
   mcpt::RenderParams p;
   scene_params(c, invPV, invV, p);
@@ -1182,6 +1186,7 @@ int mcpt_write_accum(mcpt_ctx* c, const float* rgb, int pass_count) {
     HIP_OR_RETURN(hipMemcpyAsync(c->d_accum, rgb, c->accum_bytes, hipMemcpyHostToDevice, c->stream));
   HIP_OR_RETURN(hipStreamSynchronize(c->stream));
   c->pass_count = pass_count;
+  c->plane_valid = false;
   return MCPT_OK;
 }
 
@@ -1193,17 +1198,6 @@ int checkpoint_read_ex(const char* path, float* rgb_out, long long capacity, int
                        int* next_pass, char* tag_out, int* H, unsigned long long* rows_hash);
 }  // namespace host
 }  // namespace mcpt
-
-// identity of a context's target for its checkpoints: FNV-1a (64 bit) over its image row ids
-static unsigned long long rows_hash(const mcpt_ctx* c) {
-  unsigned long long h = 1469598103934665603ULL;
-  for (int y : c->rows)
-    for (int b = 0; b < 4; ++b) {
-      h ^= (unsigned long long)(((uint32_t)y >> (8 * b)) & 0xFFu);
-      h *= 1099511628211ULL;
-    }
-  return h ? h : 1;   // 0 means "no identity" in the file
-}
 
 int mcpt_checkpoint_save(mcpt_ctx* c, const char* path, int next_pass, const char* tag) {
   if (!c || !path) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
@@ -1260,7 +1254,10 @@ int mcpt_copy_accum_device(mcpt_ctx* c, void* dst, size_t bytes) {
   return MCPT_OK;
 }
 
-int mcpt_gather_rows(mcpt_ctx* frame, mcpt_ctx* const* shards, int n_shards) {
+// mcpt_gather_rows (counted false: equal pass counts, no counts carried) and
+// mcpt_gather_rows_counted (counted true: each shard's per-pixel counts travel with its rows into
+// frame's count plane; every frame row from exactly one shard)
+static int gather_rows(mcpt_ctx* frame, mcpt_ctx* const* shards, int n_shards, bool counted) {
   if (!frame || n_shards < 0 || (n_shards > 0 && !shards)) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_gather_rows: bad arguments");
   if (!frame->has_target) return set_err(MCPT_ERR_NO_TARGET, "mcpt_gather_rows: frame has no target");
   if (frame->n_local_rows != frame->H) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_gather_rows: frame target is a shard");
@@ -1269,9 +1266,22 @@ int mcpt_gather_rows(mcpt_ctx* frame, mcpt_ctx* const* shards, int n_shards) {
     if (!s || s == frame) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_gather_rows: bad shard context");
     if (!s->has_target) return set_err(MCPT_ERR_NO_TARGET, "mcpt_gather_rows: shard has no target");
     if (s->W != frame->W || s->H != frame->H) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_gather_rows: shard size differs");
-    if (s->pass_count != shards[0]->pass_count)
+    if (!counted && s->pass_count != shards[0]->pass_count)
       return set_err(MCPT_ERR_INVALID_ARG, "mcpt_gather_rows: shards hold different pass counts");
   }
+  if (counted) {
+    // a condition, so that no pixel is left with count 0
+    bool in_order = true;
+    for (int i = 0; in_order && i < frame->n_local_rows; ++i) in_order = frame->rows[(size_t)i] == i;
+    if (!in_order) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_gather_rows_counted: frame target is not in row order");
+    std::vector<int> held((size_t)frame->H, 0);
+    for (int k = 0; k < n_shards; ++k)
+      for (int y : shards[k]->rows) ++held[(size_t)y];
+    for (int y = 0; y < frame->H; ++y)
+      if (held[(size_t)y] != 1)
+        return set_err(MCPT_ERR_INVALID_ARG, "mcpt_gather_rows_counted: every frame row must be held by exactly one shard");
+  }
+  frame->plane_valid = false;   // (the accumulator is replaced: a plain gather carries no counts)
   // the calling thread's current device is restored on every return path
   struct DeviceGuard {
     int prev = -1;
@@ -1285,6 +1295,11 @@ int mcpt_gather_rows(mcpt_ctx* frame, mcpt_ctx* const* shards, int n_shards) {
     ~EventGuard() { if (e) (void)hipEventDestroy(e); }
   };
   const size_t row_bytes = (size_t)frame->W * 3 * sizeof(float);
+  const size_t row_counts = (size_t)frame->W * sizeof(int);
+  if (counted && !frame->d_count_plane) {
+    HIP_OR_RETURN(hipSetDevice(frame->device));
+    HIP_OR_RETURN(hipMalloc(&frame->d_count_plane, (size_t)frame->H * row_counts));
+  }
   for (int k = 0; k < n_shards; ++k) {
     mcpt_ctx* s = shards[k];
     if (s->device != frame->device) {
@@ -1297,9 +1312,21 @@ int mcpt_gather_rows(mcpt_ctx* frame, mcpt_ctx* const* shards, int n_shards) {
         (void)hipGetLastError();
       }
     }
+    HIP_OR_RETURN(hipSetDevice(s->device));
+    if (counted && s->n_local_rows > 0) {
+      // the shard's own counts on its stream (which waited for the previous gather's copies of
+      // this buffer): the blocks' counts with the adaptive mode on, else its pass count
+      const size_t n_px = (size_t)s->n_local_rows * s->W;
+      if (!s->d_gather_counts) HIP_OR_RETURN(hipMalloc(&s->d_gather_counts, n_px * sizeof(int)));
+      if (s->plane_valid)
+        HIP_OR_RETURN(hipMemcpyAsync(s->d_gather_counts, s->d_count_plane, n_px * sizeof(int), hipMemcpyDeviceToDevice, s->stream));
+      else if (s->ad_on)
+        HIP_OR_RETURN(mcpt_launch_adaptive_counts(adaptive_target(s), s->d_gather_counts, s->stream));
+      else
+        HIP_OR_RETURN(hipMemsetD32Async((hipDeviceptr_t)s->d_gather_counts, s->pass_count, n_px, s->stream));
+    }
     // (1) the frame's stream waits for the shard's queued work (its renders and combines)
     EventGuard done;
-    HIP_OR_RETURN(hipSetDevice(s->device));
     HIP_OR_RETURN(hipEventCreateWithFlags(&done.e, hipEventDisableTiming));
     HIP_OR_RETURN(hipEventRecord(done.e, s->stream));
     HIP_OR_RETURN(hipSetDevice(frame->device));
@@ -1311,6 +1338,10 @@ int mcpt_gather_rows(mcpt_ctx* frame, mcpt_ctx* const* shards, int n_shards) {
       e = hipMemcpyPeerAsync((char*)frame->d_accum + (size_t)s->rows[(size_t)i] * row_bytes, frame->device,
                              (const char*)s->d_accum + (size_t)i * row_bytes, s->device, (size_t)(j - i) * row_bytes,
                              frame->stream);
+      if (counted && e == hipSuccess)
+        e = hipMemcpyPeerAsync((char*)frame->d_count_plane + (size_t)s->rows[(size_t)i] * row_counts, frame->device,
+                               (const char*)s->d_gather_counts + (size_t)i * row_counts, s->device,
+                               (size_t)(j - i) * row_counts, frame->stream);
       i = j;
     }
     if (e != hipSuccess) return set_err(MCPT_ERR_HIP, "mcpt_gather_rows: peer copy", e);
@@ -1322,8 +1353,23 @@ int mcpt_gather_rows(mcpt_ctx* frame, mcpt_ctx* const* shards, int n_shards) {
     HIP_OR_RETURN(hipSetDevice(s->device));
     HIP_OR_RETURN(hipStreamWaitEvent(s->stream, copied.e, 0));
   }
-  if (n_shards > 0) frame->pass_count = shards[0]->pass_count;
+  if (!counted) {
+    if (n_shards > 0) frame->pass_count = shards[0]->pass_count;
+    return MCPT_OK;
+  }
+  int most = 0;
+  for (int k = 0; k < n_shards; ++k) most = std::max(most, shards[k]->pass_count);
+  frame->pass_count = most;
+  frame->plane_valid = true;
   return MCPT_OK;
+}
+
+int mcpt_gather_rows(mcpt_ctx* frame, mcpt_ctx* const* shards, int n_shards) {
+  return gather_rows(frame, shards, n_shards, false);
+}
+
+int mcpt_gather_rows_counted(mcpt_ctx* frame, mcpt_ctx* const* shards, int n_shards) {
+  return gather_rows(frame, shards, n_shards, true);
 }
 
 

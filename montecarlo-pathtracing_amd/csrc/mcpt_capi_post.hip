@@ -105,20 +105,26 @@ int mcpt_read_guides(mcpt_ctx* c, float* guide8, float* albedo4) {
 }
 
 // mcpt_denoise (guided false: sigma_color is the global width) and mcpt_denoise_guided (guided
-// true: sigma_color is k_color, the width per pixel k_color * 2^-s * se from the error map)
-static int denoise_run(mcpt_ctx* c, int iterations, float sigma_color, float sigma_plane, bool guided) {
+// true: sigma_color is k_color, the width per pixel k_color * 2^-s * se from the error map);
+// resolved: the mcpt_denoise_resolved* forms, whose input is accum / (float)count with every
+// pixel's own count in place of accum / pass_count
+static int denoise_run(mcpt_ctx* c, int iterations, float sigma_color, float sigma_plane, bool guided,
+                       bool resolved = false) {
   if (!c || iterations < 0 || iterations > 8) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_denoise: iterations not in 0..8");
   if (!(sigma_color > 0.0f) || !(sigma_plane > 0.0f) || !std::isfinite(sigma_color) || !std::isfinite(sigma_plane))
     return set_err(MCPT_ERR_INVALID_ARG, "mcpt_denoise: sigmas must be positive and finite");
   if (!c->has_target) return set_err(MCPT_ERR_NO_TARGET, "no render target");
+  if (resolved && !has_pixel_counts(c))
+    return set_err(MCPT_ERR_NO_ADAPTIVE, "mcpt_denoise_resolved: no per-pixel sample counts (adaptive mode off, no counted gather)");
   bool full = c->n_local_rows == c->H;
   for (int i = 0; full && i < c->n_local_rows; ++i) full = c->rows[(size_t)i] == i;
   if (!full) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_denoise: needs a full-frame target (gather the shards first)");
   if (c->pass_count <= 0) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_denoise: the accumulator holds no passes");
-  if (c->ad_on && c->ad_n_list < c->ad_n_blocks)
+  if (!resolved && c->ad_on && c->ad_n_list < c->ad_n_blocks)
     return set_err(MCPT_ERR_INVALID_ARG, "mcpt_denoise: adaptive mode has retired blocks (per-pixel sample counts)");
   if (!c->guides_valid) return set_err(MCPT_ERR_NO_GUIDES, "mcpt_denoise: no guides rendered for this target and scene");
-  if (guided && !(c->stats_on && c->emap_valid))
+  // (a gathered frame holds no error map of its pixels: the shards' maps do not travel)
+  if (guided && (!(c->stats_on && c->emap_valid) || (resolved && c->plane_valid)))
     return set_err(MCPT_ERR_NO_STATS, "mcpt_denoise_guided: no error map (mcpt_convergence) of the current statistics");
   HIP_OR_RETURN(hipSetDevice(c->device));
   HIP_OR_RETURN(ensure_denoise_buffers(c));
@@ -130,7 +136,11 @@ static int denoise_run(mcpt_ctx* c, int iterations, float sigma_color, float sig
   const long long n = (long long)c->H * c->W;
   // (the context's stream is ordered after all queued renders: their combines run on it)
   HIP_OR_RETURN(hipEventRecord(c->dn_ev[9], c->stream));
-  HIP_OR_RETURN(mcpt_launch_average4(c->d_accum, c->d_dn[0], n, c->pass_count, c->stream));
+  if (resolved)
+    HIP_OR_RETURN(mcpt_launch_resolve4(adaptive_target(c), c->plane_valid ? c->d_count_plane : nullptr, c->d_accum,
+                                       c->d_dn[0], c->stream));
+  else
+    HIP_OR_RETURN(mcpt_launch_average4(c->d_accum, c->d_dn[0], n, c->pass_count, c->stream));
   HIP_OR_RETURN(hipEventRecord(c->dn_ev[0], c->stream));
   for (int s = 0; s < iterations; ++s) {
     const int step = 1 << s;
@@ -158,11 +168,17 @@ int mcpt_denoise_guided(mcpt_ctx* c, int iterations, float k_color, float sigma_
   return denoise_run(c, iterations, k_color, sigma_plane, true);
 }
 
+int mcpt_denoise_resolved(mcpt_ctx* c, int iterations, float sigma_color, float sigma_plane) {
+  return denoise_run(c, iterations, sigma_color, sigma_plane, false, true);
+}
+
+int mcpt_denoise_resolved_guided(mcpt_ctx* c, int iterations, float k_color, float sigma_plane) {
+  return denoise_run(c, iterations, k_color, sigma_plane, true, true);
+}
+
 // ---- noise statistics and the convergence metric (mcpt_stats.hip)
-int mcpt_stats_begin(mcpt_ctx* c) {
-  if (!c) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
-  if (!c->has_target) return set_err(MCPT_ERR_NO_TARGET, "no render target");
-  HIP_OR_RETURN(hipSetDevice(c->device));
+// the statistics' buffers of the current target (mcpt_stats_begin, mcpt_adaptive_checkpoint_load)
+static int ensure_stats_buffers(mcpt_ctx* c) {
   const size_t n = (size_t)c->n_local_rows * c->W;
   if (!c->d_conv) {
     hipError_t e = hipMalloc(&c->d_conv, sizeof(unsigned long long) * mcpt::kStatsRecWords);
@@ -173,6 +189,15 @@ int mcpt_stats_begin(mcpt_ctx* c) {
       return set_err(MCPT_ERR_HIP, "mcpt_stats_begin: hipMalloc", e);
     }
   }
+  return MCPT_OK;
+}
+
+int mcpt_stats_begin(mcpt_ctx* c) {
+  if (!c) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  if (!c->has_target) return set_err(MCPT_ERR_NO_TARGET, "no render target");
+  HIP_OR_RETURN(hipSetDevice(c->device));
+  const size_t n = (size_t)c->n_local_rows * c->W;
+  OK_OR_RETURN(ensure_stats_buffers(c));
   HIP_OR_RETURN(mcpt_launch_stats_begin(c->d_accum, c->d_stats, (long long)n, c->stream));
   c->stats_on = true;
   c->stats_passes = 0;
@@ -249,11 +274,9 @@ int mcpt_last_stats_ms(mcpt_ctx* c, float* update_ms, float* error_ms) {
 }
 
 // ---- adaptive sampling of 8x8 blocks (mcpt_adaptive.hip)
-int mcpt_adaptive_begin(mcpt_ctx* c, int min_passes) {
-  if (!c || min_passes < 0) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_adaptive_begin: min_passes must not be negative");
-  if (!c->has_target) return set_err(MCPT_ERR_NO_TARGET, "no render target");
-  if (!c->stats_on) return set_err(MCPT_ERR_NO_STATS, "mcpt_adaptive_begin: statistics are off (mcpt_stats_begin)");
-  HIP_OR_RETURN(hipSetDevice(c->device));
+// the block arrays of the current target and its block grid (mcpt_adaptive_begin,
+// mcpt_adaptive_checkpoint_load)
+static int ensure_adaptive_buffers(mcpt_ctx* c) {
   const int bx = (c->W + 7) / 8, by = (c->n_local_rows + 7) / 8;
   if (!c->d_ad_flags) {
     const size_t n = (size_t)std::max(bx * by, 1);
@@ -267,6 +290,15 @@ int mcpt_adaptive_begin(mcpt_ctx* c, int min_passes) {
   }
   c->ad_blocks_x = bx;
   c->ad_n_blocks = bx * by;
+  return MCPT_OK;
+}
+
+int mcpt_adaptive_begin(mcpt_ctx* c, int min_passes) {
+  if (!c || min_passes < 0) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_adaptive_begin: min_passes must not be negative");
+  if (!c->has_target) return set_err(MCPT_ERR_NO_TARGET, "no render target");
+  if (!c->stats_on) return set_err(MCPT_ERR_NO_STATS, "mcpt_adaptive_begin: statistics are off (mcpt_stats_begin)");
+  HIP_OR_RETURN(hipSetDevice(c->device));
+  OK_OR_RETURN(ensure_adaptive_buffers(c));
   c->ad_p0 = c->pass_count;
   c->ad_min_passes = min_passes;
   HIP_OR_RETURN(mcpt_launch_adaptive_reset(adaptive_target(c), c->d_ad_list, c->d_ad_list + c->ad_n_blocks, c->stream));
@@ -346,6 +378,7 @@ int mcpt_render_adaptive(mcpt_ctx* c, const float* invPV, const float* invV, int
   if (c && args_ok && !c->ad_on)
     return set_err(MCPT_ERR_NO_ADAPTIVE, "mcpt_render_adaptive: adaptive mode is off (mcpt_adaptive_begin)");
   OK_OR_RETURN(check_renderable(c, args_ok, "mcpt_render_adaptive"));
+  c->plane_valid = false;   // (a gathered frame's counts do not describe what is rendered into it)
   if (c->ad_n_list == 0 || n_passes == 0) return MCPT_OK;   // every block retired: nothing to launch
   HIP_OR_RETURN(hipSetDevice(c->device));
   mcpt::RenderParams p;
@@ -396,9 +429,14 @@ int mcpt_render_adaptive(mcpt_ctx* c, const float* invPV, const float* invV, int
 
 int mcpt_read_sample_counts(mcpt_ctx* c, int* counts) {
   if (!c || !counts) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
-  if (!c->ad_on) return set_err(MCPT_ERR_NO_ADAPTIVE, "mcpt_read_sample_counts: adaptive mode is off (mcpt_adaptive_begin)");
+  if (!has_pixel_counts(c)) return set_err(MCPT_ERR_NO_ADAPTIVE, "mcpt_read_sample_counts: adaptive mode is off (mcpt_adaptive_begin)");
   HIP_OR_RETURN(hipSetDevice(c->device));
   const size_t n = (size_t)c->n_local_rows * c->W;
+  if (c->plane_valid) {   // a gathered frame: the count plane itself
+    if (n) HIP_OR_RETURN(hipMemcpyAsync(counts, c->d_count_plane, n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_OR_RETURN(hipStreamSynchronize(c->stream));
+    return MCPT_OK;
+  }
   if (n) {
     int* d = nullptr;
     HIP_OR_RETURN(hipMalloc(&d, n * sizeof(int)));
@@ -413,18 +451,106 @@ int mcpt_read_sample_counts(mcpt_ctx* c, int* counts) {
 
 int mcpt_read_resolved(mcpt_ctx* c, float* rgb) {
   if (!c || !rgb) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
-  if (!c->ad_on) return set_err(MCPT_ERR_NO_ADAPTIVE, "mcpt_read_resolved: adaptive mode is off (mcpt_adaptive_begin)");
+  if (!has_pixel_counts(c)) return set_err(MCPT_ERR_NO_ADAPTIVE, "mcpt_read_resolved: adaptive mode is off (mcpt_adaptive_begin)");
   HIP_OR_RETURN(hipSetDevice(c->device));
   const size_t n = (size_t)c->n_local_rows * c->W;
   if (n) {
     float* d = nullptr;
     HIP_OR_RETURN(hipMalloc(&d, n * 3 * sizeof(float)));
-    hipError_t e = mcpt_launch_adaptive_resolve(adaptive_target(c), c->d_accum, d, c->stream);
+    hipError_t e = c->plane_valid ? mcpt_launch_resolve_plane(c->d_count_plane, c->d_accum, d, (long long)n, c->stream)
+                                  : mcpt_launch_adaptive_resolve(adaptive_target(c), c->d_accum, d, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(rgb, d, n * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     (void)hipFree(d);
     if (e != hipSuccess) return set_err(MCPT_ERR_HIP, "mcpt_read_resolved", e);
   }
+  return MCPT_OK;
+}
+
+// ---- checkpoint / resume of an adaptive render (the file layer: mcpt_image.cpp)
+int mcpt_adaptive_checkpoint_save(mcpt_ctx* c, const char* path, int next_pass, const char* tag) {
+  if (!c || !path) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  if (!c->has_target) return mcpt_err_bare(MCPT_ERR_NO_TARGET);
+  if (!c->ad_on) return set_err(MCPT_ERR_NO_ADAPTIVE, "mcpt_adaptive_checkpoint_save: adaptive mode is off (mcpt_adaptive_begin)");
+  HIP_OR_RETURN(hipSetDevice(c->device));
+  const size_t n = (size_t)c->n_local_rows * c->W, nb = (size_t)c->ad_n_blocks;
+  std::vector<float> acc(n * 3), stats(n * 4), emap(n * 2);
+  std::vector<int> flags(nb), passes(nb);
+  if (n) {
+    HIP_OR_RETURN(hipMemcpyAsync(acc.data(), c->d_accum, n * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_OR_RETURN(hipMemcpyAsync(stats.data(), c->d_stats, n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    HIP_OR_RETURN(hipMemcpyAsync(emap.data(), c->d_emap, n * sizeof(float2), hipMemcpyDeviceToHost, c->stream));
+  }
+  if (nb) {
+    HIP_OR_RETURN(hipMemcpyAsync(flags.data(), c->d_ad_flags, nb * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_OR_RETURN(hipMemcpyAsync(passes.data(), c->d_ad_passes, nb * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  }
+  HIP_OR_RETURN(hipStreamSynchronize(c->stream));
+  mcpt_adaptive_checkpoint_t h;
+  std::memset(&h, 0, sizeof(h));
+  h.W = c->W; h.rows = c->n_local_rows; h.pass_count = c->pass_count; h.next_pass = next_pass; h.H = c->H;
+  h.rows_hash = rows_hash(c);
+  h.p0 = c->ad_p0; h.min_passes = c->ad_min_passes;
+  h.stats_passes = c->stats_passes; h.stats_batches = c->stats_batches; h.emap_valid = c->emap_valid ? 1 : 0;
+  h.n_blocks = c->ad_n_blocks; h.blocks_x = c->ad_blocks_x;
+  if (mcpt_adaptive_checkpoint_write(path, &h, tag, flags.data(), passes.data(), acc.data(), stats.data(), emap.data()) !=
+      MCPT_OK)
+    return set_err(MCPT_ERR_INVALID_ARG, "mcpt_adaptive_checkpoint_save: cannot write the file");
+  return MCPT_OK;
+}
+
+int mcpt_adaptive_checkpoint_load(mcpt_ctx* c, const char* path, const char* tag, int* next_pass) {
+  if (!c || !path) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  if (!c->has_target) return mcpt_err_bare(MCPT_ERR_NO_TARGET);
+  const size_t n = (size_t)c->n_local_rows * c->W;
+  const size_t nb = (size_t)((c->W + 7) / 8) * (size_t)((c->n_local_rows + 7) / 8);
+  std::vector<float> acc(n * 3), stats(n * 4), emap(n * 2);
+  std::vector<int> flags(nb), passes(nb);
+  std::vector<char> t(MCPT_CHECKPOINT_TAG_MAX);
+  mcpt_adaptive_checkpoint_t h;
+  if (mcpt_adaptive_checkpoint_read(path, &h, t.data(), flags.data(), passes.data(), (long long)nb, acc.data(),
+                                    stats.data(), emap.data(), (long long)n) != MCPT_OK)
+    return set_err(MCPT_ERR_INVALID_ARG, "mcpt_checkpoint_load: missing, foreign or truncated file, or not this target's size");
+  if (h.H == 0 || h.rows_hash == 0)
+    return set_err(MCPT_ERR_INVALID_ARG,
+                   "mcpt_checkpoint_load: the file carries no target identity (mcpt_checkpoint_write); "
+                   "read it with mcpt_checkpoint_read and load it with mcpt_write_accum");
+  if (h.W != c->W || h.rows != c->n_local_rows || h.H != c->H || h.rows_hash != rows_hash(c))
+    return set_err(MCPT_ERR_INVALID_ARG, "mcpt_checkpoint_load: the checkpoint belongs to another target or shard");
+  if (tag && std::strcmp(tag, t.data()) != 0)
+    return set_err(MCPT_ERR_INVALID_ARG, "mcpt_checkpoint_load: the render parameters differ (tag)");
+  OK_OR_RETURN(mcpt_write_accum(c, acc.data(), h.pass_count));   // (waits for the stream's queued work)
+  HIP_OR_RETURN(hipSetDevice(c->device));
+  // statistics and the adaptive mode on in the saved state: the buffers mcpt_stats_begin /
+  // mcpt_adaptive_begin allocate, the list from the flags by the select's scan
+  OK_OR_RETURN(ensure_stats_buffers(c));
+  OK_OR_RETURN(ensure_adaptive_buffers(c));
+  if (n) {
+    HIP_OR_RETURN(hipMemcpyAsync(c->d_stats, stats.data(), n * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+    HIP_OR_RETURN(hipMemcpyAsync(c->d_emap, emap.data(), n * sizeof(float2), hipMemcpyHostToDevice, c->stream));
+  }
+  if (nb) {
+    HIP_OR_RETURN(hipMemcpyAsync(c->d_ad_flags, flags.data(), nb * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIP_OR_RETURN(hipMemcpyAsync(c->d_ad_passes, passes.data(), nb * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  }
+  c->stats_on = true;
+  c->stats_passes = h.stats_passes;
+  c->stats_batches = h.stats_batches;
+  c->emap_valid = h.emap_valid != 0;
+  c->ad_p0 = h.p0;
+  c->ad_min_passes = h.min_passes;
+  int* d_count = c->d_ad_list + c->ad_n_blocks;
+  int n_list = 0;
+  HIP_OR_RETURN(mcpt_launch_adaptive_compact(adaptive_target(c), c->d_ad_list, d_count, c->stream));
+  HIP_OR_RETURN(hipMemcpyAsync(&n_list, d_count, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIP_OR_RETURN(hipStreamSynchronize(c->stream));   // (the host arrays are read until here)
+  if (n_list < 0 || n_list > c->ad_n_blocks) {
+    free_adaptive(c);
+    return set_err(MCPT_ERR_HIP, "mcpt_adaptive_checkpoint_load: the rebuilt active list is out of range");
+  }
+  c->ad_n_list = n_list;
+  c->ad_on = true;
+  if (next_pass) *next_pass = h.next_pass;
   return MCPT_OK;
 }
 

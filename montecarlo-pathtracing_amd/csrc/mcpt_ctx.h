@@ -157,6 +157,14 @@ struct mcpt_ctx {
   int ad_min_passes = 0;
   bool ad_select_timed = false, ad_render_timed = false;
   hipEvent_t ad_ev[4] = {};         // around the last select [0, 1] and the last adaptive render [2, 3]
+  // per-pixel sample counts of a gathered frame (mcpt_gather_rows_counted): the
+  // count plane, 4 B per local pixel, allocated by the first counted gather after a
+  // mcpt_set_target*, freed by the next one and mcpt_destroy; valid until the accumulator changes
+  int* d_count_plane = nullptr;
+  bool plane_valid = false;
+  // a shard's own counts for a counted gather (4 B per local pixel, same lifetime): the peer copies
+  // read them, and the shard's stream waits for those copies before its next work
+  int* d_gather_counts = nullptr;
   int next_lane = 0;                // the lane of the next sub-launch
   int prev_lane = -1;               // the lane of the previous sub-launch if it was a lane launch, else -1
 };
@@ -184,6 +192,27 @@ inline void free_adaptive(mcpt_ctx* c) {
   c->d_ad_flags = nullptr; c->d_ad_passes = nullptr; c->d_ad_list = nullptr;
   c->ad_on = false; c->ad_n_blocks = 0; c->ad_n_list = 0;
   c->ad_select_timed = false; c->ad_render_timed = false;
+}
+
+inline void free_count_plane(mcpt_ctx* c) {
+  (void)hipFree(c->d_count_plane); (void)hipFree(c->d_gather_counts);
+  c->d_count_plane = nullptr; c->d_gather_counts = nullptr;
+  c->plane_valid = false;
+}
+
+// a context has per-pixel sample counts: (b) a counted gather filled the count
+// plane, or (a) the adaptive mode is on; the plane describes the accumulator as long as it is valid
+inline bool has_pixel_counts(const mcpt_ctx* c) { return c->plane_valid || c->ad_on; }
+
+// identity of a context's target for its checkpoints: FNV-1a (64 bit) over its image row ids
+inline unsigned long long rows_hash(const mcpt_ctx* c) {
+  unsigned long long h = 1469598103934665603ULL;
+  for (int y : c->rows)
+    for (int b = 0; b < 4; ++b) {
+      h ^= (unsigned long long)(((unsigned)y >> (8 * b)) & 0xFFu);
+      h *= 1099511628211ULL;
+    }
+  return h ? h : 1;   // 0 means "no identity" in the file
 }
 
 inline hipError_t ensure_timing_events(hipEvent_t* ev, int n) {

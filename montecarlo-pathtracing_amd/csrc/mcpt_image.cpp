@@ -11,6 +11,8 @@
 //  * mcpt_checkpoint_write / _read: a progressive render's accumulator, pass count and next
 //    first pass in one file, so the pass loop (montecarlo.cpp:454-466) can stop and resume;
 //    mcpt_checkpoint_save / _load (mcpt_capi.hip) add the target's identity (H, row-list hash).
+//  * mcpt_adaptive_checkpoint_write / _read: the same for an adaptive render ("MCPTCKA1": the
+//    accumulator with the statistics window, the error map and the blocks' flags and passes).
 //  * mcpt_transfo_*, mcpt_mat4_mul: easycppogl Transfo (gl_eigen.cpp:29-105, degrees) and
 //    Eigen's float product, evaluated with the same arithmetic as the scene producer, so a
 //    C++ caller composing transforms gets the reference's matrices bit for bit.
@@ -25,6 +27,7 @@
 #include <vector>
 
 #include <fcntl.h>
+#include <sys/stat.h>
 #include <unistd.h>
 
 #include "../../include/mcpt.h"
@@ -144,28 +147,34 @@ int mcpt_write_png(const char* path, const float* rgb, int W, int H) {
 // "MCPTCKP1" files (round 3: 5 int32, no identity) are still read.
 static const char kCkptMagic[8] = {'M', 'C', 'P', 'T', 'C', 'K', 'P', '2'};
 static const char kCkptMagicV1[8] = {'M', 'C', 'P', 'T', 'C', 'K', 'P', '1'};
+// adaptive checkpoint file (mcpt.h): magic, the fixed header below, the tag, the blocks' active
+// flags and passes (n_blocks int32 each), then the accumulator, statistics state and error map
+static const char kCkptMagicAdaptive[8] = {'M', 'C', 'P', 'T', 'C', 'K', 'A', '1'};
 
-namespace mcpt {
-namespace host {
+namespace {
+
+#pragma pack(push, 1)
+struct AdaptiveFileHeader {   // little endian, no padding: 64 bytes after the magic
+  int32_t W, rows, pass_count, next_pass, tag_len, H;
+  uint64_t rows_hash;
+  int32_t p0, min_passes;
+  int64_t stats_passes;
+  int32_t stats_batches, emap_valid;
+  int32_t n_blocks, blocks_x;
+};
+#pragma pack(pop)
+static_assert(sizeof(AdaptiveFileHeader) == 64, "the adaptive checkpoint's header is packed");
+
 // The file is written to a temporary name unique to this process and thread, flushed to the
 // device (fsync) and renamed over `path`: a killed process or a host crash leaves either the
 // previous checkpoint or the new one, and two writers never share a temporary file.
-int checkpoint_write_ex(const char* path, const float* rgb, int W, int rows, int pass_count, int next_pass,
-                        const char* tag, int H, unsigned long long rows_hash) {
-  if (!path || !rgb || W <= 0 || rows <= 0 || pass_count < 0 || H < 0) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
-  const size_t tag_len = tag ? std::strlen(tag) : 0;
-  if (tag_len >= MCPT_CHECKPOINT_TAG_MAX) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+int write_replacing(const char* path, const std::function<bool(FILE*)>& body) {
   char suffix[64];
   std::snprintf(suffix, sizeof(suffix), ".tmp.%ld.%zx", (long)getpid(), std::hash<std::thread::id>()(std::this_thread::get_id()));
   const std::string tmp = std::string(path) + suffix;
   FILE* f = std::fopen(tmp.c_str(), "wb");
   if (!f) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
-  const int32_t hdr[6] = {W, rows, pass_count, next_pass, (int32_t)tag_len, H};
-  const uint64_t hash = rows_hash;
-  const size_t n = (size_t)W * rows * 3;
-  bool ok = std::fwrite(kCkptMagic, 1, 8, f) == 8 && std::fwrite(hdr, sizeof(int32_t), 6, f) == 6 &&
-            std::fwrite(&hash, sizeof(hash), 1, f) == 1 && std::fwrite(tag ? tag : "", 1, tag_len, f) == tag_len &&
-            std::fwrite(rgb, sizeof(float), n, f) == n;
+  bool ok = body(f);
   ok = ok && std::fflush(f) == 0 && fsync(fileno(f)) == 0;
   ok = (std::fclose(f) == 0) && ok;
   if (!ok || std::rename(tmp.c_str(), path) != 0) {
@@ -182,6 +191,26 @@ int checkpoint_write_ex(const char* path, const float* rgb, int W, int rows, int
     (void)close(dfd);
   }
   return MCPT_OK;
+}
+
+}  // namespace
+
+namespace mcpt {
+namespace host {
+// (written by write_replacing: a temporary file, fsync, rename)
+int checkpoint_write_ex(const char* path, const float* rgb, int W, int rows, int pass_count, int next_pass,
+                        const char* tag, int H, unsigned long long rows_hash) {
+  if (!path || !rgb || W <= 0 || rows <= 0 || pass_count < 0 || H < 0) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  const size_t tag_len = tag ? std::strlen(tag) : 0;
+  if (tag_len >= MCPT_CHECKPOINT_TAG_MAX) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  const int32_t hdr[6] = {W, rows, pass_count, next_pass, (int32_t)tag_len, H};
+  const uint64_t hash = rows_hash;
+  const size_t n = (size_t)W * rows * 3;
+  return write_replacing(path, [&](FILE* f) {
+    return std::fwrite(kCkptMagic, 1, 8, f) == 8 && std::fwrite(hdr, sizeof(int32_t), 6, f) == 6 &&
+           std::fwrite(&hash, sizeof(hash), 1, f) == 1 && std::fwrite(tag ? tag : "", 1, tag_len, f) == tag_len &&
+           std::fwrite(rgb, sizeof(float), n, f) == n;
+  });
 }
 
 int checkpoint_read_ex(const char* path, float* rgb_out, long long capacity, int* W, int* rows, int* pass_count,
@@ -228,6 +257,81 @@ int mcpt_checkpoint_read(const char* path, float* rgb_out, long long capacity, i
                          int* next_pass, char* tag_out) {
   return mcpt::host::checkpoint_read_ex(path, rgb_out, capacity, W, rows, pass_count, next_pass, tag_out, nullptr,
                                         nullptr);
+}
+
+// a valid header: positive sizes below 2^31 pixels, the block grid of W x rows, a tag that fits
+static bool adaptive_header_ok(const AdaptiveFileHeader& h) {
+  if (h.W <= 0 || h.rows <= 0 || (long long)h.W * h.rows >= (1LL << 31)) return false;
+  if (h.pass_count < 0 || h.tag_len < 0 || h.tag_len >= MCPT_CHECKPOINT_TAG_MAX || h.H < 0) return false;
+  if (h.p0 < 0 || h.min_passes < 0 || h.stats_passes < 0 || h.stats_batches < 0) return false;
+  if (h.emap_valid != 0 && h.emap_valid != 1) return false;
+  const long long bx = ((long long)h.W + 7) / 8, by = ((long long)h.rows + 7) / 8;
+  return h.blocks_x == bx && h.n_blocks == bx * by;
+}
+
+int mcpt_adaptive_checkpoint_write(const char* path, const mcpt_adaptive_checkpoint_t* hdr, const char* tag,
+                                   const int* block_active, const int* block_passes, const float* accum,
+                                   const float* stats4, const float* emap2) {
+  if (!path || !hdr || !block_active || !block_passes || !accum || !stats4 || !emap2)
+    return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  const size_t tag_len = tag ? std::strlen(tag) : 0;
+  if (tag_len >= MCPT_CHECKPOINT_TAG_MAX) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  AdaptiveFileHeader h;
+  h.W = hdr->W; h.rows = hdr->rows; h.pass_count = hdr->pass_count; h.next_pass = hdr->next_pass;
+  h.tag_len = (int32_t)tag_len; h.H = hdr->H; h.rows_hash = hdr->rows_hash;
+  h.p0 = hdr->p0; h.min_passes = hdr->min_passes; h.stats_passes = hdr->stats_passes;
+  h.stats_batches = hdr->stats_batches; h.emap_valid = hdr->emap_valid;
+  h.n_blocks = hdr->n_blocks; h.blocks_x = hdr->blocks_x;
+  if (!adaptive_header_ok(h)) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  const size_t n = (size_t)h.W * (size_t)h.rows, nb = (size_t)h.n_blocks;
+  return write_replacing(path, [&](FILE* f) {
+    return std::fwrite(kCkptMagicAdaptive, 1, 8, f) == 8 && std::fwrite(&h, sizeof(h), 1, f) == 1 &&
+           std::fwrite(tag ? tag : "", 1, tag_len, f) == tag_len &&
+           std::fwrite(block_active, sizeof(int32_t), nb, f) == nb &&
+           std::fwrite(block_passes, sizeof(int32_t), nb, f) == nb &&
+           std::fwrite(accum, sizeof(float), n * 3, f) == n * 3 && std::fwrite(stats4, sizeof(float), n * 4, f) == n * 4 &&
+           std::fwrite(emap2, sizeof(float), n * 2, f) == n * 2;
+  });
+}
+
+int mcpt_adaptive_checkpoint_read(const char* path, mcpt_adaptive_checkpoint_t* hdr, char* tag_out, int* block_active,
+                                  int* block_passes, long long block_capacity, float* accum, float* stats4,
+                                  float* emap2, long long pixel_capacity) {
+  if (!path) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  const bool arrays = block_active || block_passes || accum || stats4 || emap2;
+  if (arrays && !(block_active && block_passes && accum && stats4 && emap2)) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  FILE* f = std::fopen(path, "rb");
+  if (!f) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  char magic[8];
+  AdaptiveFileHeader h;
+  char tag[MCPT_CHECKPOINT_TAG_MAX];
+  bool ok = std::fread(magic, 1, 8, f) == 8 && std::memcmp(magic, kCkptMagicAdaptive, 8) == 0 &&
+            std::fread(&h, sizeof(h), 1, f) == 1 && adaptive_header_ok(h) &&
+            std::fread(tag, 1, (size_t)h.tag_len, f) == (size_t)h.tag_len;
+  if (ok) {
+    // the sections' sizes follow from the header: a file of any other length is truncated or foreign
+    const unsigned long long n = (unsigned long long)h.W * (unsigned long long)h.rows, nb = (unsigned long long)h.n_blocks;
+    const unsigned long long want = 8 + sizeof(h) + (unsigned long long)h.tag_len + nb * 8 + n * 36;
+    struct stat sb;
+    ok = fstat(fileno(f), &sb) == 0 && sb.st_size >= 0 && (unsigned long long)sb.st_size == want;
+    if (ok && arrays)
+      ok = block_capacity >= 0 && nb <= (unsigned long long)block_capacity && pixel_capacity >= 0 &&
+           n <= (unsigned long long)pixel_capacity && std::fread(block_active, sizeof(int32_t), nb, f) == nb &&
+           std::fread(block_passes, sizeof(int32_t), nb, f) == nb && std::fread(accum, sizeof(float), n * 3, f) == n * 3 &&
+           std::fread(stats4, sizeof(float), n * 4, f) == n * 4 && std::fread(emap2, sizeof(float), n * 2, f) == n * 2;
+  }
+  std::fclose(f);
+  if (!ok) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  tag[h.tag_len] = '\0';
+  if (hdr) {
+    std::memset(hdr, 0, sizeof(*hdr));
+    hdr->W = h.W; hdr->rows = h.rows; hdr->pass_count = h.pass_count; hdr->next_pass = h.next_pass; hdr->H = h.H;
+    hdr->rows_hash = h.rows_hash; hdr->p0 = h.p0; hdr->min_passes = h.min_passes; hdr->stats_passes = h.stats_passes;
+    hdr->stats_batches = h.stats_batches; hdr->emap_valid = h.emap_valid; hdr->n_blocks = h.n_blocks;
+    hdr->blocks_x = h.blocks_x;
+  }
+  if (tag_out) std::memcpy(tag_out, tag, (size_t)h.tag_len + 1);
+  return MCPT_OK;
 }
 
 int mcpt_transfo_translate(float x, float y, float z, float* out16) {

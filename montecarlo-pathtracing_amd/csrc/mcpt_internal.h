@@ -277,6 +277,13 @@ hipError_t mcpt_launch_adaptive_add_passes(const mcpt::AdaptiveTarget& t, const 
 hipError_t mcpt_launch_adaptive_counts(const mcpt::AdaptiveTarget& t, int* counts, hipStream_t stream);
 hipError_t mcpt_launch_adaptive_resolve(const mcpt::AdaptiveTarget& t, const float* accum, float* out,
                                         hipStream_t stream);
+// mcpt_launch_average4's twin for a frame with per-pixel counts: out = {accum / (float)count, 0},
+// the count from `plane` (one int per pixel) or, plane null, from t's block arrays; t.W and
+// t.n_local_rows size the launch either way
+hipError_t mcpt_launch_resolve4(const mcpt::AdaptiveTarget& t, const int* plane, const float* accum, float4* out,
+                                hipStream_t stream);
+hipError_t mcpt_launch_resolve_plane(const int* plane, const float* accum, float* out, long long n_px,
+                                     hipStream_t stream);
 hipError_t mcpt_iota(int* a, int n, hipStream_t stream);
 hipError_t mcpt_split_count(const unsigned* cost_sorted, int n, int capacity, int split_max, int* out,
                             unsigned long long* dbg, hipStream_t stream);

@@ -75,6 +75,14 @@ class Adaptive(ctypes.Structure):
                                        ("samples", ctypes.c_longlong)]
 
 
+class AdaptiveCheckpoint(ctypes.Structure):
+    """mcpt_adaptive_checkpoint_t (include/mcpt.h): the header of an adaptive checkpoint file."""
+    _fields_ = [("W", ctypes.c_int), ("rows", ctypes.c_int), ("pass_count", ctypes.c_int), ("next_pass", ctypes.c_int),
+                ("H", ctypes.c_int), ("rows_hash", ctypes.c_ulonglong), ("p0", ctypes.c_int),
+                ("min_passes", ctypes.c_int), ("stats_passes", ctypes.c_longlong), ("stats_batches", ctypes.c_int),
+                ("emap_valid", ctypes.c_int), ("n_blocks", ctypes.c_int), ("blocks_x", ctypes.c_int)]
+
+
 class Hit(ctypes.Structure):
     """mcpt_hit (include/mcpt.h): one ray-query result."""
     _fields_ = [("shape", ctypes.c_int), ("prim", ctypes.c_int), ("dir", ctypes.c_int), ("dist", ctypes.c_float),
@@ -200,6 +208,15 @@ def _declare(L: ctypes.CDLL) -> None:
         "mcpt_read_resolved": (i, [_vp, fp]),
         "mcpt_adaptive_info": (i, [_vp, ip, ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_longlong)]),
         "mcpt_last_adaptive_ms": (i, [_vp, fp, fp]),
+        "mcpt_denoise_resolved": (i, [_vp, i, f, f]),
+        "mcpt_denoise_resolved_guided": (i, [_vp, i, f, f]),
+        "mcpt_gather_rows_counted": (i, [_vp, ctypes.POINTER(_vp), i]),
+        "mcpt_adaptive_checkpoint_save": (i, [_vp, ctypes.c_char_p, i, ctypes.c_char_p]),
+        "mcpt_adaptive_checkpoint_load": (i, [_vp, ctypes.c_char_p, ctypes.c_char_p, ip]),
+        "mcpt_adaptive_checkpoint_write": (i, [ctypes.c_char_p, ctypes.POINTER(AdaptiveCheckpoint), ctypes.c_char_p, ip,
+                                               ip, fp, fp, fp]),
+        "mcpt_adaptive_checkpoint_read": (i, [ctypes.c_char_p, ctypes.POINTER(AdaptiveCheckpoint), ctypes.c_char_p, ip,
+                                              ip, ctypes.c_longlong, fp, fp, fp, ctypes.c_longlong]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -485,6 +502,56 @@ def checkpoint_read(path: str) -> Tuple[np.ndarray, int, int, str]:
     if (rows.value, w.value, 3) != out.shape:
         raise MCPTError("checkpoint_read: the file changed while it was read")
     return out, pc.value, nxt.value, tag.value.decode()
+
+
+# ---- checkpoint / resume of an adaptive render (mcpt.h: mcpt_adaptive_checkpoint_write / _read)
+_ADAPTIVE_HEADER_KEYS = ("pass_count", "next_pass", "H", "rows_hash", "p0", "min_passes", "stats_passes",
+                         "stats_batches", "emap_valid")
+
+
+def adaptive_checkpoint_write(path: str, header: dict, block_active, block_passes, accum, stats, emap,
+                              tag: str = "") -> None:
+    """An "MCPTCKA1" file from plain arrays: accum rows x W x 3, stats rows x W x 4 ({Yacc, S2, Ybase, 0}),
+    emap rows x W x 2 ({se, r}), all f32; block_active / block_passes one int32 per 8x8 block of the
+    rows x W grid; header = {pass_count, next_pass, H, rows_hash, p0, min_passes, stats_passes,
+    stats_batches, emap_valid} (missing keys: 0)."""
+    a = np.ascontiguousarray(accum, np.float32)
+    if a.ndim != 3 or a.shape[2] != 3:
+        raise MCPTError("adaptive_checkpoint_write: accum must be rows x W x 3")
+    rows, w = a.shape[0], a.shape[1]
+    st = np.ascontiguousarray(stats, np.float32)
+    em = np.ascontiguousarray(emap, np.float32)
+    act = np.ascontiguousarray(block_active, np.int32).reshape(-1)
+    pas = np.ascontiguousarray(block_passes, np.int32).reshape(-1)
+    bx, by = (w + 7) // 8, (rows + 7) // 8
+    if st.shape != (rows, w, 4) or em.shape != (rows, w, 2) or act.size != bx * by or pas.size != bx * by:
+        raise MCPTError("adaptive_checkpoint_write: the arrays' shapes do not belong to one rows x W target")
+    h = AdaptiveCheckpoint(W=w, rows=rows, n_blocks=bx * by, blocks_x=bx)
+    for k in _ADAPTIVE_HEADER_KEYS:
+        setattr(h, k, int(header.get(k, 0)))
+    _check(lib().mcpt_adaptive_checkpoint_write(str(path).encode(), ctypes.byref(h), tag.encode(), _ip(act), _ip(pas),
+                                                _fp(a), _fp(st), _fp(em)), "mcpt_adaptive_checkpoint_write")
+
+
+def adaptive_checkpoint_read(path: str) -> dict:
+    """The header fields of an "MCPTCKA1" file (W, rows, n_blocks, blocks_x and
+    adaptive_checkpoint_write's header keys), "tag", and the arrays "block_active", "block_passes",
+    "accum", "stats", "emap" in adaptive_checkpoint_write's shapes."""
+    h = AdaptiveCheckpoint()
+    tag = ctypes.create_string_buffer(CHECKPOINT_TAG_MAX)
+    _check(lib().mcpt_adaptive_checkpoint_read(str(path).encode(), ctypes.byref(h), None, None, None, 0, None, None,
+                                               None, 0), "mcpt_adaptive_checkpoint_read")
+    rows, w, nb = h.rows, h.W, h.n_blocks
+    act, pas = np.empty(nb, np.int32), np.empty(nb, np.int32)
+    acc, st, em = (np.empty((rows, w, k), np.float32) for k in (3, 4, 2))
+    # the capacities bound the read if the file was replaced in between; the shape is re-read
+    _check(lib().mcpt_adaptive_checkpoint_read(str(path).encode(), ctypes.byref(h), tag, _ip(act), _ip(pas), nb,
+                                               _fp(acc), _fp(st), _fp(em), rows * w), "mcpt_adaptive_checkpoint_read")
+    if (h.rows, h.W, h.n_blocks) != (rows, w, nb):
+        raise MCPTError("adaptive_checkpoint_read: the file changed while it was read")
+    out = {k: getattr(h, k) for k, _ in AdaptiveCheckpoint._fields_}
+    out.update(tag=tag.value.decode(), block_active=act, block_passes=pas, accum=acc, stats=st, emap=em)
+    return out
 
 
 class Renderer:
@@ -862,6 +929,50 @@ class Renderer:
             rec = self.adaptive_select(threshold, mu_floor)     # (fewer than two batches: MCPT_ERR_NO_STATS)
         rec["rendered"] = done
         return rec
+
+    # ---- frames with per-pixel sample counts: filter, checkpoint, gather (mcpt.h)
+    def denoise_resolved(self, iterations: int = 5, sigma_color: float = DENOISE_SIGMA_COLOR,
+                         sigma_plane: float = DENOISE_SIGMA_PLANE) -> np.ndarray:
+        """mcpt_denoise_resolved + mcpt_read_denoised: denoise() over accum / (float)count with every
+        pixel's own sample count (adaptive mode on, or after gather_rows_counted)."""
+        _check(lib().mcpt_denoise_resolved(self._h, int(iterations), float(sigma_color), float(sigma_plane)),
+               "mcpt_denoise_resolved")
+        out = np.zeros((self.n_local_rows, self.W, 3), np.float32)
+        _check(lib().mcpt_read_denoised(self._h, _fp(out)), "mcpt_read_denoised")
+        return out
+
+    def denoise_resolved_guided(self, iterations: int = 5, k_color: float = DENOISE_K_COLOR,
+                                sigma_plane: float = DENOISE_SIGMA_PLANE) -> np.ndarray:
+        """mcpt_denoise_resolved_guided + mcpt_read_denoised: denoise_guided() over the resolved
+        colour, with the error map of the last adaptive_select()."""
+        _check(lib().mcpt_denoise_resolved_guided(self._h, int(iterations), float(k_color), float(sigma_plane)),
+               "mcpt_denoise_resolved_guided")
+        out = np.zeros((self.n_local_rows, self.W, 3), np.float32)
+        _check(lib().mcpt_read_denoised(self._h, _fp(out)), "mcpt_read_denoised")
+        return out
+
+    def save_adaptive_checkpoint(self, path: str, next_pass: int, tag: str = "") -> None:
+        """mcpt_adaptive_checkpoint_save: the accumulator, the statistics window, the error map and
+        the blocks' state of an adaptive render (the mode must be on) to `path`."""
+        _check(lib().mcpt_adaptive_checkpoint_save(self._h, str(path).encode(), int(next_pass), tag.encode()),
+               "mcpt_adaptive_checkpoint_save")
+
+    def load_adaptive_checkpoint(self, path: str, tag: Optional[str] = None) -> int:
+        """mcpt_adaptive_checkpoint_load: resume an adaptive render saved for this target (and, if
+        given, with this tag): statistics and the adaptive mode come on in the saved state; returns
+        the first pass of the next render call."""
+        nxt = ctypes.c_int()
+        _check(lib().mcpt_adaptive_checkpoint_load(self._h, str(path).encode(),
+                                                   None if tag is None else tag.encode(), ctypes.byref(nxt)),
+               "mcpt_adaptive_checkpoint_load")
+        return nxt.value
+
+    def gather_rows_counted(self, shards) -> None:
+        """mcpt_gather_rows_counted: gather_rows() for shards with per-pixel counts or different pass
+        counts; their counts fill this full-frame renderer's count plane (read_sample_counts,
+        read_resolved, denoise_resolved).  Every frame row must come from exactly one shard."""
+        hs = (_vp * max(len(shards), 1))(*[s._h for s in shards])
+        _check(lib().mcpt_gather_rows_counted(self._h, hs, len(shards)), "mcpt_gather_rows_counted")
 
     def trace(self, origins, dirs, any_hit: bool = False, prim: int = -1) -> np.ndarray:
         """Ray queries (traverse_all_bvh / just_hit_bvh, or one primitive) + intersection_info.

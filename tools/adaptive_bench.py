@@ -10,6 +10,13 @@
     the plain twin of the same kernel — interleaved, device times, medians and spread.
 (d) scenes 1, 6, 8 at 480x270: RMSE of the resolved adaptive image against the scene's own 2,048-spp
     render (other passes), beside a uniform render of the same sample count and of the same wall time.
+(e) the resolve step of mcpt_denoise_resolved (accum / each pixel's own count -> the filter's first
+    float4 buffer) against the averaging step of mcpt_denoise, mcpt_denoise_iteration_ms(-1) of each,
+    interleaved in one process, scene 6 at 1080p and 4K, medians of 20 after 3 warm-ups: with nothing
+    retired (both read the same frame), and with about half the blocks retired, the counts from the
+    block arrays and from the count plane of a counted gather separately.  Byte floor: 12 B read and
+    16 B written per pixel, plus 8 B per block or 4 B per pixel for the counts.
+    `--only e` measures (e) alone and keeps the other sections of an existing --out file.
 Medians of `reps` runs after warm-ups; the spread is (max - min) / median."""
 import argparse
 import json
@@ -141,23 +148,105 @@ def bench_point(r, thresholds):
     return out
 
 
+def compare(base, other):
+    """other / base of two interleaved series, and whether the medians differ by more than either
+    series' own run-to-run spread."""
+    ratio = other["median"] / base["median"]
+    return {"ratio": ratio, "outside_spread": abs(ratio - 1.0) > max(base["spread"], other["spread"])}
+
+
+def bench_resolve(r, reps=20, warm=3):
+    out = []
+    frame = mcpt.Renderer(0)
+    try:
+        for W, H in ((1920, 1080), (3840, 2160)):
+            cam = setup(r, 6, W, H)
+            r.stats_begin()
+            r.adaptive_begin(0)
+            r.render_adaptive(cam[0], cam[1], 1, 8, 0.0, 8)
+            r.render_adaptive(cam[0], cam[1], 9, 8, 0.0, 8)
+            r.render_guides(*cam)
+            lib = mcpt.lib()
+
+            def step_ms(ctx, fn):       # the step alone: 0 iterations, no image read back
+                st = fn(ctx._h, 0, 1.0, 1.0)
+                assert st == 0, st
+                return ctx.denoise_iteration_ms(-1)
+
+            avg, blk = [], []
+            for k in range(reps + warm):
+                a = step_ms(r, lib.mcpt_denoise)
+                b = step_ms(r, lib.mcpt_denoise_resolved)
+                if k >= warm:
+                    avg.append(a)
+                    blk.append(b)
+            info = r.adaptive_info()
+            assert info["n_active"] == info["n_blocks"]
+            n_px, n_blocks = W * H, info["n_blocks"]
+            a, b = med(avg), med(blk)
+            row = {"W": W, "H": H, "n_blocks": n_blocks,
+                   "floor_bytes": {"average": n_px * 28, "resolve_blocks": n_px * 28 + n_blocks * 8,
+                                   "resolve_plane": n_px * 32},
+                   "nothing_retired": {"average_ms": a, "resolve_blocks_ms": b, **compare(a, b),
+                                       "average_GBs": n_px * 28 / (a["median"] * 1e-3) / 1e9,
+                                       "resolve_blocks_GBs": (n_px * 28 + n_blocks * 8) / (b["median"] * 1e-3) / 1e9}}
+            # about half the blocks retired: a threshold at the median of the blocks' largest r
+            r.adaptive_select(1e-6)
+            rr = r.read_error_map()[..., 1]
+            by, bx = (H + 7) // 8, (W + 7) // 8
+            pad = np.zeros((by * 8, bx * 8), np.float32)
+            pad[:H, :W] = rr
+            bmax = pad.reshape(by, 8, bx, 8).max(axis=(1, 3))
+            rec = r.adaptive_select(float(np.median(bmax[bmax > 0])))
+            retired = 1.0 - rec["n_active_blocks"] / rec["n_blocks"]
+            r.render_adaptive(cam[0], cam[1], 17, 8, 0.0, 8)      # the counts now take two values
+            setup(frame, 6, W, H)
+            frame.render_guides(*cam)
+            frame.gather_rows_counted([r])                          # the same frame with its counts in a plane
+            avg, blk, pln = [], [], []
+            for k in range(reps + warm):
+                a = step_ms(frame, lib.mcpt_denoise)
+                b = step_ms(r, lib.mcpt_denoise_resolved)
+                c = step_ms(frame, lib.mcpt_denoise_resolved)
+                if k >= warm:
+                    avg.append(a)
+                    blk.append(b)
+                    pln.append(c)
+            a, b, c = med(avg), med(blk), med(pln)
+            row["half_retired"] = {"retired_fraction": retired, "average_ms": a, "resolve_blocks_ms": b,
+                                   "resolve_plane_ms": c, "blocks": compare(a, b), "plane": compare(a, c)}
+            out.append(row)
+            print(json.dumps(row), flush=True)
+            r.adaptive_end()
+            r.stats_end()
+    finally:
+        frame.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "adaptive_bench.json"))
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--thresholds", default="0.2,0.1,0.05")
+    ap.add_argument("--only", default="", help="e: measure section (e) alone, keep the rest of --out")
     a = ap.parse_args()
     r = mcpt.Renderer(0)
     try:
-        res = {"device": torch.cuda.get_device_name(0), "reps": a.reps,
-               "select": bench_select(r, a.reps), "list_path": bench_list_path(r, a.reps),
-               "point": bench_point(r, [float(x) for x in a.thresholds.split(",")])}
+        if a.only == "e":
+            res = json.load(open(a.out)) if os.path.exists(a.out) else {"device": torch.cuda.get_device_name(0)}
+            res["resolve"] = bench_resolve(r)
+        else:
+            res = {"device": torch.cuda.get_device_name(0), "reps": a.reps,
+                   "select": bench_select(r, a.reps), "list_path": bench_list_path(r, a.reps),
+                   "point": bench_point(r, [float(x) for x in a.thresholds.split(",")]),
+                   "resolve": bench_resolve(r)}
     finally:
         r.close()
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(res, f, indent=1)
-    print(json.dumps({k: res[k] for k in ("select", "list_path")}, indent=1))
+    print(json.dumps({k: res[k] for k in ("select", "list_path", "resolve") if k in res}, indent=1))
 
 
 if __name__ == "__main__":
