@@ -220,9 +220,39 @@ int mcpt_gather_rows(mcpt_ctx* frame, mcpt_ctx* const* shards, int n_shards);
  * mcpt_denoise_resolved filters the frame (mcpt_denoise_resolved_guided returns MCPT_ERR_NO_STATS:
  * the shards' error maps do not travel).  The plane stays valid until frame's accumulator changes:
  * mcpt_set_target*, mcpt_clear_accum, mcpt_write_accum, mcpt_checkpoint_load, mcpt_gather_rows and
- * any mcpt_render* into `frame` invalidate it.  Out of scope: the multi-process (torch.distributed
- * / RCCL) gather carries no counts. */
+ * any mcpt_render* into `frame` invalidate it.  The multi-process (torch.distributed / RCCL) gather
+ * carries counts through mcpt_pack_counted_device and mcpt_load_rows_counted below. */
 int mcpt_gather_rows_counted(mcpt_ctx* frame, mcpt_ctx* const* shards, int n_shards);
+
+/* The counted gather across processes (mcpt/dist.py ShardedRenderer.gather_counted):
+ * each rank packs its shard, the caller's collective moves the packed rows to one rank, and that rank
+ * loads them into a full-frame context.  A packed record is 16 bytes per pixel, {r, g, b, count}: the
+ * accumulator's three f32 words bit for bit and the pixel's int32 sample count; rows in local order,
+ * n_local x W records.  Nothing on the way may read the words as floats (sums may be inf or NaN,
+ * counts are denormal bit patterns): carry them as int32.
+ *
+ * mcpt_pass_count: the accumulator's pass count (what mcpt_read_accum reports) without the copy;
+ * host only, no synchronization.
+ * mcpt_pack_counted_device: the local accumulator and every pixel's sample count into `dst_dev`
+ * (16-byte aligned, `bytes` >= n_local x W x 16, else MCPT_ERR_INVALID_ARG; MCPT_ERR_NO_TARGET without a
+ * target).  The count is chosen as mcpt_gather_rows_counted chooses a shard's: the count plane when
+ * valid, else the adaptive mode's per-pixel counts, else the pass count for every pixel; any target,
+ * mode on or off.  One kernel on the context's stream, ordered after the queued renders like
+ * mcpt_copy_accum_device; asynchronous.
+ * mcpt_load_rows_counted: `frame` (a full-frame target in row order) <- packed rows on frame's
+ * device: frame row y from row src_row[y] of the src_rows x W records at `src_dev` (16-byte aligned).
+ * src_row: H ints on the host, each in [0, src_rows); pass_count > 0; else MCPT_ERR_INVALID_ARG and
+ * `frame` keeps what it has.  One kernel on frame's stream writes the sums to the accumulator and the
+ * counts to the count plane (allocated and freed as mcpt_gather_rows_counted's); asynchronous.  The
+ * index is uploaded when it differs from the previous call's (replacing one waits for the stream).
+ * Afterwards `frame` is in the state mcpt_gather_rows_counted leaves: per-pixel counts from the plane,
+ * its pass count = pass_count, mcpt_read_sample_counts / mcpt_read_resolved / mcpt_denoise_resolved
+ * serve it, mcpt_denoise_resolved_guided returns MCPT_ERR_NO_STATS, and the same calls invalidate the
+ * plane. */
+int mcpt_pass_count(mcpt_ctx* ctx, int* pass_count);
+int mcpt_pack_counted_device(mcpt_ctx* ctx, void* dst_dev, size_t bytes);
+int mcpt_load_rows_counted(mcpt_ctx* frame, const void* src_dev, long long src_rows, const int* src_row,
+                           int pass_count);
 
 /* Select the traversal strategy (mcpt_traversal) for later renders; default AUTO.  AUTO times
  * its schedule candidates on the first launches of >= 2^24 samples after a scene upload — the
@@ -458,7 +488,8 @@ int mcpt_last_stats_ms(mcpt_ctx* ctx, float* update_ms, float* error_ms);
  *
  * A context HAS PER-PIXEL SAMPLE COUNTS when (a) the adaptive mode is on (the count of a pixel is
  * the pass count at mcpt_adaptive_begin plus its block's passes) or (b) a counted gather has filled
- * its count plane (mcpt_gather_rows_counted).  The resolved colour of a pixel is accum /
+ * its count plane: mcpt_gather_rows_counted inside one process, or mcpt_load_rows_counted from the
+ * packed rows a multi-process gather delivered.  The resolved colour of a pixel is accum /
  * (float)count per channel, mcpt_read_resolved's bits; mcpt_read_sample_counts and
  * mcpt_read_resolved serve both cases (MCPT_ERR_NO_ADAPTIVE with neither).
  *
@@ -472,8 +503,10 @@ int mcpt_last_stats_ms(mcpt_ctx* ctx, float* update_ms, float* error_ms);
  * (case b) it always returns MCPT_ERR_NO_STATS.  With no block retired the resolved forms give
  * mcpt_denoise's bits.
  *
- * Out of scope, the only remaining gap: the multi-process gather (torch.distributed / RCCL,
- * mcpt/dist.py) carries no counts. */
+ * Both gathers carry the counts: in one process mcpt_gather_rows_counted, across processes
+ * (torch.distributed / RCCL, mcpt/dist.py) mcpt_pack_counted_device on every rank and
+ * mcpt_load_rows_counted on the receiving one.  Out of scope: the shards' error maps do not travel
+ * with either, so the guided filter on a gathered frame returns MCPT_ERR_NO_STATS. */
 typedef struct mcpt_adaptive_t {
   long long n_px, n_above;
   unsigned long long sum_q;

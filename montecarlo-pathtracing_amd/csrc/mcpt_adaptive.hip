@@ -192,6 +192,41 @@ __global__ __launch_bounds__(256) void resolve_plane_kernel(const int* __restric
   out[3 * i] = accum[3 * i] / nb; out[3 * i + 1] = accum[3 * i + 1] / nb; out[3 * i + 2] = accum[3 * i + 2] / nb;
 }
 
+// The multi-process counted gather's two ends.  A packed record is 16 bytes per
+// pixel, {r, g, b, count}: the accumulator's three f32 words as they are and the pixel's int32 sample
+// count.  Both kernels move words, never floats (an overflowed sum's inf / NaN payload and a count's
+// denormal bit pattern pass through), one lane per pixel, a workgroup per 256 columns of a row, the
+// 16-byte side as one vector access per lane.
+//  * pack_counted_kernel: the shard's rows in local order.  The count is the count plane's (plane
+//    non-null), else p0 + the block's passes (t.passes non-null: the adaptive mode), else `uniform`.
+//  * load_rows_counted_kernel: frame row y from packed row src_row[y]; the sums to accum, the counts
+//    to the plane (the row scatter and the split in one pass).
+__global__ __launch_bounds__(256) void pack_counted_kernel(AdaptiveTarget t, const int* __restrict__ plane,
+                                                           int uniform, const unsigned* __restrict__ accum,
+                                                           uint4* __restrict__ out) {
+  const int x = blockIdx.x * 256 + threadIdx.x;
+  if (x >= t.W) return;
+  for (int lr = blockIdx.y; lr < t.n_local_rows; lr += gridDim.y) {
+    const long long i = (long long)lr * t.W + x;
+    const int n = plane ? plane[i] : t.passes ? t.p0 + t.passes[(lr >> 3) * t.blocks_x + (x >> 3)] : uniform;
+    out[i] = make_uint4(accum[3 * i], accum[3 * i + 1], accum[3 * i + 2], (unsigned)n);
+  }
+}
+
+__global__ __launch_bounds__(256) void load_rows_counted_kernel(const uint4* __restrict__ src,
+                                                                const int* __restrict__ src_row, int W, int H,
+                                                                unsigned* __restrict__ accum,
+                                                                int* __restrict__ plane) {
+  const int x = blockIdx.x * 256 + threadIdx.x;
+  if (x >= W) return;
+  for (int y = blockIdx.y; y < H; y += gridDim.y) {
+    const uint4 v = src[(long long)src_row[y] * W + x];   // (the host checked 0 <= src_row[y] < src_rows)
+    const long long i = (long long)y * W + x;
+    accum[3 * i] = v.x; accum[3 * i + 1] = v.y; accum[3 * i + 2] = v.z;
+    plane[i] = (int)v.w;
+  }
+}
+
 __global__ __launch_bounds__(256) void combine_list_kernel(float* __restrict__ accum, const float* __restrict__ partial,
                                                            long long n_px, int n_seg, int W, int n_local_rows,
                                                            int blocks_x, int n_blocks, const int* __restrict__ list,
@@ -274,6 +309,25 @@ hipError_t mcpt_launch_resolve_plane(const int* plane, const float* accum, float
                                      hipStream_t stream) {
   if (n_px <= 0) return hipSuccess;
   hipLaunchKernelGGL(mcpt::resolve_plane_kernel, dim3(grid256(n_px)), dim3(256), 0, stream, plane, accum, out, n_px);
+  return hipGetLastError();
+}
+
+// a workgroup per 256 columns of a row; rows past the grid's y limit are stepped over
+static dim3 row_grid(int W, int rows) { return dim3(grid256(W), (unsigned)std::min(rows, 65535)); }
+
+hipError_t mcpt_launch_pack_counted(const mcpt::AdaptiveTarget& t, const int* plane, int uniform, const float* accum,
+                                    void* out, hipStream_t stream) {
+  if (t.W <= 0 || t.n_local_rows <= 0) return hipSuccess;
+  hipLaunchKernelGGL(mcpt::pack_counted_kernel, row_grid(t.W, t.n_local_rows), dim3(256), 0, stream, t, plane, uniform,
+                     reinterpret_cast<const unsigned*>(accum), static_cast<uint4*>(out));
+  return hipGetLastError();
+}
+
+hipError_t mcpt_launch_load_rows_counted(const void* src, const int* src_row, int W, int H, float* accum, int* plane,
+                                         hipStream_t stream) {
+  if (W <= 0 || H <= 0) return hipSuccess;
+  hipLaunchKernelGGL(mcpt::load_rows_counted_kernel, row_grid(W, H), dim3(256), 0, stream,
+                     static_cast<const uint4*>(src), src_row, W, H, reinterpret_cast<unsigned*>(accum), plane);
   return hipGetLastError();
 }
 

@@ -2,6 +2,7 @@
 // the à-trous denoiser, noise statistics and the convergence metric, adaptive sampling).
 #include <algorithm>
 #include <cmath>
+#include <cstdint>
 #include <cstring>
 
 #include "mcpt_ctx.h"
@@ -559,6 +560,70 @@ int mcpt_last_adaptive_ms(mcpt_ctx* c, float* select_ms, float* render_ms) {
   HIP_OR_RETURN(hipSetDevice(c->device));
   OK_OR_RETURN(pair_ms(c->ad_select_timed, c->ad_ev[0], c->ad_ev[1], select_ms));
   return pair_ms(c->ad_render_timed, c->ad_ev[2], c->ad_ev[3], render_ms);
+}
+
+// ---- the multi-process counted gather's two ends (the collective between them is
+// the caller's: mcpt/dist.py)
+int mcpt_pass_count(mcpt_ctx* c, int* pass_count) {
+  if (!c || !pass_count) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  if (!c->has_target) return mcpt_err_bare(MCPT_ERR_NO_TARGET);
+  *pass_count = c->pass_count;
+  return MCPT_OK;
+}
+
+constexpr size_t kPackedBytes = 16;   // {r, g, b, count} per pixel
+
+int mcpt_pack_counted_device(mcpt_ctx* c, void* dst, size_t bytes) {
+  if (!c) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  if (!c->has_target) return mcpt_err_bare(MCPT_ERR_NO_TARGET);
+  const size_t need = (size_t)c->n_local_rows * c->W * kPackedBytes;
+  if (bytes < need) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_pack_counted_device: destination smaller than local pixels x 16 bytes");
+  if (need == 0) return MCPT_OK;
+  if (!dst || ((uintptr_t)dst & (kPackedBytes - 1)))
+    return set_err(MCPT_ERR_INVALID_ARG, "mcpt_pack_counted_device: destination must be a 16-byte aligned device pointer");
+  HIP_OR_RETURN(hipSetDevice(c->device));
+  // the count's source as the in-process counted gather picks it: the plane, the blocks, the pass count
+  mcpt::AdaptiveTarget t = adaptive_target(c);
+  if (!c->ad_on) { t.passes = nullptr; t.flags = nullptr; }
+  HIP_OR_RETURN(mcpt_launch_pack_counted(t, c->plane_valid ? c->d_count_plane : nullptr, c->pass_count, c->d_accum, dst,
+                                         c->stream));
+  return MCPT_OK;
+}
+
+int mcpt_load_rows_counted(mcpt_ctx* c, const void* src, long long src_rows, const int* src_row, int pass_count) {
+  if (!c || !src || !src_row || pass_count <= 0 || ((uintptr_t)src & (kPackedBytes - 1)))
+    return set_err(MCPT_ERR_INVALID_ARG, "mcpt_load_rows_counted: bad arguments (16-byte aligned source, pass_count > 0)");
+  if (!c->has_target) return set_err(MCPT_ERR_NO_TARGET, "mcpt_load_rows_counted: frame has no target");
+  if (c->n_local_rows != c->H) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_load_rows_counted: frame target is a shard");
+  for (int i = 0; i < c->H; ++i)
+    if (c->rows[(size_t)i] != i) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_load_rows_counted: frame target is not in row order");
+  for (int y = 0; y < c->H; ++y)
+    if (src_row[y] < 0 || src_row[y] >= src_rows)
+      return set_err(MCPT_ERR_INVALID_ARG, "mcpt_load_rows_counted: a source row lies outside the packed buffer");
+  c->plane_valid = false;   // (the accumulator is replaced)
+  if (c->H == 0 || c->W == 0) return MCPT_OK;
+  HIP_OR_RETURN(hipSetDevice(c->device));
+  const size_t n_px = (size_t)c->H * c->W, index_bytes = (size_t)c->H * sizeof(int);
+  if (!c->d_count_plane) HIP_OR_RETURN(hipMalloc(&c->d_count_plane, n_px * sizeof(int)));
+  if (!c->d_load_index) {
+    HIP_OR_RETURN(hipMalloc(&c->d_load_index, index_bytes));
+    c->load_index.clear();
+  }
+  if (c->load_index.size() != (size_t)c->H || std::memcmp(c->load_index.data(), src_row, index_bytes) != 0) {
+    // on the stream after the loads that read the previous index; a queued upload of the previous
+    // index may still read the host copy, so replacing one waits for it (a first upload does not)
+    if (!c->load_index.empty()) HIP_OR_RETURN(hipStreamSynchronize(c->stream));
+    c->load_index.assign(src_row, src_row + c->H);
+    const hipError_t e = hipMemcpyAsync(c->d_load_index, c->load_index.data(), index_bytes, hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) {
+      c->load_index.clear();
+      return set_err(MCPT_ERR_HIP, "mcpt_load_rows_counted: index upload", e);
+    }
+  }
+  HIP_OR_RETURN(mcpt_launch_load_rows_counted(src, c->d_load_index, c->W, c->H, c->d_accum, c->d_count_plane, c->stream));
+  c->pass_count = pass_count;
+  c->plane_valid = true;
+  return MCPT_OK;
 }
 
 int mcpt_read_denoised(mcpt_ctx* c, float* rgb_out) {

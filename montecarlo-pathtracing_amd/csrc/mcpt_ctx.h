@@ -165,7 +165,11 @@ struct mcpt_ctx {
   // a shard's own counts for a counted gather (4 B per local pixel, same lifetime): the peer copies
   // read them, and the shard's stream waits for those copies before its next work
   int* d_gather_counts = nullptr;
-  int next_lane = 0;                // the lane of the next sub-launch
+  // mcpt_load_rows_counted's row index (H ints, same lifetime): uploaded when it differs from the
+  // host copy kept here
+  int* d_load_index = nullptr;
+  std::vector<int> load_index;
+  int next_lane = 0;               // the lane of the next sub-launch
   int prev_lane = -1;               // the lane of the previous sub-launch if it was a lane launch, else -1
 };
 
@@ -195,8 +199,9 @@ inline void free_adaptive(mcpt_ctx* c) {
 }
 
 inline void free_count_plane(mcpt_ctx* c) {
-  (void)hipFree(c->d_count_plane); (void)hipFree(c->d_gather_counts);
-  c->d_count_plane = nullptr; c->d_gather_counts = nullptr;
+  (void)hipFree(c->d_count_plane); (void)hipFree(c->d_gather_counts); (void)hipFree(c->d_load_index);
+  c->d_count_plane = nullptr; c->d_gather_counts = nullptr; c->d_load_index = nullptr;
+  c->load_index.clear();
   c->plane_valid = false;
 }
 

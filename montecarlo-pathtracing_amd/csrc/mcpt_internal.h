@@ -284,6 +284,14 @@ hipError_t mcpt_launch_resolve4(const mcpt::AdaptiveTarget& t, const int* plane,
                                 hipStream_t stream);
 hipError_t mcpt_launch_resolve_plane(const int* plane, const float* accum, float* out, long long n_px,
                                      hipStream_t stream);
+// the multi-process counted gather's ends: 16-byte records {r, g, b bits, int32 count} per pixel.
+// pack: t's local rows in order into `out` (16-byte aligned), the count from `plane` (non-null), else
+// from t's block arrays (t.passes non-null), else `uniform`.  load: frame row y of a W x H frame from
+// packed row src_row[y] of `src` (16-byte aligned), the sums to accum and the counts to plane.
+hipError_t mcpt_launch_pack_counted(const mcpt::AdaptiveTarget& t, const int* plane, int uniform, const float* accum,
+                                    void* out, hipStream_t stream);
+hipError_t mcpt_launch_load_rows_counted(const void* src, const int* src_row, int W, int H, float* accum, int* plane,
+                                         hipStream_t stream);
 hipError_t mcpt_iota(int* a, int n, hipStream_t stream);
 hipError_t mcpt_split_count(const unsigned* cost_sorted, int n, int capacity, int split_max, int* out,
                             unsigned long long* dbg, hipStream_t stream);

@@ -211,6 +211,9 @@ def _declare(L: ctypes.CDLL) -> None:
         "mcpt_denoise_resolved": (i, [_vp, i, f, f]),
         "mcpt_denoise_resolved_guided": (i, [_vp, i, f, f]),
         "mcpt_gather_rows_counted": (i, [_vp, ctypes.POINTER(_vp), i]),
+        "mcpt_pass_count": (i, [_vp, ip]),
+        "mcpt_pack_counted_device": (i, [_vp, _vp, ctypes.c_size_t]),
+        "mcpt_load_rows_counted": (i, [_vp, _vp, ctypes.c_longlong, ip, i]),
         "mcpt_adaptive_checkpoint_save": (i, [_vp, ctypes.c_char_p, i, ctypes.c_char_p]),
         "mcpt_adaptive_checkpoint_load": (i, [_vp, ctypes.c_char_p, ctypes.c_char_p, ip]),
         "mcpt_adaptive_checkpoint_write": (i, [ctypes.c_char_p, ctypes.POINTER(AdaptiveCheckpoint), ctypes.c_char_p, ip,
@@ -973,6 +976,29 @@ class Renderer:
         read_resolved, denoise_resolved).  Every frame row must come from exactly one shard."""
         hs = (_vp * max(len(shards), 1))(*[s._h for s in shards])
         _check(lib().mcpt_gather_rows_counted(self._h, hs, len(shards)), "mcpt_gather_rows_counted")
+
+    # ---- the counted gather across processes (mcpt.h; DESIGN.md §3.9.1; mcpt.dist.ShardedRenderer)
+    def pass_count(self) -> int:
+        """mcpt_pass_count: read_accum()'s pass count without the copy or a wait."""
+        n = ctypes.c_int()
+        _check(lib().mcpt_pass_count(self._h, ctypes.byref(n)), "mcpt_pass_count")
+        return n.value
+
+    def pack_counted_device(self, dst_ptr: int, nbytes: int) -> None:
+        """mcpt_pack_counted_device: 16-byte records {r, g, b bits, int32 sample count} of the local
+        pixels into a device buffer (an int32 torch tensor), on our stream after the queued renders."""
+        _check(lib().mcpt_pack_counted_device(self._h, _vp(dst_ptr), ctypes.c_size_t(nbytes)),
+               "mcpt_pack_counted_device")
+
+    def load_rows_counted(self, src_ptr: int, src_rows: int, src_row, pass_count: int) -> None:
+        """mcpt_load_rows_counted: this full-frame renderer's accumulator and count plane <- packed
+        rows on its device, frame row y from packed row src_row[y] (H ints, each < src_rows); leaves
+        the state of gather_rows_counted with `pass_count` as the pass count.  Asynchronous."""
+        idx = np.ascontiguousarray(src_row, dtype=np.int32)
+        if idx.shape != (self.H,):
+            raise MCPTError(f"load_rows_counted: expected {self.H} source rows, got {idx.shape}")
+        _check(lib().mcpt_load_rows_counted(self._h, _vp(src_ptr), int(src_rows), _ip(idx), int(pass_count)),
+               "mcpt_load_rows_counted")
 
     def trace(self, origins, dirs, any_hit: bool = False, prim: int = -1) -> np.ndarray:
         """Ray queries (traverse_all_bvh / just_hit_bvh, or one primitive) + intersection_info.

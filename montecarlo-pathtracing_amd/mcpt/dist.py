@@ -12,6 +12,12 @@ data path of the render itself; the gather is the frame's only exchange step.
 
 The gather/reassembly here is device-agnostic torch code so the N>1 path is covered by
 world_size-2 ``gloo`` tests on CPU (tests/test_dist_gloo.py).
+
+Adaptive renders: ShardedRenderer passes the statistics and adaptive calls to
+its shard, merges the shards' select records over the process group (merge_adaptive_records) and
+gathers the frame WITH its per-pixel sample counts (gather_counted: 16 B/px int32 records, one
+gather, one load kernel into a full-frame context on rank 0; tests/test_dist_counted_gloo.py,
+tests/test_gpu_dist_adaptive.py).
 """
 from __future__ import annotations
 
@@ -74,8 +80,16 @@ def frame_row_index(H: int, band_rows: int, world: int, partition: str = "bands"
 class FrameGather:
     """Pre-allocated buffers + index for gathering row-band shards into a frame on `dst`.
 
-    ``gather(local)``: local is [n_local_rows, W, 3] on this rank's device; returns the
-    assembled [H, W, 3] frame on `dst` (None on other ranks).
+    ``gather(local)``: local is [n_local_rows, W, C] on this rank's device; returns the
+    assembled [H, W, C] frame on `dst` (None on other ranks).  ``gather_raw(local)`` runs the same
+    exchange and returns the receive buffer itself, [world * max_rows, W, C] in rank order (frame
+    row y is its row ``index[y]``; the padding rows of shorter shards are never indexed), for a
+    caller that scatters the rows itself (ShardedRenderer.gather_counted).
+
+    ``channels`` and ``dtype`` give the per-pixel record: the default, 3 float32, is the
+    accumulator's sums; 4 int32 is the counted gather's packed record {r, g, b bits, sample count}
+    (DESIGN.md §3.9.1), carried as integers so that no step of the exchange reads the words as floats.
+    ``assemble=False`` leaves the frame tensor out (gather_raw only).
 
     At world 1 the send buffer is the frame and no collective runs, unless
     ``force_collective``: then the world-1 gather goes through the process group like any other
@@ -84,24 +98,28 @@ class FrameGather:
 
     def __init__(self, H: int, W: int, band_rows: int, world: int, rank: int, device: torch.device,
                  dst: int = 0, group=None, use_gather: bool = True, partition: str = "bands",
-                 force_collective: bool = False):
+                 force_collective: bool = False, channels: int = 3, dtype: torch.dtype = torch.float32,
+                 assemble: bool = True):
         self.collective = world > 1 or force_collective
         self.H, self.W, self.band_rows, self.world, self.rank = H, W, band_rows, world, rank
         self.dst, self.group, self.device, self.partition = dst, group, device, partition
+        self.C = C = int(channels)
         self.m = max_local_rows(H, band_rows, world, partition)
         self.n_local = len(local_rows(H, band_rows, world, rank, partition))
-        self.send = torch.zeros((self.m, W, 3), dtype=torch.float32, device=device)
+        self.send = torch.zeros((self.m, W, C), dtype=dtype, device=device)
         self.use_gather = use_gather
         if rank == dst or not use_gather:
-            self.recv = torch.empty((world * self.m, W, 3), dtype=torch.float32, device=device)
-            self.recv_list = list(self.recv.view(world, self.m, W, 3).unbind(0))
+            self.recv = torch.empty((world * self.m, W, C), dtype=dtype, device=device)
+            self.recv_list = list(self.recv.view(world, self.m, W, C).unbind(0))
         else:
             self.recv, self.recv_list = None, None
         self.index = torch.as_tensor(frame_row_index(H, band_rows, world, partition), device=device)
-        self.frame = (torch.empty((H, W, 3), dtype=torch.float32, device=device)
-                      if rank == dst and self.collective else None)
+        self.frame = (torch.empty((H, W, C), dtype=dtype, device=device)
+                      if rank == dst and self.collective and assemble else None)
 
-    def gather(self, local: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
+    def gather_raw(self, local: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
+        """The exchange alone: the receive buffer [world * max_rows, W, C] on `dst` (the send buffer
+        at world 1 without force_collective), None on other ranks.  A buffer this object reuses."""
         if local is not None:
             self.send[: self.n_local].copy_(local)
         if not self.collective:
@@ -109,7 +127,7 @@ class FrameGather:
         staged = self.device.type != "cpu" and dist.get_backend(self.group) == "gloo"
         if staged:   # rehearsal of the N>1 path on one GPU (gloo collectives need host tensors)
             send, recv = self.send.cpu(), (self.recv.cpu() if self.recv is not None else None)
-            recv_list = list(recv.view(self.world, self.m, self.W, 3).unbind(0)) if recv is not None else None
+            recv_list = list(recv.view(self.world, self.m, self.W, self.C).unbind(0)) if recv is not None else None
         else:
             send, recv, recv_list = self.send, self.recv, self.recv_list
         if self.use_gather:
@@ -120,8 +138,55 @@ class FrameGather:
             return None
         if staged:
             self.recv.copy_(recv)
-        torch.index_select(self.recv, 0, self.index, out=self.frame)
+        return self.recv
+
+    def gather(self, local: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
+        recv = self.gather_raw(local)
+        if not self.collective or recv is None:
+            return recv
+        torch.index_select(recv, 0, self.index, out=self.frame)
         return self.frame
+
+
+# ---- the frame record of an adaptive select over row shards (include/mcpt.h: "the records of shards
+# add ... and max")
+RECORD_SUMS = ("n_px", "n_above", "sum_q", "samples", "n_active_blocks", "n_blocks")
+RECORD_MAXES = ("passes", "batches")
+
+
+def _f32_bits(x: float) -> int:
+    return int(np.array([x], np.float32).view(np.uint32)[0])
+
+
+def merge_adaptive_records(local: dict, group=None, device: Optional[torch.device] = None) -> dict:
+    """The frame's adaptive_select record from every rank's shard record: the integer fields of
+    RECORD_SUMS add, those of RECORD_MAXES and max_r take the largest, and mean_r is recomputed
+    as sum_q / 65536 / n_px (mcpt_adaptive_select's arithmetic).  One all-gather of nine int64 words
+    per rank (max_r travels as its bit pattern: r >= 0, so the bits order as the values), reduced
+    with Python integers: exact, a sum_q past 2^53 included.  Every rank returns the merged record,
+    with its own under "local".  `device`: where the collective's tensors live (default: the host
+    for gloo, else the current cuda device); needs no GPU over gloo."""
+    keys = RECORD_SUMS + RECORD_MAXES
+    words = [int(local[k]) for k in keys] + [_f32_bits(local["max_r"])]
+    if not all(0 <= w < 2 ** 63 for w in words):
+        raise ValueError(f"merge_adaptive_records: a field does not fit int64: {local}")
+    world = dist.get_world_size(group)
+    if dist.get_backend(group) == "gloo":
+        device = torch.device("cpu")
+    elif device is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    mine = torch.tensor(words, dtype=torch.int64, device=device)
+    parts = [torch.empty_like(mine) for _ in range(world)]
+    dist.all_gather(parts, mine, group=group)
+    rows = [p.tolist() for p in parts]
+    out = {}
+    for j, k in enumerate(keys):
+        col = [r[j] for r in rows]
+        out[k] = sum(col) if k in RECORD_SUMS else max(col)
+    out["max_r"] = float(np.array([max(r[-1] for r in rows)], np.uint32).view(np.float32)[0])
+    out["mean_r"] = out["sum_q"] / 65536.0 / out["n_px"] if out["n_px"] > 0 else 0.0
+    out["local"] = dict(local)
+    return out
 
 
 class ShardedRenderer:
@@ -149,7 +214,10 @@ class ShardedRenderer:
         else:
             self.r.set_target_rows(W, H, local_rows(H, band_rows, world, rank, partition))
         self.W, self.H, self.band_rows, self.world, self.rank = W, H, band_rows, world, rank
-        self.partition = partition
+        self.partition, self.local_rank, self.group, self.force_collective = partition, local_rank, group, force_collective
+        self.scene = None
+        self.gc = None            # the counted gather's buffers and frame context: made on first use
+        self.frame_r = None
         self.g = FrameGather(H, W, band_rows, world, rank, self.device, group=group, partition=partition,
                              force_collective=force_collective)
         # the gather buffers were allocated (and zero-filled) on the caller's stream
@@ -157,6 +225,9 @@ class ShardedRenderer:
 
     def upload_scene(self, scene) -> None:
         self.r.upload_scene(scene)
+        self.scene = scene
+        if self.frame_r is not None:
+            self.frame_r.upload_scene(scene)
 
     def render(self, invPV, invV, first_pass, n_passes, date=0.0, bounces=3, refract_ind=1.0, variant=0):
         self.r.render(invPV, invV, first_pass, n_passes, date, bounces, refract_ind, variant)
@@ -182,5 +253,116 @@ class ShardedRenderer:
         caller.wait_stream(self.stream)
         return frame
 
+    # ---- adaptive sampling over the shards: the shard context's calls, the
+    # frame's record merged over the group, and the counted gather
+    def stats_begin(self) -> None:
+        self.r.stats_begin()
+
+    def adaptive_begin(self, min_passes: int = 0) -> None:
+        self.r.adaptive_begin(min_passes)
+
+    def adaptive_end(self) -> None:
+        self.r.adaptive_end()
+
+    def render_adaptive(self, invPV, invV, first_pass, n_passes, date=0.0, bounces=3, refract_ind=1.0, variant=0):
+        self.r.render_adaptive(invPV, invV, first_pass, n_passes, date, bounces, refract_ind, variant)
+
+    def adaptive_select(self, threshold: float, mu_floor: Optional[float] = None) -> dict:
+        """The local select, then the shards' records merged over the process group
+        (merge_adaptive_records): the frame's record on every rank, this rank's under "local"."""
+        import mcpt
+        local = self.r.adaptive_select(threshold, mcpt.ERROR_MU_FLOOR if mu_floor is None else mu_floor)
+        if self.world == 1 and not self.force_collective:
+            return dict(local, local=dict(local))
+        return merge_adaptive_records(local, self.group, self.device)
+
+    def render_adaptive_until(self, invPV, invV, threshold: float, batch: int = 32, max_passes: int = 4096,
+                              min_passes: int = 0, check_every: int = 1, first_pass: int = 1, date: float = 0.0,
+                              bounces: int = 3, refract_ind: float = 1.0, variant: int = 0,
+                              mu_floor: Optional[float] = None) -> dict:
+        """mcpt.Renderer.render_adaptive_until over the shards: every rank renders its active blocks
+        in calls of `batch` passes and the loop ends on the MERGED record (no active block on any
+        rank, or `max_passes`), so every rank leaves it in the same round; a rank whose blocks have
+        all retired keeps calling (an empty list launches nothing).  Returns the last merged record
+        plus "rendered" (passes) and "rounds" (render calls); the mode stays on for gather_counted()."""
+        if batch <= 0 or check_every <= 0 or max_passes <= 0 or not threshold > 0:
+            raise ValueError("render_adaptive_until: batch, check_every, max_passes and threshold must be positive")
+        self.stats_begin()
+        self.adaptive_begin(min_passes)
+        done, calls, rec = 0, 0, None
+        while done < max_passes:
+            n = min(batch, max_passes - done)
+            self.render_adaptive(invPV, invV, first_pass + done, n, date, bounces, refract_ind, variant)
+            done += n
+            calls += 1
+            if calls >= 2 and (calls % check_every == 0 or done >= max_passes):
+                rec = self.adaptive_select(threshold, mu_floor)
+                if rec["n_active_blocks"] == 0:
+                    break
+        if rec is None:
+            rec = self.adaptive_select(threshold, mu_floor)     # (fewer than two batches: MCPT_ERR_NO_STATS)
+        rec["rendered"], rec["rounds"] = done, calls
+        return rec
+
+    def _counted_setup(self) -> None:
+        import mcpt
+        self.gc = FrameGather(self.H, self.W, self.band_rows, self.world, self.rank, self.device, group=self.group,
+                              partition=self.partition, force_collective=self.force_collective, channels=4,
+                              dtype=torch.int32, assemble=False)
+        self.src_row = frame_row_index(self.H, self.band_rows, self.world, self.partition).astype(np.int32)
+        self.most = torch.zeros(1, dtype=torch.int32, device=self.device)
+        if self.rank == self.gc.dst:
+            # the frame context shares the shard context's stream: its load is ordered after the
+            # collective, and its reads (read_accum, denoise_resolved, ...) after the load
+            self.frame_r = mcpt.Renderer(self.local_rank)
+            self.frame_r.set_stream(self.stream.cuda_stream)
+            self.frame_r.set_target(self.W, self.H)
+            if self.scene is not None:
+                self.frame_r.upload_scene(self.scene)
+
+    def gather_counted(self):
+        """gather() for an adaptive render: the frame WITH its per-pixel sample counts.  Every rank
+        packs its rows into 16 B/px records {r, g, b bits, int32 count} (mcpt_pack_counted_device;
+        with the adaptive mode off the count is the pass count), one gather moves them to rank 0 as
+        int32 words, and there one kernel (mcpt_load_rows_counted) scatters the rows into a
+        full-frame mcpt.Renderer on the same device and stream, which is returned (None on other
+        ranks): read_accum, read_sample_counts, read_resolved and denoise_resolved (after
+        render_guides) serve it exactly as after the in-process gather_rows_counted.  That renderer
+        is created on first use, reused by later calls and closed by close().
+
+        The frame's pass count is the largest over the ranks: a 1-element MAX reduction in the same
+        group and, on rank 0, ONE host read of it (a stream wait).  The call ends a render and does
+        not belong in a timed loop of launches; gather() stays free of host waits.
+
+        Stream discipline as gather(): the private stream first waits for the caller's current
+        stream, pack, collective and load run on it, and the caller's stream then waits for it."""
+        if self.gc is None:
+            self._counted_setup()
+        g, n = self.gc, self.gc.n_local
+        most = self.r.pass_count()
+        caller = torch.cuda.current_stream(self.device)
+        self.stream.wait_stream(caller)   # (also orders the first call's buffer fills before the pack)
+        with torch.cuda.stream(self.stream):
+            if n:
+                self.r.pack_counted_device(g.send.data_ptr(), n * self.W * 16)
+            raw = g.gather_raw(None)
+            if g.collective:
+                if dist.get_backend(self.group) == "gloo":   # host tensors (the staged rehearsal on one GPU)
+                    t = torch.tensor([most], dtype=torch.int32)
+                    dist.reduce(t, g.dst, op=dist.ReduceOp.MAX, group=self.group)
+                    most = int(t.item())
+                else:
+                    self.most.fill_(most)
+                    dist.reduce(self.most, g.dst, op=dist.ReduceOp.MAX, group=self.group)
+                    if self.rank == g.dst:
+                        most = int(self.most.item())   # the one host read
+            if raw is not None:
+                self.frame_r.load_rows_counted(raw.data_ptr(), raw.shape[0], self.src_row, most)
+        caller.wait_stream(self.stream)
+        return self.frame_r if raw is not None else None
+
     def close(self) -> None:
+        if self.frame_r is not None:
+            self.frame_r.close()
+            self.frame_r = None
         self.r.close()
