@@ -217,8 +217,8 @@ int mcpt_gather_rows(mcpt_ctx* frame, mcpt_ctx* const* shards, int n_shards);
  * count.  Every row of `frame` (a full-frame target in row order) must be held by exactly one
  * shard, else MCPT_ERR_INVALID_ARG: no pixel is left with count 0.  Afterwards `frame` has
  * per-pixel counts: mcpt_read_sample_counts and mcpt_read_resolved serve the plane and
- * mcpt_denoise_resolved filters the frame (mcpt_denoise_resolved_guided returns MCPT_ERR_NO_STATS:
- * the shards' error maps do not travel).  The plane stays valid until frame's accumulator changes:
+ * mcpt_denoise_resolved filters the frame (mcpt_denoise_resolved_guided returns MCPT_ERR_NO_STATS
+ * until the shards' error maps have been gathered too: mcpt_gather_error_map below).  The plane stays valid until frame's accumulator changes:
  * mcpt_set_target*, mcpt_clear_accum, mcpt_write_accum, mcpt_checkpoint_load, mcpt_gather_rows and
  * any mcpt_render* into `frame` invalidate it.  The multi-process (torch.distributed / RCCL) gather
  * carries counts through mcpt_pack_counted_device and mcpt_load_rows_counted below. */
@@ -247,12 +247,62 @@ int mcpt_gather_rows_counted(mcpt_ctx* frame, mcpt_ctx* const* shards, int n_sha
  * index is uploaded when it differs from the previous call's (replacing one waits for the stream).
  * Afterwards `frame` is in the state mcpt_gather_rows_counted leaves: per-pixel counts from the plane,
  * its pass count = pass_count, mcpt_read_sample_counts / mcpt_read_resolved / mcpt_denoise_resolved
- * serve it, mcpt_denoise_resolved_guided returns MCPT_ERR_NO_STATS, and the same calls invalidate the
- * plane. */
+ * serve it, mcpt_denoise_resolved_guided returns MCPT_ERR_NO_STATS (until mcpt_load_rows_error_map
+ * below), and the same calls invalidate the plane. */
 int mcpt_pass_count(mcpt_ctx* ctx, int* pass_count);
 int mcpt_pack_counted_device(mcpt_ctx* ctx, void* dst_dev, size_t bytes);
 int mcpt_load_rows_counted(mcpt_ctx* frame, const void* src_dev, long long src_rows, const int* src_row,
                            int pass_count);
+
+/* The GATHERED ERROR MAP of a frame context: the shards' error maps {se, r},
+ * which are per pixel and do not depend on the partition, moved to the context that holds the
+ * gathered frame, so that the noise-guided filters serve sharded renders.  State: a device plane of
+ * H x W x {se, r} f32 (8 B per pixel) with a validity flag, allocated by the first call that fills it
+ * after a mcpt_set_target* and freed by the next mcpt_set_target* / mcpt_destroy, alongside the count
+ * plane.  It describes the accumulator the frame holds, so everything that invalidates the count
+ * plane invalidates it: mcpt_set_target*, mcpt_clear_accum, mcpt_write_accum, mcpt_checkpoint_load,
+ * mcpt_gather_rows, mcpt_gather_rows_counted, mcpt_load_rows_counted and any mcpt_render* into the
+ * frame.  The order of use is therefore: gather the rows (plain or counted), then gather the map.
+ * The row gathers themselves are unchanged and carry no map.
+ *
+ * While the plane is valid, mcpt_denoise_guided (a plainly gathered frame of uniform shards) and
+ * mcpt_denoise_resolved_guided (a frame with a count plane) read it in place of the context's own
+ * window map, mcpt_read_error_map returns it (H x W x 2 f32), and mcpt_error_map_record reduces it.
+ * Without one all of them behave as before (MCPT_ERR_NO_STATS on a gathered frame).
+ *
+ * mcpt_gather_error_map: inside one process; peer copies of every shard's map rows into the plane at
+ * their global rows, one hipMemcpyPeerAsync per run of consecutive global rows, with
+ * mcpt_gather_rows_counted's stream ordering in both directions and device / event restore.
+ * `frame`: a full-frame target in row order with the shards' W x H; every frame row held by exactly
+ * one shard (else MCPT_ERR_INVALID_ARG); every shard with statistics on and an error map of its
+ * current window (else MCPT_ERR_NO_STATS), written by mcpt_convergence (uniform shards) or
+ * mcpt_adaptive_select (adaptive shards: retired blocks contribute their stored entries).  On any
+ * error the plane is left invalid.  Asynchronous.
+ * mcpt_pack_error_map_device: across processes, the sending end; the shard's n_local x W map entries
+ * in local row order into `dst_dev` (8-byte aligned, `bytes` >= n_local x W x 8, else
+ * MCPT_ERR_INVALID_ARG; MCPT_ERR_NO_TARGET without a target, MCPT_ERR_NO_STATS without a current map),
+ * a device-to-device copy on the context's stream after the queued work.  The words travel as bits
+ * (se may be inf or NaN for an overflowed pixel): carry them as int32, like the packed rows.
+ * mcpt_load_rows_error_map: the receiving end; frame row y of the plane from row src_row[y] of the
+ * src_rows x W 8-byte records at `src_dev` (8-byte aligned), one kernel on frame's stream that moves
+ * the records as integers; asynchronous.  The index contract is mcpt_load_rows_counted's (H host ints
+ * in [0, src_rows), else MCPT_ERR_INVALID_ARG), and the device copy of the index is shared with it: a
+ * counted load and a map load with the same index upload it once.  On any error the plane is left
+ * invalid.
+ * mcpt_error_map_record: the frame-level record of whichever map is current on the context: the
+ * gathered plane when valid, else the context's own window map, else MCPT_ERR_NO_STATS.  n_px,
+ * n_above = #{r > threshold}, max_r, sum_q and mean_r as mcpt_convergence defines them, reduced from
+ * the STORED r values (neither se nor r is recomputed), so the records of the shards' last
+ * mcpt_convergence / mcpt_adaptive_select with the same threshold add up to it; passes = the
+ * context's pass count for a gathered plane (batches = 0), the window's passes and batches for an own
+ * map.  Positive finite threshold, else MCPT_ERR_INVALID_ARG.  Synchronizes.
+ * mcpt_error_map_source: 0 no map, 1 the context's own window map, 2 the gathered plane; host only. */
+struct mcpt_convergence_t;   /* (defined with mcpt_convergence below) */
+int mcpt_gather_error_map(mcpt_ctx* frame, mcpt_ctx* const* shards, int n_shards);
+int mcpt_pack_error_map_device(mcpt_ctx* ctx, void* dst_dev, size_t bytes);
+int mcpt_load_rows_error_map(mcpt_ctx* frame, const void* src_dev, long long src_rows, const int* src_row);
+int mcpt_error_map_record(mcpt_ctx* ctx, float threshold, struct mcpt_convergence_t* out);
+int mcpt_error_map_source(mcpt_ctx* ctx, int* source);
 
 /* Select the traversal strategy (mcpt_traversal) for later renders; default AUTO.  AUTO times
  * its schedule candidates on the first launches of >= 2^24 samples after a scene upload — the
@@ -413,11 +463,13 @@ int mcpt_last_denoise_path(mcpt_ctx* ctx, int* lds_mask);
  * mean_r = sum_q / 65536 / n_px.  Needs statistics on and two batches or more (else
  * MCPT_ERR_NO_STATS), positive finite threshold and mu_floor (else MCPT_ERR_INVALID_ARG).
  * Synchronizes.  mcpt_read_error_map: n_local x 2 f32 {se, r} of the window's last
- * mcpt_convergence (MCPT_ERR_NO_STATS without one).  Synchronizes.
+ * mcpt_convergence (MCPT_ERR_NO_STATS without one); on a context with a valid gathered error map
+ * (mcpt_gather_error_map), H x W x 2 f32 of that map.  Synchronizes.
  *
  * mcpt_denoise_guided: mcpt_denoise with the colour term's width taken per pixel from the error
  * map, k_color * se (halved each iteration), in place of sigma_color; mcpt_denoise's preconditions
- * plus an error map of the current window (else MCPT_ERR_NO_STATS).  The map is read as the last
+ * plus an error map (else MCPT_ERR_NO_STATS): the gathered error map when the context holds a valid
+ * one (sharded renders: mcpt_gather_error_map), else the current window's, read as the last
  * mcpt_convergence wrote it.  It writes mcpt_denoise's result buffers: mcpt_read_denoised,
  * mcpt_last_denoise_ms, mcpt_denoise_iteration_ms and mcpt_last_denoise_path serve both filters.
  *
@@ -500,13 +552,15 @@ int mcpt_last_stats_ms(mcpt_ctx* ctx, float* update_ms, float* error_ms);
  * mcpt_denoise_iteration_ms with -1 the resolve step, mcpt_last_denoise_path).  A context without
  * per-pixel counts returns MCPT_ERR_NO_ADAPTIVE.  The guided form needs the error map of the
  * current window (the last mcpt_adaptive_select's), else MCPT_ERR_NO_STATS; on a gathered frame
- * (case b) it always returns MCPT_ERR_NO_STATS.  With no block retired the resolved forms give
+ * (case b) it needs a GATHERED ERROR MAP (below) and returns MCPT_ERR_NO_STATS without one, whatever
+ * window the frame context runs itself.  With no block retired the resolved forms give
  * mcpt_denoise's bits.
  *
  * Both gathers carry the counts: in one process mcpt_gather_rows_counted, across processes
  * (torch.distributed / RCCL, mcpt/dist.py) mcpt_pack_counted_device on every rank and
- * mcpt_load_rows_counted on the receiving one.  Out of scope: the shards' error maps do not travel
- * with either, so the guided filter on a gathered frame returns MCPT_ERR_NO_STATS. */
+ * mcpt_load_rows_counted on the receiving one.  The shards' error maps do not travel with them:
+ * they travel through the separate calls declared after the counted gather's (the gathered error
+ * map), after which the guided filters serve the gathered frame. */
 typedef struct mcpt_adaptive_t {
   long long n_px, n_above;
   unsigned long long sum_q;

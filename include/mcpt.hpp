@@ -582,6 +582,35 @@ class Renderer {
     for (const Renderer* r : shards) h.push_back(r->c_);
     check(mcpt_gather_rows_counted(c_, h.data(), (int)h.size()), "mcpt_gather_rows_counted");
   }
+  // the gathered error map (mcpt.h): after gather_rows / gather_rows_counted, the
+  // shards' error maps (their last convergence() / adaptive_select()) into this full-frame renderer;
+  // denoise_guided / denoise_resolved_guided, read_error_map and error_map_record then serve it
+  void gather_error_map(const std::vector<const Renderer*>& shards) {
+    std::vector<mcpt_ctx*> h;
+    for (const Renderer* r : shards) h.push_back(r->c_);
+    check(mcpt_gather_error_map(c_, h.data(), (int)h.size()), "mcpt_gather_error_map");
+  }
+  // its multi-process ends: local pixels x 8-byte {se, r} records into a device buffer / frame row y
+  // from packed row src_row[y] (H ints, load_rows_counted's index)
+  void pack_error_map_device(void* dst_dev, size_t bytes) {
+    check(mcpt_pack_error_map_device(c_, dst_dev, bytes), "mcpt_pack_error_map_device");
+  }
+  void load_rows_error_map(const void* src_dev, long long src_rows, const std::vector<int>& src_row) {
+    if ((int)src_row.size() != H_) throw std::runtime_error("load_rows_error_map: one source row per frame row");
+    check(mcpt_load_rows_error_map(c_, src_dev, src_rows, src_row.data()), "mcpt_load_rows_error_map");
+  }
+  // convergence()'s record reduced from the stored r values of the map this renderer holds
+  mcpt_convergence_t error_map_record(float threshold) {
+    mcpt_convergence_t rec;
+    check(mcpt_error_map_record(c_, threshold, &rec), "mcpt_error_map_record");
+    return rec;
+  }
+  // 0 no error map, 1 the own window's, 2 the gathered map
+  int error_map_source() const {
+    int s = 0;
+    check(mcpt_error_map_source(c_, &s), "mcpt_error_map_source");
+    return s;
+  }
   void set_traversal(int mode) { check(mcpt_set_traversal(c_, mode), "mcpt_set_traversal"); }
   // render lanes (consecutive launches overlapping each other's tails; same bits): on by default
   void set_render_lanes(bool on) { check(mcpt_set_render_lanes(c_, on ? 1 : 0), "mcpt_set_render_lanes"); }

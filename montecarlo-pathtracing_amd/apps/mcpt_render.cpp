@@ -21,6 +21,8 @@
 //   mcpt_render --scene 6 --spp 4096 --chunk 32 --target-error 0.02 --out s6.png   (stop at 2 % mean relative error)
 //   mcpt_render --scene 6 --spp 4096 --chunk 32 --adaptive --target-error 0.05 --denoise 3 --checkpoint s6.ckpt
 //   mcpt_render --scene 6 --spp 4096 --chunk 32 --adaptive --target-error 0.05 --devices 0,1,2,3 --aov s6
+//   mcpt_render --scene 8 --spp 512 --chunk 32 --devices 0,1,2,3 --denoise-guided 3 --out s8.png   (the shards'
+//       error maps are gathered after the rows, mcpt_gather_error_map, for the noise-guided filter)
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -79,8 +81,10 @@ void usage() {
                "                                   PREFIX_samples.pfm; the image is accum / each pixel's own count;\n"
                "                                   with --devices every shard selects on its own rows; --denoise,\n"
                "                                   --checkpoint and --resume use the per-pixel-count forms)\n"
-               "                   [--denoise-guided [N]]   (one device: the a-trous filter with the colour width\n"
-               "                                             from each pixel's standard error; >= 2 chunks)\n");
+               "                   [--denoise-guided [N]]   (the a-trous filter with the colour width from each\n"
+               "                                             pixel's standard error; >= 2 chunks; with --devices\n"
+               "                                             the shards' error maps are gathered with the rows,\n"
+               "                                             not together with --adaptive)\n");
 }
 
 bool parse(int argc, char** argv, Args& a) {
@@ -144,8 +148,12 @@ bool parse(int argc, char** argv, Args& a) {
     }
   }
   if (!a.devices.empty() && (!a.checkpoint.empty() || !a.resume.empty())) return false;   // one device only
-  // (the frame's statistics: one device; adaptive shards keep their own, whose error maps do not travel)
-  if (!a.devices.empty() && ((a.target_error > 0.0 && !a.adaptive) || a.denoise_guided >= 0)) return false;
+  // (stopping N host threads on a merged record is not built: a uniform --target-error is one device's)
+  if (!a.devices.empty() && a.target_error > 0.0 && !a.adaptive) return false;
+  // (the guided filter on a gathered frame: the uniform shards' error maps travel with
+  // mcpt_gather_error_map; with --adaptive the combination stays refused here, and the library calls
+  // gather_rows_counted + gather_error_map + denoise_resolved_guided serve it)
+  if (!a.devices.empty() && a.adaptive && a.denoise_guided >= 0) return false;
   if (a.denoise >= 0 && a.denoise_guided >= 0) return false;                                // one filter
   if (a.adaptive && !(a.target_error > 0.0)) return false;   // adaptive sampling needs its threshold
   return a.width > 0 && a.height > 0 && a.spp >= 0 && a.chunk > 0 && a.subsampling >= 0 && a.subsampling < 16;
@@ -164,6 +172,10 @@ std::string adaptive_json(double target_error, bool converged, const mcpt_adapti
                 rec.n_px > 0 ? (double)rec.samples / (double)rec.n_px : 0.0);
   return buf;
 }
+
+// the threshold of a convergence query that is made for its error map alone (no --target-error): the
+// map does not depend on it
+constexpr float kMapThreshold = 0.05f;
 
 // --denoise / --aov on the context that holds the whole frame: the guide buffers, the AOV files,
 // and the filtered image in place of the averaged one
@@ -191,8 +203,12 @@ void post_process(const Args& a, mcpt::Renderer& r, const mcpt::Camera& cam, int
     for (size_t i = 0; i < cnt.size(); ++i) smp[3 * i] = smp[3 * i + 1] = smp[3 * i + 2] = (float)cnt[i];
     mcpt::write_pfm(a.aov + "_samples.pfm", smp, W, H);
   }
-  if (r.stats_info().batches >= 2) {   // noise statistics on: the error map (of the final state) and its filter
-    if (!a.adaptive) r.convergence(a.target_error > 0.0 ? (float)a.target_error : 0.05f);   // (adaptive: the last select's map)
+  // noise statistics on: the error map (of the final state) and its filter; a gathered frame
+  // (--devices) holds the shards' maps, which mcpt_gather_error_map delivered
+  const bool gathered_map = r.error_map_source() == 2;
+  if (gathered_map || r.stats_info().batches >= 2) {
+    if (!a.adaptive && !gathered_map)   // (adaptive: the last select's map)
+      r.convergence(a.target_error > 0.0 ? (float)a.target_error : kMapThreshold);
     if (!a.aov.empty()) {
       const std::vector<float> m = r.read_error_map();
       const size_t n = (size_t)W * H;
@@ -371,11 +387,15 @@ int main(int argc, char** argv) {
                 shard_done = shard_rec[(size_t)k].n_active_blocks == 0;
               }
             }
+            // uniform shards with --denoise-guided: a statistics window over the chunks and, after the
+            // last, the shard's error map (fewer than two chunks: MCPT_ERR_NO_STATS, as on one device)
+            if (!a.adaptive && a.denoise_guided >= 0) s.stats_begin();
             for (int done = 0; !a.adaptive && done < a.spp; done += a.chunk) {
               const int n = std::min(a.chunk, a.spp - done);
               s.render(cam, a.first_pass + done, n, a.date, a.bounces, a.ior, a.variant);
               shard_ms[(size_t)k] += s.last_render_ms();   // (synchronizes this shard)
             }
+            if (!a.adaptive && a.denoise_guided >= 0) s.convergence(kMapThreshold);
           } catch (const std::exception& e) {
             errors[(size_t)k] = e.what();
           }
@@ -393,6 +413,7 @@ int main(int argc, char** argv) {
         frame.gather_rows(views);
         img = frame.read_image();
       }
+      if (a.denoise_guided >= 0) frame.gather_error_map(views);   // (after the rows: a row gather invalidates it)
       if (post) post_process(a, frame, cam, W, H, img, guides_ms, filter_ms);
       const auto t2 = std::chrono::steady_clock::now();
       wall_ms = std::chrono::duration<double, std::milli>(t2 - t0).count();

@@ -227,6 +227,18 @@ __global__ __launch_bounds__(256) void load_rows_counted_kernel(const uint4* __r
   }
 }
 
+// load_rows_counted_kernel's twin for the gathered error map: frame row y of the
+// map plane from row src_row[y] of the packed 8-byte records {se, r}, one lane per pixel, the record
+// as one 8-byte integer access each way (se may be inf or NaN: the words are never read as floats)
+__global__ __launch_bounds__(256) void load_rows_error_map_kernel(const uint2* __restrict__ src,
+                                                                  const int* __restrict__ src_row, int W, int H,
+                                                                  uint2* __restrict__ plane) {
+  const int x = blockIdx.x * 256 + threadIdx.x;
+  if (x >= W) return;
+  for (int y = blockIdx.y; y < H; y += gridDim.y)   // (the host checked 0 <= src_row[y] < src_rows)
+    plane[(long long)y * W + x] = src[(long long)src_row[y] * W + x];
+}
+
 __global__ __launch_bounds__(256) void combine_list_kernel(float* __restrict__ accum, const float* __restrict__ partial,
                                                            long long n_px, int n_seg, int W, int n_local_rows,
                                                            int blocks_x, int n_blocks, const int* __restrict__ list,
@@ -328,6 +340,14 @@ hipError_t mcpt_launch_load_rows_counted(const void* src, const int* src_row, in
   if (W <= 0 || H <= 0) return hipSuccess;
   hipLaunchKernelGGL(mcpt::load_rows_counted_kernel, row_grid(W, H), dim3(256), 0, stream,
                      static_cast<const uint4*>(src), src_row, W, H, reinterpret_cast<unsigned*>(accum), plane);
+  return hipGetLastError();
+}
+
+hipError_t mcpt_launch_load_rows_error_map(const void* src, const int* src_row, int W, int H, float2* plane,
+                                           hipStream_t stream) {
+  if (W <= 0 || H <= 0) return hipSuccess;
+  hipLaunchKernelGGL(mcpt::load_rows_error_map_kernel, row_grid(W, H), dim3(256), 0, stream,
+                     static_cast<const uint2*>(src), src_row, W, H, reinterpret_cast<uint2*>(plane));
   return hipGetLastError();
 }
 

@@ -124,8 +124,11 @@ static int denoise_run(mcpt_ctx* c, int iterations, float sigma_color, float sig
   if (!resolved && c->ad_on && c->ad_n_list < c->ad_n_blocks)
     return set_err(MCPT_ERR_INVALID_ARG, "mcpt_denoise: adaptive mode has retired blocks (per-pixel sample counts)");
   if (!c->guides_valid) return set_err(MCPT_ERR_NO_GUIDES, "mcpt_denoise: no guides rendered for this target and scene");
-  // (a gathered frame holds no error map of its pixels: the shards' maps do not travel)
-  if (guided && (!(c->stats_on && c->emap_valid) || (resolved && c->plane_valid)))
+  // the guided forms' map: the gathered plane when it is valid (mcpt_gather_error_map /
+  // mcpt_load_rows_error_map), else the own window's; a frame with gathered counts holds no window
+  // of its pixels, so its own map never serves it
+  const float2* emap = c->emap_plane_valid ? c->d_emap_plane : c->d_emap;
+  if (guided && !c->emap_plane_valid && (!(c->stats_on && c->emap_valid) || (resolved && c->plane_valid)))
     return set_err(MCPT_ERR_NO_STATS, "mcpt_denoise_guided: no error map (mcpt_convergence) of the current statistics");
   HIP_OR_RETURN(hipSetDevice(c->device));
   HIP_OR_RETURN(ensure_denoise_buffers(c));
@@ -151,7 +154,7 @@ static int denoise_run(mcpt_ctx* c, int iterations, float sigma_color, float sig
     // (guided: the kernel forms kc per pixel from sc = k_color * 2^-s and the pixel's se, §3.8)
     const float kc = guided ? sc : 1.0f / (sc * sc), kp = 1.0f / (sp * sp);
     HIP_OR_RETURN(mcpt_launch_atrous(c->d_dn[s & 1], c->d_dn[(s + 1) & 1], c->d_guide, c->W, c->H, step, kc, kp,
-                                     guided ? c->d_emap : nullptr, naive, c->stream));
+                                     guided ? emap : nullptr, naive, c->stream));
     HIP_OR_RETURN(hipEventRecord(c->dn_ev[s + 1], c->stream));
     if (!naive && step <= 2) lds_mask |= 1 << s;
   }
@@ -258,11 +261,12 @@ int mcpt_convergence(mcpt_ctx* c, float threshold, float mu_floor, mcpt_converge
 
 int mcpt_read_error_map(mcpt_ctx* c, float* se_r2) {
   if (!c || !se_r2) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
-  if (!c->stats_on || c->stats_batches < 2 || !c->emap_valid)
+  if (!c->emap_plane_valid && (!c->stats_on || c->stats_batches < 2 || !c->emap_valid))
     return set_err(MCPT_ERR_NO_STATS, "mcpt_read_error_map: no mcpt_convergence of the current statistics");
   HIP_OR_RETURN(hipSetDevice(c->device));
   const size_t n = (size_t)c->n_local_rows * c->W;
-  if (n) HIP_OR_RETURN(hipMemcpyAsync(se_r2, c->d_emap, n * sizeof(float2), hipMemcpyDeviceToHost, c->stream));
+  const float2* emap = c->emap_plane_valid ? c->d_emap_plane : c->d_emap;   // (a gathered frame: its plane)
+  if (n) HIP_OR_RETURN(hipMemcpyAsync(se_r2, emap, n * sizeof(float2), hipMemcpyDeviceToHost, c->stream));
   HIP_OR_RETURN(hipStreamSynchronize(c->stream));
   return MCPT_OK;
 }
@@ -379,7 +383,7 @@ int mcpt_render_adaptive(mcpt_ctx* c, const float* invPV, const float* invV, int
   if (c && args_ok && !c->ad_on)
     return set_err(MCPT_ERR_NO_ADAPTIVE, "mcpt_render_adaptive: adaptive mode is off (mcpt_adaptive_begin)");
   OK_OR_RETURN(check_renderable(c, args_ok, "mcpt_render_adaptive"));
-  c->plane_valid = false;   // (a gathered frame's counts do not describe what is rendered into it)
+  invalidate_planes(c);   // (a gathered frame's counts do not describe what is rendered into it)
   if (c->ad_n_list == 0 || n_passes == 0) return MCPT_OK;   // every block retired: nothing to launch
   HIP_OR_RETURN(hipSetDevice(c->device));
   mcpt::RenderParams p;
@@ -590,21 +594,10 @@ int mcpt_pack_counted_device(mcpt_ctx* c, void* dst, size_t bytes) {
   return MCPT_OK;
 }
 
-int mcpt_load_rows_counted(mcpt_ctx* c, const void* src, long long src_rows, const int* src_row, int pass_count) {
-  if (!c || !src || !src_row || pass_count <= 0 || ((uintptr_t)src & (kPackedBytes - 1)))
-    return set_err(MCPT_ERR_INVALID_ARG, "mcpt_load_rows_counted: bad arguments (16-byte aligned source, pass_count > 0)");
-  if (!c->has_target) return set_err(MCPT_ERR_NO_TARGET, "mcpt_load_rows_counted: frame has no target");
-  if (c->n_local_rows != c->H) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_load_rows_counted: frame target is a shard");
-  for (int i = 0; i < c->H; ++i)
-    if (c->rows[(size_t)i] != i) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_load_rows_counted: frame target is not in row order");
-  for (int y = 0; y < c->H; ++y)
-    if (src_row[y] < 0 || src_row[y] >= src_rows)
-      return set_err(MCPT_ERR_INVALID_ARG, "mcpt_load_rows_counted: a source row lies outside the packed buffer");
-  c->plane_valid = false;   // (the accumulator is replaced)
-  if (c->H == 0 || c->W == 0) return MCPT_OK;
-  HIP_OR_RETURN(hipSetDevice(c->device));
-  const size_t n_px = (size_t)c->H * c->W, index_bytes = (size_t)c->H * sizeof(int);
-  if (!c->d_count_plane) HIP_OR_RETURN(hipMalloc(&c->d_count_plane, n_px * sizeof(int)));
+// the loads' row index (H ints) on the device: uploaded when it differs from the host copy of the
+// previous load's, so mcpt_load_rows_counted and mcpt_load_rows_error_map with one index upload it once
+static int upload_load_index(mcpt_ctx* c, const int* src_row) {
+  const size_t index_bytes = (size_t)c->H * sizeof(int);
   if (!c->d_load_index) {
     HIP_OR_RETURN(hipMalloc(&c->d_load_index, index_bytes));
     c->load_index.clear();
@@ -617,12 +610,106 @@ int mcpt_load_rows_counted(mcpt_ctx* c, const void* src, long long src_rows, con
     const hipError_t e = hipMemcpyAsync(c->d_load_index, c->load_index.data(), index_bytes, hipMemcpyHostToDevice, c->stream);
     if (e != hipSuccess) {
       c->load_index.clear();
-      return set_err(MCPT_ERR_HIP, "mcpt_load_rows_counted: index upload", e);
+      return set_err(MCPT_ERR_HIP, "mcpt_load_rows: index upload", e);
     }
   }
+  return MCPT_OK;
+}
+
+int mcpt_load_rows_counted(mcpt_ctx* c, const void* src, long long src_rows, const int* src_row, int pass_count) {
+  if (!c || !src || !src_row || pass_count <= 0 || ((uintptr_t)src & (kPackedBytes - 1)))
+    return set_err(MCPT_ERR_INVALID_ARG, "mcpt_load_rows_counted: bad arguments (16-byte aligned source, pass_count > 0)");
+  if (!c->has_target) return set_err(MCPT_ERR_NO_TARGET, "mcpt_load_rows_counted: frame has no target");
+  if (c->n_local_rows != c->H) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_load_rows_counted: frame target is a shard");
+  for (int i = 0; i < c->H; ++i)
+    if (c->rows[(size_t)i] != i) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_load_rows_counted: frame target is not in row order");
+  for (int y = 0; y < c->H; ++y)
+    if (src_row[y] < 0 || src_row[y] >= src_rows)
+      return set_err(MCPT_ERR_INVALID_ARG, "mcpt_load_rows_counted: a source row lies outside the packed buffer");
+  invalidate_planes(c);   // (the accumulator is replaced)
+  if (c->H == 0 || c->W == 0) return MCPT_OK;
+  HIP_OR_RETURN(hipSetDevice(c->device));
+  const size_t n_px = (size_t)c->H * c->W;
+  if (!c->d_count_plane) HIP_OR_RETURN(hipMalloc(&c->d_count_plane, n_px * sizeof(int)));
+  OK_OR_RETURN(upload_load_index(c, src_row));
   HIP_OR_RETURN(mcpt_launch_load_rows_counted(src, c->d_load_index, c->W, c->H, c->d_accum, c->d_count_plane, c->stream));
   c->pass_count = pass_count;
   c->plane_valid = true;
+  return MCPT_OK;
+}
+
+// ---- the gathered error map's multi-process ends, its record and its source
+constexpr size_t kMapBytes = sizeof(float2);   // {se, r} per pixel
+
+// the map a context currently holds: 2 the gathered plane, 1 its own window's, 0 none
+static int error_map_source(const mcpt_ctx* c) {
+  return c->emap_plane_valid ? 2 : (c->stats_on && c->emap_valid) ? 1 : 0;
+}
+
+int mcpt_error_map_source(mcpt_ctx* c, int* source) {
+  if (!c || !source) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  *source = error_map_source(c);
+  return MCPT_OK;
+}
+
+int mcpt_pack_error_map_device(mcpt_ctx* c, void* dst, size_t bytes) {
+  if (!c) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  if (!c->has_target) return mcpt_err_bare(MCPT_ERR_NO_TARGET);
+  if (!(c->stats_on && c->emap_valid))
+    return set_err(MCPT_ERR_NO_STATS, "mcpt_pack_error_map_device: no error map of the current statistics window");
+  const size_t need = (size_t)c->n_local_rows * c->W * kMapBytes;
+  if (bytes < need) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_pack_error_map_device: destination smaller than local pixels x 8 bytes");
+  if (need == 0) return MCPT_OK;
+  if (!dst || ((uintptr_t)dst & (kMapBytes - 1)))
+    return set_err(MCPT_ERR_INVALID_ARG, "mcpt_pack_error_map_device: destination must be an 8-byte aligned device pointer");
+  HIP_OR_RETURN(hipSetDevice(c->device));
+  // (the map is contiguous in local row order already: a copy on the stream, behind the select)
+  HIP_OR_RETURN(hipMemcpyAsync(dst, c->d_emap, need, hipMemcpyDeviceToDevice, c->stream));
+  return MCPT_OK;
+}
+
+int mcpt_load_rows_error_map(mcpt_ctx* c, const void* src, long long src_rows, const int* src_row) {
+  if (!c) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  c->emap_plane_valid = false;   // (on any error the frame holds no gathered map)
+  if (!src || !src_row || ((uintptr_t)src & (kMapBytes - 1)))
+    return set_err(MCPT_ERR_INVALID_ARG, "mcpt_load_rows_error_map: bad arguments (8-byte aligned source)");
+  if (!c->has_target) return set_err(MCPT_ERR_NO_TARGET, "mcpt_load_rows_error_map: frame has no target");
+  if (c->n_local_rows != c->H) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_load_rows_error_map: frame target is a shard");
+  for (int i = 0; i < c->H; ++i)
+    if (c->rows[(size_t)i] != i) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_load_rows_error_map: frame target is not in row order");
+  for (int y = 0; y < c->H; ++y)
+    if (src_row[y] < 0 || src_row[y] >= src_rows)
+      return set_err(MCPT_ERR_INVALID_ARG, "mcpt_load_rows_error_map: a source row lies outside the packed buffer");
+  if (c->H == 0 || c->W == 0) return MCPT_OK;
+  HIP_OR_RETURN(hipSetDevice(c->device));
+  if (!c->d_emap_plane) HIP_OR_RETURN(hipMalloc(&c->d_emap_plane, (size_t)c->H * c->W * kMapBytes));
+  OK_OR_RETURN(upload_load_index(c, src_row));
+  HIP_OR_RETURN(mcpt_launch_load_rows_error_map(src, c->d_load_index, c->W, c->H, c->d_emap_plane, c->stream));
+  c->emap_plane_valid = true;
+  return MCPT_OK;
+}
+
+int mcpt_error_map_record(mcpt_ctx* c, float threshold, mcpt_convergence_t* out) {
+  if (!c || !out) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  if (!(threshold > 0.0f) || !std::isfinite(threshold))
+    return set_err(MCPT_ERR_INVALID_ARG, "mcpt_error_map_record: threshold must be positive and finite");
+  const int source = error_map_source(c);
+  if (source == 0) return set_err(MCPT_ERR_NO_STATS, "mcpt_error_map_record: no error map (gathered or of the current statistics)");
+  HIP_OR_RETURN(hipSetDevice(c->device));
+  if (!c->d_emap_rec) HIP_OR_RETURN(hipMalloc(&c->d_emap_rec, sizeof(unsigned long long) * mcpt::kStatsRecWords));
+  const long long n = (long long)c->n_local_rows * c->W;
+  HIP_OR_RETURN(mcpt_launch_error_map_record(source == 2 ? c->d_emap_plane : c->d_emap, n, threshold, c->d_emap_rec,
+                                             c->stream));
+  unsigned long long part[mcpt::kStatsRecWords] = {};
+  HIP_OR_RETURN(hipMemcpyAsync(part, c->d_emap_rec, sizeof(part), hipMemcpyDeviceToHost, c->stream));
+  HIP_OR_RETURN(hipStreamSynchronize(c->stream));
+  unsigned long long h[3] = {0, 0, 0};
+  reduce_stats_records(part, 3, h);
+  fill_frame_record(c, h, out);
+  if (source == 2) {   // (a gathered map belongs to no window of this context)
+    out->passes = c->pass_count;
+    out->batches = 0;
+  }
   return MCPT_OK;
 }
 

@@ -169,6 +169,13 @@ struct mcpt_ctx {
   // host copy kept here
   int* d_load_index = nullptr;
   std::vector<int> load_index;
+  // the gathered error map of a frame (mcpt_gather_error_map, mcpt_load_rows_error_map; DESIGN.md
+  // §3.9.1): H x W x {se, r}, 8 B per pixel, allocated by the first call that fills it after a
+  // mcpt_set_target*, freed with the count plane; valid until the accumulator changes
+  float2* d_emap_plane = nullptr;
+  bool emap_plane_valid = false;
+  // mcpt_error_map_record's partial records (as d_conv; the plane's lifetime)
+  unsigned long long* d_emap_rec = nullptr;
   int next_lane = 0;               // the lane of the next sub-launch
   int prev_lane = -1;               // the lane of the previous sub-launch if it was a lane launch, else -1
 };
@@ -200,10 +207,17 @@ inline void free_adaptive(mcpt_ctx* c) {
 
 inline void free_count_plane(mcpt_ctx* c) {
   (void)hipFree(c->d_count_plane); (void)hipFree(c->d_gather_counts); (void)hipFree(c->d_load_index);
+  (void)hipFree(c->d_emap_plane); (void)hipFree(c->d_emap_rec);
   c->d_count_plane = nullptr; c->d_gather_counts = nullptr; c->d_load_index = nullptr;
+  c->d_emap_plane = nullptr; c->d_emap_rec = nullptr;
   c->load_index.clear();
   c->plane_valid = false;
+  c->emap_plane_valid = false;
 }
+
+// the accumulator changes: what a gather stored about its pixels (the count plane, the gathered
+// error map) no longer describes it
+inline void invalidate_planes(mcpt_ctx* c) { c->plane_valid = false; c->emap_plane_valid = false; }
 
 // a context has per-pixel sample counts: (b) a counted gather filled the count
 // plane, or (a) the adaptive mode is on; the plane describes the accumulator as long as it is valid

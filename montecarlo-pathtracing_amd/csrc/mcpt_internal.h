@@ -243,6 +243,10 @@ constexpr int kStatsRecSlots = 32, kStatsRecStride = 16, kStatsRecWords = kStats
 }
 hipError_t mcpt_launch_stats_error(const float4* state, float2* emap, long long n_px, long long passes, int batches,
                                    float mu_floor, float threshold, unsigned long long* rec, hipStream_t stream);
+// zeroes rec, then reduces a stored map's r values into it as mcpt_launch_stats_error does (the map
+// is only read: a gathered plane or a window's own map)
+hipError_t mcpt_launch_error_map_record(const float2* emap, long long n_px, float threshold, unsigned long long* rec,
+                                        hipStream_t stream);
 hipError_t mcpt_launch_render(const mcpt::RenderParams& p, bool count, hipStream_t stream);
 hipError_t mcpt_launch_combine(const mcpt::RenderParams& p, hipStream_t stream);
 // adaptive sampling of 8x8 blocks (mcpt_adaptive.hip).  Per block an active flag
@@ -292,6 +296,10 @@ hipError_t mcpt_launch_pack_counted(const mcpt::AdaptiveTarget& t, const int* pl
                                     void* out, hipStream_t stream);
 hipError_t mcpt_launch_load_rows_counted(const void* src, const int* src_row, int W, int H, float* accum, int* plane,
                                          hipStream_t stream);
+// the gathered error map's load: frame row y of `plane` (W x H x {se, r}) from row src_row[y] of the
+// 8-byte records at `src` (8-byte aligned), moved as integers
+hipError_t mcpt_launch_load_rows_error_map(const void* src, const int* src_row, int W, int H, float2* plane,
+                                           hipStream_t stream);
 hipError_t mcpt_iota(int* a, int n, hipStream_t stream);
 hipError_t mcpt_split_count(const unsigned* cost_sorted, int n, int capacity, int split_max, int* out,
                             unsigned long long* dbg, hipStream_t stream);

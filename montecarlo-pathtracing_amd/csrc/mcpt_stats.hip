@@ -54,29 +54,13 @@ __global__ __launch_bounds__(256) void stats_update_kernel(const float* __restri
 
 constexpr int kErrorMaxBlocks = 2048;   // 8 workgroups per CU of a 256-CU chip
 
-// rec: kStatsRecSlots partial records of kStatsRecStride words, workgroup b adds into slot
-// b % kStatsRecSlots: [0] n_above, [1] sum_q (64-bit adds), [2] max_r's bits (a 32-bit max on the
-// word's low half)
-__global__ __launch_bounds__(256) void error_kernel(const float4* __restrict__ st, float2* __restrict__ emap,
-                                                    long long n_px, float nf, float bm1f, float mu_floor,
-                                                    float threshold, unsigned long long* __restrict__ rec) {
+// A workgroup's share of the frame record from its lanes' sums: wave shuffles, one LDS step, one
+// set of atomics into slot blockIdx.x % kStatsRecSlots.  Idle lanes (past the frame's end) hold the
+// sums' neutral elements and take part in the shuffles.  Every lane of the workgroup calls it.
+__device__ __forceinline__ void reduce_record(unsigned long long above, unsigned long long qsum, unsigned rmax,
+                                              unsigned long long* __restrict__ rec) {
   __shared__ unsigned long long s_above[4], s_q[4];
   __shared__ unsigned s_max[4];
-  // a lane's sums over its grid steps (q <= 2^22 per pixel, up to 2^31 / (2048 x 256) pixels per
-  // lane once the grid cap binds): 64-bit from the start
-  unsigned long long above = 0, qsum = 0;
-  unsigned rmax = 0;
-  const long long stride = (long long)gridDim.x * 256;
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n_px; i += stride) {
-    const float2 e = pixel_error(st[i], nf, bm1f, mu_floor);   // {se, r} (mcpt_stats_err.h)
-    const float r = e.y;
-    emap[i] = e;
-    above += (r > threshold) ? 1u : 0u;
-    qsum += error_q(r);
-    const unsigned rb = __float_as_uint(r);   // r >= 0: the bits order as the values
-    rmax = rb > rmax ? rb : rmax;
-  }
-  // idle lanes (past the frame's end) hold the sums' neutral elements and take part in the shuffles
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {
     above += __shfl_down(above, off, 64);
@@ -106,6 +90,47 @@ __global__ __launch_bounds__(256) void error_kernel(const float4* __restrict__ s
   }
 }
 
+// rec: kStatsRecSlots partial records of kStatsRecStride words, workgroup b adds into slot
+// b % kStatsRecSlots: [0] n_above, [1] sum_q (64-bit adds), [2] max_r's bits (a 32-bit max on the
+// word's low half)
+__global__ __launch_bounds__(256) void error_kernel(const float4* __restrict__ st, float2* __restrict__ emap,
+                                                    long long n_px, float nf, float bm1f, float mu_floor,
+                                                    float threshold, unsigned long long* __restrict__ rec) {
+  // a lane's sums over its grid steps (q <= 2^22 per pixel, up to 2^31 / (2048 x 256) pixels per
+  // lane once the grid cap binds): 64-bit from the start
+  unsigned long long above = 0, qsum = 0;
+  unsigned rmax = 0;
+  const long long stride = (long long)gridDim.x * 256;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n_px; i += stride) {
+    const float2 e = pixel_error(st[i], nf, bm1f, mu_floor);   // {se, r} (mcpt_stats_err.h)
+    const float r = e.y;
+    emap[i] = e;
+    above += (r > threshold) ? 1u : 0u;
+    qsum += error_q(r);
+    const unsigned rb = __float_as_uint(r);   // r >= 0: the bits order as the values
+    rmax = rb > rmax ? rb : rmax;
+  }
+  reduce_record(above, qsum, rmax, rec);
+}
+
+// The frame record of a STORED error map (mcpt_error_map_record): error_kernel's
+// reduction over the map's r values as they are (a gathered plane, or a window's own map); neither
+// se nor r is recomputed, and the map is only read.  8 B per pixel of traffic.
+__global__ __launch_bounds__(256) void error_map_record_kernel(const float2* __restrict__ emap, long long n_px,
+                                                               float threshold, unsigned long long* __restrict__ rec) {
+  unsigned long long above = 0, qsum = 0;
+  unsigned rmax = 0;
+  const long long stride = (long long)gridDim.x * 256;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n_px; i += stride) {
+    const float r = emap[i].y;   // 0 <= r <= 64 as pixel_error wrote it
+    above += (r > threshold) ? 1u : 0u;
+    qsum += error_q(r);
+    const unsigned rb = __float_as_uint(r);
+    rmax = rb > rmax ? rb : rmax;
+  }
+  reduce_record(above, qsum, rmax, rec);
+}
+
 }  // namespace mcpt
 
 hipError_t mcpt_launch_stats_begin(const float* accum, float4* state, long long n_px, hipStream_t stream) {
@@ -129,5 +154,15 @@ hipError_t mcpt_launch_stats_error(const float4* state, float2* emap, long long 
   const long long blocks = (n_px + 255) / 256;
   hipLaunchKernelGGL(mcpt::error_kernel, dim3((unsigned)std::min<long long>(blocks, mcpt::kErrorMaxBlocks)), dim3(256),
                      0, stream, state, emap, n_px, (float)passes, (float)(batches - 1), mu_floor, threshold, rec);
+  return hipGetLastError();
+}
+
+hipError_t mcpt_launch_error_map_record(const float2* emap, long long n_px, float threshold, unsigned long long* rec,
+                                        hipStream_t stream) {
+  hipError_t e = hipMemsetAsync(rec, 0, sizeof(unsigned long long) * mcpt::kStatsRecWords, stream);
+  if (e != hipSuccess || n_px <= 0) return e;
+  const long long blocks = (n_px + 255) / 256;
+  hipLaunchKernelGGL(mcpt::error_map_record_kernel, dim3((unsigned)std::min<long long>(blocks, mcpt::kErrorMaxBlocks)),
+                     dim3(256), 0, stream, emap, n_px, threshold, rec);
   return hipGetLastError();
 }

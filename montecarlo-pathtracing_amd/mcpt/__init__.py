@@ -214,6 +214,11 @@ def _declare(L: ctypes.CDLL) -> None:
         "mcpt_pass_count": (i, [_vp, ip]),
         "mcpt_pack_counted_device": (i, [_vp, _vp, ctypes.c_size_t]),
         "mcpt_load_rows_counted": (i, [_vp, _vp, ctypes.c_longlong, ip, i]),
+        "mcpt_gather_error_map": (i, [_vp, ctypes.POINTER(_vp), i]),
+        "mcpt_pack_error_map_device": (i, [_vp, _vp, ctypes.c_size_t]),
+        "mcpt_load_rows_error_map": (i, [_vp, _vp, ctypes.c_longlong, ip]),
+        "mcpt_error_map_record": (i, [_vp, f, ctypes.POINTER(Convergence)]),
+        "mcpt_error_map_source": (i, [_vp, ip]),
         "mcpt_adaptive_checkpoint_save": (i, [_vp, ctypes.c_char_p, i, ctypes.c_char_p]),
         "mcpt_adaptive_checkpoint_load": (i, [_vp, ctypes.c_char_p, ctypes.c_char_p, ip]),
         "mcpt_adaptive_checkpoint_write": (i, [ctypes.c_char_p, ctypes.POINTER(AdaptiveCheckpoint), ctypes.c_char_p, ip,
@@ -795,7 +800,8 @@ class Renderer:
 
     def read_error_map(self) -> np.ndarray:
         """(local rows, W, 2) f32: {standard error of the mean luminance, relative error r} of the
-        last convergence()."""
+        last convergence() / adaptive_select(); on a frame with a gathered error map
+        (gather_error_map, load_rows_error_map) that map, (H, W, 2)."""
         out = np.zeros((self.n_local_rows, self.W, 2), np.float32)
         _check(lib().mcpt_read_error_map(self._h, _fp(out)), "mcpt_read_error_map")
         return out
@@ -999,6 +1005,44 @@ class Renderer:
             raise MCPTError(f"load_rows_counted: expected {self.H} source rows, got {idx.shape}")
         _check(lib().mcpt_load_rows_counted(self._h, _vp(src_ptr), int(src_rows), _ip(idx), int(pass_count)),
                "mcpt_load_rows_counted")
+
+    # ---- the gathered error map: the guided filters on sharded renders (mcpt.h)
+    def gather_error_map(self, shards) -> None:
+        """mcpt_gather_error_map: this full-frame renderer's gathered error map <- the shard
+        renderers' maps (their last convergence() / adaptive_select()), after gather_rows() or
+        gather_rows_counted(); denoise_guided / denoise_resolved_guided, read_error_map and
+        error_map_record then serve the frame.  Every frame row must come from exactly one shard."""
+        hs = (_vp * max(len(shards), 1))(*[s._h for s in shards])
+        _check(lib().mcpt_gather_error_map(self._h, hs, len(shards)), "mcpt_gather_error_map")
+
+    def pack_error_map_device(self, dst_ptr: int, nbytes: int) -> None:
+        """mcpt_pack_error_map_device: the local pixels' 8-byte {se, r} records into a device buffer
+        (an int32 torch tensor: the words travel as bits), on our stream after the queued work."""
+        _check(lib().mcpt_pack_error_map_device(self._h, _vp(dst_ptr), ctypes.c_size_t(nbytes)),
+               "mcpt_pack_error_map_device")
+
+    def load_rows_error_map(self, src_ptr: int, src_rows: int, src_row) -> None:
+        """mcpt_load_rows_error_map: this full-frame renderer's gathered error map <- packed map rows
+        on its device, frame row y from packed row src_row[y] (load_rows_counted's index; after the
+        load of the rows themselves).  Asynchronous."""
+        idx = np.ascontiguousarray(src_row, dtype=np.int32)
+        if idx.shape != (self.H,):
+            raise MCPTError(f"load_rows_error_map: expected {self.H} source rows, got {idx.shape}")
+        _check(lib().mcpt_load_rows_error_map(self._h, _vp(src_ptr), int(src_rows), _ip(idx)),
+               "mcpt_load_rows_error_map")
+
+    def error_map_record(self, threshold: float) -> dict:
+        """mcpt_error_map_record: convergence()'s record reduced from the stored r values of the map
+        this renderer holds (the gathered map, else its own window's).  Synchronizes."""
+        rec = Convergence()
+        _check(lib().mcpt_error_map_record(self._h, float(threshold), ctypes.byref(rec)), "mcpt_error_map_record")
+        return {k: getattr(rec, k) for k, _ in Convergence._fields_}
+
+    def error_map_source(self) -> int:
+        """mcpt_error_map_source: 0 no error map, 1 the own window's, 2 the gathered map."""
+        s = ctypes.c_int()
+        _check(lib().mcpt_error_map_source(self._h, ctypes.byref(s)), "mcpt_error_map_source")
+        return s.value
 
     def trace(self, origins, dirs, any_hit: bool = False, prim: int = -1) -> np.ndarray:
         """Ray queries (traverse_all_bvh / just_hit_bvh, or one primitive) + intersection_info.

@@ -17,7 +17,10 @@ Adaptive renders: ShardedRenderer passes the statistics and 
 its shard, merges the shards' select records over the process group (merge_adaptive_records) and
 gathers the frame WITH its per-pixel sample counts (gather_counted: 16 B/px int32 records, one
 gather, one load kernel into a full-frame context on rank 0; tests/test_dist_counted_gloo.py,
-tests/test_gpu_dist_adaptive.py).
+tests/test_gpu_dist_adaptive.py).  With ``error_map=True`` both gathers also move the shards' error maps
+(8 B/px int32 records through a second FrameGather, mcpt_load_rows_error_map on rank 0), so that the
+noise-guided filters serve the gathered frame; ShardedRenderer.convergence merges the uniform shards'
+records (tests/test_emap_gather_host.py, tests/test_gpu_emap_gather.py).
 """
 from __future__ import annotations
 
@@ -158,18 +161,15 @@ def _f32_bits(x: float) -> int:
     return int(np.array([x], np.float32).view(np.uint32)[0])
 
 
-def merge_adaptive_records(local: dict, group=None, device: Optional[torch.device] = None) -> dict:
-    """The frame's adaptive_select record from every rank's shard record: the integer fields of
-    RECORD_SUMS add, those of RECORD_MAXES and max_r take the largest, and mean_r is recomputed
-    as sum_q / 65536 / n_px (mcpt_adaptive_select's arithmetic).  One all-gather of nine int64 words
-    per rank (max_r travels as its bit pattern: r >= 0, so the bits order as the values), reduced
-    with Python integers: exact, a sum_q past 2^53 included.  Every rank returns the merged record,
-    with its own under "local".  `device`: where the collective's tensors live (default: the host
-    for gloo, else the current cuda device); needs no GPU over gloo."""
-    keys = RECORD_SUMS + RECORD_MAXES
+def _merge_records(local: dict, sums, maxes, group=None, device: Optional[torch.device] = None) -> dict:
+    """One all-gather of the record's integer fields plus max_r's bit pattern (r >= 0, so the bits
+    order as the values) as int64 words per rank, reduced with Python integers: exact, a sum_q past
+    2^53 included.  The fields of `sums` add, those of `maxes` and max_r take the largest, mean_r is
+    recomputed as sum_q / 65536 / n_px."""
+    keys = tuple(sums) + tuple(maxes)
     words = [int(local[k]) for k in keys] + [_f32_bits(local["max_r"])]
     if not all(0 <= w < 2 ** 63 for w in words):
-        raise ValueError(f"merge_adaptive_records: a field does not fit int64: {local}")
+        raise ValueError(f"merge of shard records: a field does not fit int64: {local}")
     world = dist.get_world_size(group)
     if dist.get_backend(group) == "gloo":
         device = torch.device("cpu")
@@ -182,11 +182,31 @@ def merge_adaptive_records(local: dict, group=None, device: Optional[torch.devic
     out = {}
     for j, k in enumerate(keys):
         col = [r[j] for r in rows]
-        out[k] = sum(col) if k in RECORD_SUMS else max(col)
+        out[k] = sum(col) if k in sums else max(col)
     out["max_r"] = float(np.array([max(r[-1] for r in rows)], np.uint32).view(np.float32)[0])
     out["mean_r"] = out["sum_q"] / 65536.0 / out["n_px"] if out["n_px"] > 0 else 0.0
     out["local"] = dict(local)
     return out
+
+
+def merge_adaptive_records(local: dict, group=None, device: Optional[torch.device] = None) -> dict:
+    """The frame's adaptive_select record from every rank's shard record: the integer fields of
+    RECORD_SUMS add, those of RECORD_MAXES and max_r take the largest, and mean_r is recomputed
+    as sum_q / 65536 / n_px (mcpt_adaptive_select's arithmetic).  One all-gather of nine int64 words
+    per rank (max_r travels as its bit pattern: r >= 0, so the bits order as the values), reduced
+    with Python integers: exact, a sum_q past 2^53 included.  Every rank returns the merged record,
+    with its own under "local".  `device`: where the collective's tensors live (default: the host
+    for gloo, else the current cuda device); needs no GPU over gloo."""
+    return _merge_records(local, RECORD_SUMS, RECORD_MAXES, group, device)
+
+
+CONVERGENCE_SUMS = ("n_px", "n_above", "sum_q")
+
+
+def merge_convergence_records(local: dict, group=None, device: Optional[torch.device] = None) -> dict:
+    """merge_adaptive_records for the smaller record of mcpt_convergence (uniform shards): n_px,
+    n_above and sum_q add, passes, batches and max_r take the largest, mean_r is recomputed."""
+    return _merge_records(local, CONVERGENCE_SUMS, RECORD_MAXES, group, device)
 
 
 class ShardedRenderer:
@@ -217,6 +237,7 @@ class ShardedRenderer:
         self.partition, self.local_rank, self.group, self.force_collective = partition, local_rank, group, force_collective
         self.scene = None
         self.gc = None            # the counted gather's buffers and frame context: made on first use
+        self.gm = None            # the error map's gather buffers: made on first use
         self.frame_r = None
         self.g = FrameGather(H, W, band_rows, world, rank, self.device, group=group, partition=partition,
                              force_collective=force_collective)
@@ -232,7 +253,7 @@ class ShardedRenderer:
     def render(self, invPV, invV, first_pass, n_passes, date=0.0, bounces=3, refract_ind=1.0, variant=0):
         self.r.render(invPV, invV, first_pass, n_passes, date, bounces, refract_ind, variant)
 
-    def gather(self) -> Optional[torch.Tensor]:
+    def gather(self, error_map: bool = False):
         """Copy the local accumulator into the send buffer and gather the frame to rank 0, both
         on `self.stream` after the queued renders; the caller's current stream is then made to
         wait for it, so the returned frame is safe to use there.
@@ -242,7 +263,16 @@ class ShardedRenderer:
         after everything the caller has queued on its current stream by then (the private
         stream waits for it first), so work the caller queued that reads the previous frame
         completes before the buffer changes; keep a copy (``frame.clone()``) to hold a frame
-        across gathers."""
+        across gathers.
+
+        ``error_map=True`` (a uniform render with statistics on, after convergence()): the frame is
+        delivered into a full-frame mcpt.Renderer on rank 0 together with the shards' error maps, as
+        gather_counted(error_map=True) does, and that renderer is returned in place of a tensor
+        (None on other ranks).  The rows travel as packed records whose count is the pass count for
+        every pixel, so its denoise_resolved_guided gives accum / pass_count filtered with the
+        gathered map: denoise_guided's bits on one context."""
+        if error_map:
+            return self.gather_counted(error_map=True)
         n = self.g.n_local
         caller = torch.cuda.current_stream(self.device)
         self.stream.wait_stream(caller)   # the caller's reads of the previous frame come first
@@ -257,6 +287,16 @@ class ShardedRenderer:
     # frame's record merged over the group, and the counted gather
     def stats_begin(self) -> None:
         self.r.stats_begin()
+
+    def convergence(self, threshold: float, mu_floor: Optional[float] = None) -> dict:
+        """The uniform counterpart of adaptive_select: the local mcpt_convergence (which writes the
+        shard's error map), then the shards' records merged over the process group
+        (merge_convergence_records): the frame's record on every rank, this rank's under "local"."""
+        import mcpt
+        local = self.r.convergence(threshold, mcpt.ERROR_MU_FLOOR if mu_floor is None else mu_floor)
+        if self.world == 1 and not self.force_collective:
+            return dict(local, local=dict(local))
+        return merge_convergence_records(local, self.group, self.device)
 
     def adaptive_begin(self, min_passes: int = 0) -> None:
         self.r.adaptive_begin(min_passes)
@@ -320,7 +360,7 @@ class ShardedRenderer:
             if self.scene is not None:
                 self.frame_r.upload_scene(self.scene)
 
-    def gather_counted(self):
+    def gather_counted(self, error_map: bool = False):
         """gather() for an adaptive render: the frame WITH its per-pixel sample counts.  Every rank
         packs its rows into 16 B/px records {r, g, b bits, int32 count} (mcpt_pack_counted_device;
         with the adaptive mode off the count is the pass count), one gather moves them to rank 0 as
@@ -335,9 +375,19 @@ class ShardedRenderer:
         not belong in a timed loop of launches; gather() stays free of host waits.
 
         Stream discipline as gather(): the private stream first waits for the caller's current
-        stream, pack, collective and load run on it, and the caller's stream then waits for it."""
+        stream, pack, collective and load run on it, and the caller's stream then waits for it.
+
+        ``error_map=True``: every rank also packs its error map (the last adaptive_select's or
+        convergence()'s; mcpt_pack_error_map_device, 8 B/px {se, r} carried as two int32 words) into
+        a second FrameGather, the same collective moves it, and rank 0 loads it behind the rows with
+        the same row index (mcpt_load_rows_error_map: the index is uploaded once for the pair).  The
+        returned renderer then serves denoise_resolved_guided, read_error_map and error_map_record."""
         if self.gc is None:
             self._counted_setup()
+        if error_map and self.gm is None:
+            self.gm = FrameGather(self.H, self.W, self.band_rows, self.world, self.rank, self.device, group=self.group,
+                                  partition=self.partition, force_collective=self.force_collective, channels=2,
+                                  dtype=torch.int32, assemble=False)
         g, n = self.gc, self.gc.n_local
         most = self.r.pass_count()
         caller = torch.cuda.current_stream(self.device)
@@ -358,6 +408,12 @@ class ShardedRenderer:
                         most = int(self.most.item())   # the one host read
             if raw is not None:
                 self.frame_r.load_rows_counted(raw.data_ptr(), raw.shape[0], self.src_row, most)
+            if error_map:
+                if n:
+                    self.r.pack_error_map_device(self.gm.send.data_ptr(), n * self.W * 8)
+                raw_map = self.gm.gather_raw(None)
+                if raw_map is not None:
+                    self.frame_r.load_rows_error_map(raw_map.data_ptr(), raw_map.shape[0], self.src_row)
         caller.wait_stream(self.stream)
         return self.frame_r if raw is not None else None
 

@@ -17,6 +17,14 @@
     block arrays and from the count plane of a counted gather separately.  Byte floor: 12 B read and
     16 B written per pixel, plus 8 B per block or 4 B per pixel for the counts.
     `--only e` measures (e) alone and keeps the other sections of an existing --out file.
+(f) the gathered error map, scene 6 at 1080p, eight balanced uniform shards and the
+    frame on one GPU and one stream, HIP events around the calls, medians of 20 after 3 warm-ups,
+    interleaved: the counted gather alone (mcpt_gather_rows_counted: 16 B/px moved), the map gather
+    after it (mcpt_gather_error_map: 8 B/px), the multi-process form's ends for the rows
+    (mcpt_pack_counted_device x 8 + mcpt_load_rows_counted) and for the map
+    (mcpt_pack_error_map_device x 8 + mcpt_load_rows_error_map), and mcpt_error_map_record on the
+    gathered map beside mcpt_convergence's error kernel (mcpt_last_stats_ms) on a full-frame context.
+    `--only f` likewise.
 Medians of `reps` runs after warm-ups; the spread is (max - min) / median."""
 import argparse
 import json
@@ -224,29 +232,120 @@ def bench_resolve(r, reps=20, warm=3):
     return out
 
 
+def bench_emap_gather(reps=20, warm=3, W=1920, H=1080, n_shards=8):
+    import ctypes
+    ts = torch.cuda.Stream()
+    made = []
+
+    def uniform(rows):
+        r = mcpt.Renderer(0)
+        made.append(r)
+        r.set_stream(ts.cuda_stream)
+        r.upload_scene(mcpt.Scene.reference(6))
+        if rows is None:
+            r.set_target(W, H)
+        else:
+            r.set_target_rows(W, H, rows)
+        cam = mcpt.camera_canonical(W, H)
+        r.stats_begin()
+        for first in (1, 5):
+            r.render(cam[0], cam[1], first, 4, 0.0, 4)
+        r.convergence(0.05)
+        return r
+
+    def balanced(k):
+        rows, n = np.zeros(H, np.int32), ctypes.c_int()
+        assert mcpt.lib().mcpt_balanced_rows(H, n_shards, k, 8, mcpt._ip(rows), ctypes.byref(n)) == 0
+        return rows[:n.value].tolist()
+
+    def timed(fn):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record(ts)
+        fn()
+        b.record(ts)
+        b.synchronize()
+        return a.elapsed_time(b)
+
+    try:
+        row_sets = [balanced(k) for k in range(n_shards)]
+        shards = [uniform(rows) for rows in row_sets]
+        full = uniform(None)
+        frame = mcpt.Renderer(0)
+        made.append(frame)
+        frame.set_stream(ts.cuda_stream)
+        frame.set_target(W, H)
+        m = max(len(rows) for rows in row_sets)
+        src = np.zeros(H, np.int32)
+        for k, rows in enumerate(row_sets):
+            src[np.asarray(rows)] = k * m + np.arange(len(rows))
+        with torch.cuda.stream(ts):
+            rows_buf = torch.zeros((n_shards * m, W, 4), dtype=torch.int32, device="cuda:0")
+            map_buf = torch.zeros((n_shards * m, W, 2), dtype=torch.int32, device="cuda:0")
+        ts.synchronize()
+
+        def pack_load_rows():
+            for k, s in enumerate(shards):
+                s.pack_counted_device(rows_buf[k * m].data_ptr(), s.n_local_rows * W * 16)
+            frame.load_rows_counted(rows_buf.data_ptr(), rows_buf.shape[0], src, 8)
+
+        def pack_load_map():
+            for k, s in enumerate(shards):
+                s.pack_error_map_device(map_buf[k * m].data_ptr(), s.n_local_rows * W * 8)
+            frame.load_rows_error_map(map_buf.data_ptr(), map_buf.shape[0], src)
+
+        series = {k: [] for k in ("gather_rows_counted_ms", "gather_error_map_ms", "pack_load_rows_ms", "pack_load_map_ms",
+                                  "error_map_record_ms", "convergence_call_ms", "convergence_error_kernel_ms")}
+        for k in range(reps + warm):
+            row = {"gather_rows_counted_ms": timed(lambda: frame.gather_rows_counted(shards)),
+                   "gather_error_map_ms": timed(lambda: frame.gather_error_map(shards)),
+                   "error_map_record_ms": timed(lambda: frame.error_map_record(0.05)),
+                   "pack_load_rows_ms": timed(pack_load_rows),
+                   "pack_load_map_ms": timed(pack_load_map),
+                   "convergence_call_ms": timed(lambda: full.convergence(0.05))}
+            row["convergence_error_kernel_ms"] = full.last_stats_ms()[1]
+            if k >= warm:
+                for name, v in row.items():
+                    series[name].append(v)
+        same = bool(np.array_equal(frame.read_error_map().view(np.uint32), full.read_error_map().view(np.uint32)))
+        out = {"W": W, "H": H, "n_shards": n_shards, "reps": reps, "map_equals_full_frame": same,
+               "bytes_moved": {"rows_counted": W * H * 16, "map": W * H * 8}}
+        out.update({name: med(v) for name, v in series.items()})
+        out["map_over_counted_gather"] = out["gather_error_map_ms"]["median"] / out["gather_rows_counted_ms"]["median"]
+        out["map_over_rows_pack_load"] = out["pack_load_map_ms"]["median"] / out["pack_load_rows_ms"]["median"]
+        out["record_over_convergence_call"] = out["error_map_record_ms"]["median"] / out["convergence_call_ms"]["median"]
+        print(json.dumps(out), flush=True)
+        return out
+    finally:
+        for r in made:
+            r.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "adaptive_bench.json"))
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--thresholds", default="0.2,0.1,0.05")
-    ap.add_argument("--only", default="", help="e: measure section (e) alone, keep the rest of --out")
+    ap.add_argument("--only", default="", help="e / f: measure section (e) / (f) alone, keep the rest of --out")
     a = ap.parse_args()
     r = mcpt.Renderer(0)
     try:
-        if a.only == "e":
+        if a.only == "f":
+            res = json.load(open(a.out)) if os.path.exists(a.out) else {"device": torch.cuda.get_device_name(0)}
+            res["emap_gather"] = bench_emap_gather()
+        elif a.only == "e":
             res = json.load(open(a.out)) if os.path.exists(a.out) else {"device": torch.cuda.get_device_name(0)}
             res["resolve"] = bench_resolve(r)
         else:
             res = {"device": torch.cuda.get_device_name(0), "reps": a.reps,
                    "select": bench_select(r, a.reps), "list_path": bench_list_path(r, a.reps),
                    "point": bench_point(r, [float(x) for x in a.thresholds.split(",")]),
-                   "resolve": bench_resolve(r)}
+                   "resolve": bench_resolve(r), "emap_gather": bench_emap_gather()}
     finally:
         r.close()
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(res, f, indent=1)
-    print(json.dumps({k: res[k] for k in ("select", "list_path", "resolve") if k in res}, indent=1))
+    print(json.dumps({k: res[k] for k in ("select", "list_path", "resolve", "emap_gather") if k in res}, indent=1))
 
 
 if __name__ == "__main__":

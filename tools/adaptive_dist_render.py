@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
 """An adaptive render over N processes, one per GPU, gathered WITH its per-pixel sample counts
 (DESIGN.md §3.9.1): ShardedRenderer.render_adaptive_until on every rank, gather_counted() to rank 0,
-which writes PREFIX.png (the resolved image, or the filtered one with --denoise N) and
+which writes PREFIX.png (the resolved image, or the filtered one with --denoise N or, with
+--denoise-guided N, the noise-guided filter over the shards' gathered error maps) and
 PREFIX_samples.pfm (every pixel's sample count in all three channels, as mcpt_render --aov does).
 
     python tools/adaptive_dist_render.py --gpus 8 --scene 6 --width 1920 --height 1080 \\
-        --spp 1024 --chunk 32 --target-error 0.05 [--denoise 3] --out frame
+        --spp 1024 --chunk 32 --target-error 0.05 [--denoise 3 | --denoise-guided 3] --out frame
     python -m torch.distributed.run --nproc-per-node 8 tools/adaptive_dist_render.py --gpus 8 ...
 
 Without a launcher (WORLD_SIZE unset) the tool starts its own --gpus N ranks, as
@@ -38,12 +39,17 @@ def parse():
     ap.add_argument("--min-passes", type=int, default=0)
     ap.add_argument("--bounces", type=int, default=3)
     ap.add_argument("--denoise", type=int, default=0, help="a-trous iterations over the resolved image (0: none)")
+    ap.add_argument("--denoise-guided", type=int, default=0,
+                    help="noise-guided a-trous iterations over the resolved image, the colour width from the "
+                         "shards' error maps, which travel with the gather (0: none)")
     ap.add_argument("--out", default="adaptive_dist", help="output prefix")
     ap.add_argument("--backend", choices=("auto", "nccl", "gloo"), default="auto")
     ap.add_argument("--timeout", type=float, default=300.0, help="seconds each child rank may run")
     a = ap.parse_args()
     if a.gpus < 1 or a.spp < 1 or a.chunk < 1 or not a.target_error > 0 or not 0 <= a.denoise <= 8:
         ap.error("--gpus, --spp, --chunk must be >= 1, --target-error > 0, --denoise in 0..8")
+    if not 0 <= a.denoise_guided <= 8 or (a.denoise and a.denoise_guided):
+        ap.error("--denoise-guided in 0..8, and one filter only")
     return a
 
 
@@ -113,10 +119,13 @@ def rank_main(a) -> int:
         t0 = time.perf_counter()
         rec = sr.render_adaptive_until(ipv, iv, a.target_error, batch=a.chunk, max_passes=a.spp,
                                        min_passes=a.min_passes, bounces=a.bounces)
-        frame = sr.gather_counted()
+        frame = sr.gather_counted(error_map=a.denoise_guided > 0)
         if frame is not None:
             counts = frame.read_sample_counts()
-            if a.denoise > 0:
+            if a.denoise_guided > 0:
+                frame.render_guides(ipv, iv)
+                img = frame.denoise_resolved_guided(a.denoise_guided)
+            elif a.denoise > 0:
                 frame.render_guides(ipv, iv)
                 img = frame.denoise_resolved(a.denoise)
             else:
@@ -126,7 +135,7 @@ def rank_main(a) -> int:
             mcpt.write_pfm(a.out + "_samples.pfm", np.repeat(counts.astype(np.float32)[..., None], 3, axis=2))
             rec.pop("local")
             print(json.dumps(dict(rec, scene=a.scene, W=W, H=H, n_gpus=world, backend=backend if world > 1 else None,
-                                  denoise=a.denoise, mean_spp=rec["samples"] / rec["n_px"], wall_s=wall,
+                                  denoise=a.denoise, denoise_guided=a.denoise_guided, mean_spp=rec["samples"] / rec["n_px"], wall_s=wall,
                                   png=a.out + ".png", samples=int(counts.sum()))), flush=True)
     finally:
         if sr is not None:
