@@ -17,8 +17,9 @@
 //  * combine_list_kernel: one wave per listed block adds the block's segment sums to the
 //    accumulator in chunk order (combine_kernel's sequence per pixel); unlisted pixels' segment
 //    slots are unwritten and are not read.
-//  * add_passes / counts / resolve: the per-block pass counts, the per-pixel sample counts p0 +
-//    passes[block], and accum / (float)count per channel (mcpt_average's single division).
+//  * add_passes / counts / resolve: the per-block pass counts, the per-pixel sample counts from the
+//    context's count source (count_at, mcpt_internal.h: the count plane, p0 + passes[block] or the
+//    pass count), and accum / (float)count per channel (mcpt_average's single division).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -150,46 +151,30 @@ __global__ __launch_bounds__(256) void add_passes_kernel(int* __restrict__ passe
   if (b >= 0 && b < n_blocks) passes[b] += add;
 }
 
-__device__ __forceinline__ int pixel_count(const AdaptiveTarget& t, long long i) {
-  const int lr = (int)(i / t.W), x = (int)(i - (long long)lr * t.W);
-  return t.p0 + t.passes[(lr >> 3) * t.blocks_x + (x >> 3)];
-}
-
-__global__ __launch_bounds__(256) void counts_kernel(AdaptiveTarget t, int* __restrict__ counts, long long n_px) {
+__global__ __launch_bounds__(256) void counts_kernel(CountSource src, int* __restrict__ counts, long long n_px) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i >= n_px) return;
-  counts[i] = pixel_count(t, i);
+  counts[i] = count_at(src, i);
 }
 
-__global__ __launch_bounds__(256) void resolve_kernel(AdaptiveTarget t, const float* __restrict__ accum,
+__global__ __launch_bounds__(256) void resolve_kernel(CountSource src, const float* __restrict__ accum,
                                                       float* __restrict__ out, long long n_px) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i >= n_px) return;
-  const float nb = (float)pixel_count(t, i);
+  const float nb = (float)count_at(src, i);
   out[3 * i] = accum[3 * i] / nb; out[3 * i + 1] = accum[3 * i + 1] / nb; out[3 * i + 2] = accum[3 * i + 2] / nb;
 }
 
 // The filter's first input from a frame with per-pixel counts (average4_kernel's twin, DESIGN.md
 // §3.9): accum / (float)count per channel as float4 (rgb, 0), one lane per pixel, one 16-byte store.
-// The count comes from the count plane of a counted gather (plane non-null: 4 B per pixel) or from
-// the block arrays (4 B per block, 64 lanes of a row run share at most ceil(64 / 8) + 1 words).
-__global__ __launch_bounds__(256) void resolve4_kernel(AdaptiveTarget t, const int* __restrict__ plane,
-                                                       const float* __restrict__ accum, float4* __restrict__ out,
-                                                       long long n_px) {
+// The count comes from the count plane of a counted gather (4 B per pixel) or from the block arrays
+// (4 B per block, 64 lanes of a row run share at most ceil(64 / 8) + 1 words): count_at.
+__global__ __launch_bounds__(256) void resolve4_kernel(CountSource src, const float* __restrict__ accum,
+                                                       float4* __restrict__ out, long long n_px) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i >= n_px) return;
-  const float nb = (float)(plane ? plane[i] : pixel_count(t, i));
+  const float nb = (float)count_at(src, i);
   out[i] = make_float4(accum[3 * i] / nb, accum[3 * i + 1] / nb, accum[3 * i + 2] / nb, 0.0f);
-}
-
-// mcpt_read_resolved of a gathered frame: resolve_kernel with the count plane's counts
-__global__ __launch_bounds__(256) void resolve_plane_kernel(const int* __restrict__ plane,
-                                                            const float* __restrict__ accum, float* __restrict__ out,
-                                                            long long n_px) {
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n_px) return;
-  const float nb = (float)plane[i];
-  out[3 * i] = accum[3 * i] / nb; out[3 * i + 1] = accum[3 * i + 1] / nb; out[3 * i + 2] = accum[3 * i + 2] / nb;
 }
 
 // The multi-process counted gather's two ends.  A packed record is 16 bytes per
@@ -197,19 +182,17 @@ __global__ __launch_bounds__(256) void resolve_plane_kernel(const int* __restric
 // count.  Both kernels move words, never floats (an overflowed sum's inf / NaN payload and a count's
 // denormal bit pattern pass through), one lane per pixel, a workgroup per 256 columns of a row, the
 // 16-byte side as one vector access per lane.
-//  * pack_counted_kernel: the shard's rows in local order.  The count is the count plane's (plane
-//    non-null), else p0 + the block's passes (t.passes non-null: the adaptive mode), else `uniform`.
+//  * pack_counted_kernel: the shard's rows in local order, every pixel's count from count_at.
 //  * load_rows_counted_kernel: frame row y from packed row src_row[y]; the sums to accum, the counts
 //    to the plane (the row scatter and the split in one pass).
-__global__ __launch_bounds__(256) void pack_counted_kernel(AdaptiveTarget t, const int* __restrict__ plane,
-                                                           int uniform, const unsigned* __restrict__ accum,
+__global__ __launch_bounds__(256) void pack_counted_kernel(CountSource src, int n_rows,
+                                                           const unsigned* __restrict__ accum,
                                                            uint4* __restrict__ out) {
   const int x = blockIdx.x * 256 + threadIdx.x;
-  if (x >= t.W) return;
-  for (int lr = blockIdx.y; lr < t.n_local_rows; lr += gridDim.y) {
-    const long long i = (long long)lr * t.W + x;
-    const int n = plane ? plane[i] : t.passes ? t.p0 + t.passes[(lr >> 3) * t.blocks_x + (x >> 3)] : uniform;
-    out[i] = make_uint4(accum[3 * i], accum[3 * i + 1], accum[3 * i + 2], (unsigned)n);
+  if (x >= src.W) return;
+  for (int lr = blockIdx.y; lr < n_rows; lr += gridDim.y) {
+    const long long i = (long long)lr * src.W + x;
+    out[i] = make_uint4(accum[3 * i], accum[3 * i + 1], accum[3 * i + 2], (unsigned)count_at(src, i));
   }
 }
 
@@ -294,43 +277,33 @@ hipError_t mcpt_launch_adaptive_add_passes(const mcpt::AdaptiveTarget& t, const 
   return hipGetLastError();
 }
 
-hipError_t mcpt_launch_adaptive_counts(const mcpt::AdaptiveTarget& t, int* counts, hipStream_t stream) {
-  const long long n = (long long)t.n_local_rows * t.W;
-  if (n <= 0) return hipSuccess;
-  hipLaunchKernelGGL(mcpt::counts_kernel, dim3(grid256(n)), dim3(256), 0, stream, t, counts, n);
-  return hipGetLastError();
-}
-
-hipError_t mcpt_launch_adaptive_resolve(const mcpt::AdaptiveTarget& t, const float* accum, float* out,
-                                        hipStream_t stream) {
-  const long long n = (long long)t.n_local_rows * t.W;
-  if (n <= 0) return hipSuccess;
-  hipLaunchKernelGGL(mcpt::resolve_kernel, dim3(grid256(n)), dim3(256), 0, stream, t, accum, out, n);
-  return hipGetLastError();
-}
-
-hipError_t mcpt_launch_resolve4(const mcpt::AdaptiveTarget& t, const int* plane, const float* accum, float4* out,
-                                hipStream_t stream) {
-  const long long n = (long long)t.n_local_rows * t.W;
-  if (n <= 0) return hipSuccess;
-  hipLaunchKernelGGL(mcpt::resolve4_kernel, dim3(grid256(n)), dim3(256), 0, stream, t, plane, accum, out, n);
-  return hipGetLastError();
-}
-
-hipError_t mcpt_launch_resolve_plane(const int* plane, const float* accum, float* out, long long n_px,
-                                     hipStream_t stream) {
+hipError_t mcpt_launch_counts(const mcpt::CountSource& src, int* counts, long long n_px, hipStream_t stream) {
   if (n_px <= 0) return hipSuccess;
-  hipLaunchKernelGGL(mcpt::resolve_plane_kernel, dim3(grid256(n_px)), dim3(256), 0, stream, plane, accum, out, n_px);
+  hipLaunchKernelGGL(mcpt::counts_kernel, dim3(grid256(n_px)), dim3(256), 0, stream, src, counts, n_px);
+  return hipGetLastError();
+}
+
+hipError_t mcpt_launch_resolve(const mcpt::CountSource& src, const float* accum, float* out, long long n_px,
+                               hipStream_t stream) {
+  if (n_px <= 0) return hipSuccess;
+  hipLaunchKernelGGL(mcpt::resolve_kernel, dim3(grid256(n_px)), dim3(256), 0, stream, src, accum, out, n_px);
+  return hipGetLastError();
+}
+
+hipError_t mcpt_launch_resolve4(const mcpt::CountSource& src, const float* accum, float4* out, long long n_px,
+                                hipStream_t stream) {
+  if (n_px <= 0) return hipSuccess;
+  hipLaunchKernelGGL(mcpt::resolve4_kernel, dim3(grid256(n_px)), dim3(256), 0, stream, src, accum, out, n_px);
   return hipGetLastError();
 }
 
 // a workgroup per 256 columns of a row; rows past the grid's y limit are stepped over
 static dim3 row_grid(int W, int rows) { return dim3(grid256(W), (unsigned)std::min(rows, 65535)); }
 
-hipError_t mcpt_launch_pack_counted(const mcpt::AdaptiveTarget& t, const int* plane, int uniform, const float* accum,
-                                    void* out, hipStream_t stream) {
-  if (t.W <= 0 || t.n_local_rows <= 0) return hipSuccess;
-  hipLaunchKernelGGL(mcpt::pack_counted_kernel, row_grid(t.W, t.n_local_rows), dim3(256), 0, stream, t, plane, uniform,
+hipError_t mcpt_launch_pack_counted(const mcpt::CountSource& src, int n_rows, const float* accum, void* out,
+                                    hipStream_t stream) {
+  if (src.W <= 0 || n_rows <= 0) return hipSuccess;
+  hipLaunchKernelGGL(mcpt::pack_counted_kernel, row_grid(src.W, n_rows), dim3(256), 0, stream, src, n_rows,
                      reinterpret_cast<const unsigned*>(accum), static_cast<uint4*>(out));
   return hipGetLastError();
 }

@@ -1,5 +1,6 @@
 // mcpt_capi.hip — C ABI, device half: context, scene upload (repack to device records),
-// framebuffer / row-band sharding, render launches, accumulator read-back.
+// framebuffer / row-band sharding, render launches, accumulator read-back.  (What runs on a
+// rendered accumulator: mcpt_capi_post.hip; what moves a shard into a frame: mcpt_capi_gather.hip.)
 //
 // Replaces the GL state of the reference's render path: Texture2D uploads
 // (bvh_gpu/gpu_bvh_scene.cpp:143-160), the RGB32F FBO + blend (MontecarloGPU/montecarlo.cpp:
@@ -1243,205 +1244,6 @@ int mcpt_accum_device_ptr(mcpt_ctx* c, void** dev_ptr, size_t* bytes) {
   if (bytes) *bytes = c->accum_bytes;
   return MCPT_OK;
 }
-
-int mcpt_copy_accum_device(mcpt_ctx* c, void* dst, size_t bytes) {
-  if (!c || (!dst && bytes)) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
-  if (!c->has_target) return mcpt_err_bare(MCPT_ERR_NO_TARGET);
-  if (bytes < c->accum_bytes) return set_err(MCPT_ERR_INVALID_ARG, "destination smaller than the accumulator");
-  HIP_OR_RETURN(hipSetDevice(c->device));
-  if (c->accum_bytes)
-    HIP_OR_RETURN(hipMemcpyAsync(dst, c->d_accum, c->accum_bytes, hipMemcpyDeviceToDevice, c->stream));
-  return MCPT_OK;
-}
-
-namespace {
-// the gathers' guards: the calling thread's current device is restored on every return path
-struct DeviceGuard {
-  int prev = -1;
-  DeviceGuard() { if (hipGetDevice(&prev) != hipSuccess) prev = -1; }
-  ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-// an event created in a gather is destroyed on every return path (it is released by HIP once the
-// waits recorded against it have been satisfied)
-struct EventGuard {
-  hipEvent_t e = nullptr;
-  ~EventGuard() { if (e) (void)hipEventDestroy(e); }
-};
-// direct xGMI reads/writes between a frame's device and a shard's (once per process)
-int enable_peer_access(const mcpt_ctx* frame, const mcpt_ctx* s) {
-  if (s->device == frame->device) return MCPT_OK;
-  int ok = 0;
-  HIP_OR_RETURN(hipDeviceCanAccessPeer(&ok, frame->device, s->device));
-  if (ok) {
-    HIP_OR_RETURN(hipSetDevice(frame->device));
-    const hipError_t e = hipDeviceEnablePeerAccess(s->device, 0);
-    if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) return set_err(MCPT_ERR_HIP, "hipDeviceEnablePeerAccess", e);
-    (void)hipGetLastError();
-  }
-  return MCPT_OK;
-}
-}  // namespace
-
-// mcpt_gather_rows (counted false: equal pass counts, no counts carried) and
-// mcpt_gather_rows_counted (counted true: each shard's per-pixel counts travel with its rows into
-// frame's count plane; every frame row from exactly one shard)
-static int gather_rows(mcpt_ctx* frame, mcpt_ctx* const* shards, int n_shards, bool counted) {
-  if (!frame || n_shards < 0 || (n_shards > 0 && !shards)) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_gather_rows: bad arguments");
-  if (!frame->has_target) return set_err(MCPT_ERR_NO_TARGET, "mcpt_gather_rows: frame has no target");
-  if (frame->n_local_rows != frame->H) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_gather_rows: frame target is a shard");
-  for (int k = 0; k < n_shards; ++k) {
-    const mcpt_ctx* s = shards[k];
-    if (!s || s == frame) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_gather_rows: bad shard context");
-    if (!s->has_target) return set_err(MCPT_ERR_NO_TARGET, "mcpt_gather_rows: shard has no target");
-    if (s->W != frame->W || s->H != frame->H) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_gather_rows: shard size differs");
-    if (!counted && s->pass_count != shards[0]->pass_count)
-      return set_err(MCPT_ERR_INVALID_ARG, "mcpt_gather_rows: shards hold different pass counts");
-  }
-  if (counted) {
-    // a condition, so that no pixel is left with count 0
-    bool in_order = true;
-    for (int i = 0; in_order && i < frame->n_local_rows; ++i) in_order = frame->rows[(size_t)i] == i;
-    if (!in_order) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_gather_rows_counted: frame target is not in row order");
-    std::vector<int> held((size_t)frame->H, 0);
-    for (int k = 0; k < n_shards; ++k)
-      for (int y : shards[k]->rows) ++held[(size_t)y];
-    for (int y = 0; y < frame->H; ++y)
-      if (held[(size_t)y] != 1)
-        return set_err(MCPT_ERR_INVALID_ARG, "mcpt_gather_rows_counted: every frame row must be held by exactly one shard");
-  }
-  invalidate_planes(frame);   // (the accumulator is replaced: a plain gather carries no counts)
-  DeviceGuard device_guard;
-  const size_t row_bytes = (size_t)frame->W * 3 * sizeof(float);
-  const size_t row_counts = (size_t)frame->W * sizeof(int);
-  if (counted && !frame->d_count_plane) {
-    HIP_OR_RETURN(hipSetDevice(frame->device));
-    HIP_OR_RETURN(hipMalloc(&frame->d_count_plane, (size_t)frame->H * row_counts));
-  }
-  for (int k = 0; k < n_shards; ++k) {
-    mcpt_ctx* s = shards[k];
-    OK_OR_RETURN(enable_peer_access(frame, s));
-    HIP_OR_RETURN(hipSetDevice(s->device));
-    if (counted && s->n_local_rows > 0) {
-      // the shard's own counts on its stream (which waited for the previous gather's copies of
-      // this buffer): the blocks' counts with the adaptive mode on, else its pass count
-      const size_t n_px = (size_t)s->n_local_rows * s->W;
-      if (!s->d_gather_counts) HIP_OR_RETURN(hipMalloc(&s->d_gather_counts, n_px * sizeof(int)));
-      if (s->plane_valid)
-        HIP_OR_RETURN(hipMemcpyAsync(s->d_gather_counts, s->d_count_plane, n_px * sizeof(int), hipMemcpyDeviceToDevice, s->stream));
-      else if (s->ad_on)
-        HIP_OR_RETURN(mcpt_launch_adaptive_counts(adaptive_target(s), s->d_gather_counts, s->stream));
-      else
-        HIP_OR_RETURN(hipMemsetD32Async((hipDeviceptr_t)s->d_gather_counts, s->pass_count, n_px, s->stream));
-    }
-    // (1) the frame's stream waits for the shard's queued work (its renders and combines)
-    EventGuard done;
-    HIP_OR_RETURN(hipEventCreateWithFlags(&done.e, hipEventDisableTiming));
-    HIP_OR_RETURN(hipEventRecord(done.e, s->stream));
-    HIP_OR_RETURN(hipSetDevice(frame->device));
-    HIP_OR_RETURN(hipStreamWaitEvent(frame->stream, done.e, 0));
-    hipError_t e = hipSuccess;
-    for (int i = 0; e == hipSuccess && i < s->n_local_rows;) {
-      int j = i + 1;   // run of consecutive global rows: one contiguous copy
-      while (j < s->n_local_rows && s->rows[(size_t)j] == s->rows[(size_t)j - 1] + 1) ++j;
-      e = hipMemcpyPeerAsync((char*)frame->d_accum + (size_t)s->rows[(size_t)i] * row_bytes, frame->device,
-                             (const char*)s->d_accum + (size_t)i * row_bytes, s->device, (size_t)(j - i) * row_bytes,
-                             frame->stream);
-      if (counted && e == hipSuccess)
-        e = hipMemcpyPeerAsync((char*)frame->d_count_plane + (size_t)s->rows[(size_t)i] * row_counts, frame->device,
-                               (const char*)s->d_gather_counts + (size_t)i * row_counts, s->device,
-                               (size_t)(j - i) * row_counts, frame->stream);
-      i = j;
-    }
-    if (e != hipSuccess) return set_err(MCPT_ERR_HIP, "mcpt_gather_rows: peer copy", e);
-    // (2) the shard's later work (a progressive caller's next render adds into d_accum in
-    // place) waits for the copies that read its accumulator
-    EventGuard copied;
-    HIP_OR_RETURN(hipEventCreateWithFlags(&copied.e, hipEventDisableTiming));
-    HIP_OR_RETURN(hipEventRecord(copied.e, frame->stream));
-    HIP_OR_RETURN(hipSetDevice(s->device));
-    HIP_OR_RETURN(hipStreamWaitEvent(s->stream, copied.e, 0));
-  }
-  if (!counted) {
-    if (n_shards > 0) frame->pass_count = shards[0]->pass_count;
-    return MCPT_OK;
-  }
-  int most = 0;
-  for (int k = 0; k < n_shards; ++k) most = std::max(most, shards[k]->pass_count);
-  frame->pass_count = most;
-  frame->plane_valid = true;
-  return MCPT_OK;
-}
-
-int mcpt_gather_rows(mcpt_ctx* frame, mcpt_ctx* const* shards, int n_shards) {
-  return gather_rows(frame, shards, n_shards, false);
-}
-
-int mcpt_gather_rows_counted(mcpt_ctx* frame, mcpt_ctx* const* shards, int n_shards) {
-  return gather_rows(frame, shards, n_shards, true);
-}
-
-// The shards' error maps into the frame's gathered map plane: gather_rows' peer
-// copies, stream ordering and device / event restore for the 8-byte {se, r} records.  The rows were
-// gathered before (a row gather invalidates the plane); on any error the plane is left invalid.
-int mcpt_gather_error_map(mcpt_ctx* frame, mcpt_ctx* const* shards, int n_shards) {
-  if (!frame || n_shards < 0 || (n_shards > 0 && !shards)) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_gather_error_map: bad arguments");
-  frame->emap_plane_valid = false;
-  if (!frame->has_target) return set_err(MCPT_ERR_NO_TARGET, "mcpt_gather_error_map: frame has no target");
-  if (frame->n_local_rows != frame->H) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_gather_error_map: frame target is a shard");
-  for (int i = 0; i < frame->H; ++i)
-    if (frame->rows[(size_t)i] != i) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_gather_error_map: frame target is not in row order");
-  std::vector<int> held((size_t)frame->H, 0);
-  for (int k = 0; k < n_shards; ++k) {
-    const mcpt_ctx* s = shards[k];
-    if (!s || s == frame) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_gather_error_map: bad shard context");
-    if (!s->has_target) return set_err(MCPT_ERR_NO_TARGET, "mcpt_gather_error_map: shard has no target");
-    if (s->W != frame->W || s->H != frame->H) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_gather_error_map: shard size differs");
-    for (int y : s->rows) ++held[(size_t)y];
-  }
-  for (int y = 0; y < frame->H; ++y)
-    if (held[(size_t)y] != 1)
-      return set_err(MCPT_ERR_INVALID_ARG, "mcpt_gather_error_map: every frame row must be held by exactly one shard");
-  for (int k = 0; k < n_shards; ++k)
-    if (!(shards[k]->stats_on && shards[k]->emap_valid))
-      return set_err(MCPT_ERR_NO_STATS, "mcpt_gather_error_map: a shard holds no error map of its current statistics window");
-  DeviceGuard device_guard;
-  const size_t row_bytes = (size_t)frame->W * sizeof(float2);
-  if (!frame->d_emap_plane && frame->H > 0 && frame->W > 0) {
-    HIP_OR_RETURN(hipSetDevice(frame->device));
-    HIP_OR_RETURN(hipMalloc(&frame->d_emap_plane, (size_t)frame->H * row_bytes));
-  }
-  for (int k = 0; k < n_shards; ++k) {
-    mcpt_ctx* s = shards[k];
-    OK_OR_RETURN(enable_peer_access(frame, s));
-    // (1) the frame's stream waits for the shard's queued work (the kernel that wrote its map)
-    HIP_OR_RETURN(hipSetDevice(s->device));
-    EventGuard done;
-    HIP_OR_RETURN(hipEventCreateWithFlags(&done.e, hipEventDisableTiming));
-    HIP_OR_RETURN(hipEventRecord(done.e, s->stream));
-    HIP_OR_RETURN(hipSetDevice(frame->device));
-    HIP_OR_RETURN(hipStreamWaitEvent(frame->stream, done.e, 0));
-    hipError_t e = hipSuccess;
-    for (int i = 0; e == hipSuccess && i < s->n_local_rows;) {
-      int j = i + 1;   // run of consecutive global rows: one contiguous copy
-      while (j < s->n_local_rows && s->rows[(size_t)j] == s->rows[(size_t)j - 1] + 1) ++j;
-      e = hipMemcpyPeerAsync((char*)frame->d_emap_plane + (size_t)s->rows[(size_t)i] * row_bytes, frame->device,
-                             (const char*)s->d_emap + (size_t)i * row_bytes, s->device, (size_t)(j - i) * row_bytes,
-                             frame->stream);
-      i = j;
-    }
-    if (e != hipSuccess) return set_err(MCPT_ERR_HIP, "mcpt_gather_error_map: peer copy", e);
-    // (2) the shard's later work (its next select rewrites the map in place) waits for the copies
-    EventGuard copied;
-    HIP_OR_RETURN(hipEventCreateWithFlags(&copied.e, hipEventDisableTiming));
-    HIP_OR_RETURN(hipEventRecord(copied.e, frame->stream));
-    HIP_OR_RETURN(hipSetDevice(s->device));
-    HIP_OR_RETURN(hipStreamWaitEvent(s->stream, copied.e, 0));
-  }
-  frame->emap_plane_valid = true;
-  return MCPT_OK;
-}
-
-
 
 int mcpt_trace(mcpt_ctx* c, const float* origins, const float* dirs, int n, int any_hit, int prim, mcpt_hit* out) {
   if (!c || n < 0 || (n > 0 && (!origins || !dirs || !out))) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_trace: bad arguments");

@@ -1,8 +1,8 @@
 // mcpt_capi_post.hip — C ABI, device half: what runs on a rendered accumulator (guide buffers and
-// the à-trous denoiser, noise statistics and the convergence metric, adaptive sampling).
+// the à-trous denoiser, noise statistics and the convergence metric, adaptive sampling, the held
+// error map's record).  The gathers that fill a frame's planes are mcpt_capi_gather.hip's.
 #include <algorithm>
 #include <cmath>
-#include <cstdint>
 #include <cstring>
 
 #include "mcpt_ctx.h"
@@ -117,18 +117,18 @@ static int denoise_run(mcpt_ctx* c, int iterations, float sigma_color, float sig
   if (!c->has_target) return set_err(MCPT_ERR_NO_TARGET, "no render target");
   if (resolved && !has_pixel_counts(c))
     return set_err(MCPT_ERR_NO_ADAPTIVE, "mcpt_denoise_resolved: no per-pixel sample counts (adaptive mode off, no counted gather)");
-  bool full = c->n_local_rows == c->H;
-  for (int i = 0; full && i < c->n_local_rows; ++i) full = c->rows[(size_t)i] == i;
-  if (!full) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_denoise: needs a full-frame target (gather the shards first)");
+  if (!plan::is_full_frame(c->rows, c->H))
+    return set_err(MCPT_ERR_INVALID_ARG, "mcpt_denoise: needs a full-frame target (gather the shards first)");
   if (c->pass_count <= 0) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_denoise: the accumulator holds no passes");
   if (!resolved && c->ad_on && c->ad_n_list < c->ad_n_blocks)
     return set_err(MCPT_ERR_INVALID_ARG, "mcpt_denoise: adaptive mode has retired blocks (per-pixel sample counts)");
   if (!c->guides_valid) return set_err(MCPT_ERR_NO_GUIDES, "mcpt_denoise: no guides rendered for this target and scene");
-  // the guided forms' map: the gathered plane when it is valid (mcpt_gather_error_map /
-  // mcpt_load_rows_error_map), else the own window's; a frame with gathered counts holds no window
-  // of its pixels, so its own map never serves it
-  const float2* emap = c->emap_plane_valid ? c->d_emap_plane : c->d_emap;
-  if (guided && !c->emap_plane_valid && (!(c->stats_on && c->emap_valid) || (resolved && c->plane_valid)))
+  // the guided forms' map: the one the context holds (the gathered plane, else the own window's);
+  // a frame with gathered counts holds no window of its pixels, so its own map never serves the
+  // resolved form of it
+  const float2* emap = held_error_map(c);
+  const int source = error_map_source(c);
+  if (guided && (source == 0 || (resolved && c->plane_valid && source != 2)))
     return set_err(MCPT_ERR_NO_STATS, "mcpt_denoise_guided: no error map (mcpt_convergence) of the current statistics");
   HIP_OR_RETURN(hipSetDevice(c->device));
   HIP_OR_RETURN(ensure_denoise_buffers(c));
@@ -141,8 +141,7 @@ static int denoise_run(mcpt_ctx* c, int iterations, float sigma_color, float sig
   // (the context's stream is ordered after all queued renders: their combines run on it)
   HIP_OR_RETURN(hipEventRecord(c->dn_ev[9], c->stream));
   if (resolved)
-    HIP_OR_RETURN(mcpt_launch_resolve4(adaptive_target(c), c->plane_valid ? c->d_count_plane : nullptr, c->d_accum,
-                                       c->d_dn[0], c->stream));
+    HIP_OR_RETURN(mcpt_launch_resolve4(count_source(c), c->d_accum, c->d_dn[0], n, c->stream));
   else
     HIP_OR_RETURN(mcpt_launch_average4(c->d_accum, c->d_dn[0], n, c->pass_count, c->stream));
   HIP_OR_RETURN(hipEventRecord(c->dn_ev[0], c->stream));
@@ -261,12 +260,12 @@ int mcpt_convergence(mcpt_ctx* c, float threshold, float mu_floor, mcpt_converge
 
 int mcpt_read_error_map(mcpt_ctx* c, float* se_r2) {
   if (!c || !se_r2) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
-  if (!c->emap_plane_valid && (!c->stats_on || c->stats_batches < 2 || !c->emap_valid))
+  const int source = error_map_source(c);
+  if (source == 0 || (source == 1 && c->stats_batches < 2))
     return set_err(MCPT_ERR_NO_STATS, "mcpt_read_error_map: no mcpt_convergence of the current statistics");
   HIP_OR_RETURN(hipSetDevice(c->device));
   const size_t n = (size_t)c->n_local_rows * c->W;
-  const float2* emap = c->emap_plane_valid ? c->d_emap_plane : c->d_emap;   // (a gathered frame: its plane)
-  if (n) HIP_OR_RETURN(hipMemcpyAsync(se_r2, emap, n * sizeof(float2), hipMemcpyDeviceToHost, c->stream));
+  if (n) HIP_OR_RETURN(hipMemcpyAsync(se_r2, held_error_map(c), n * sizeof(float2), hipMemcpyDeviceToHost, c->stream));
   HIP_OR_RETURN(hipStreamSynchronize(c->stream));
   return MCPT_OK;
 }
@@ -437,15 +436,10 @@ int mcpt_read_sample_counts(mcpt_ctx* c, int* counts) {
   if (!has_pixel_counts(c)) return set_err(MCPT_ERR_NO_ADAPTIVE, "mcpt_read_sample_counts: adaptive mode is off (mcpt_adaptive_begin)");
   HIP_OR_RETURN(hipSetDevice(c->device));
   const size_t n = (size_t)c->n_local_rows * c->W;
-  if (c->plane_valid) {   // a gathered frame: the count plane itself
-    if (n) HIP_OR_RETURN(hipMemcpyAsync(counts, c->d_count_plane, n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIP_OR_RETURN(hipStreamSynchronize(c->stream));
-    return MCPT_OK;
-  }
   if (n) {
     int* d = nullptr;
     HIP_OR_RETURN(hipMalloc(&d, n * sizeof(int)));
-    hipError_t e = mcpt_launch_adaptive_counts(adaptive_target(c), d, c->stream);
+    hipError_t e = mcpt_launch_counts(count_source(c), d, (long long)n, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(counts, d, n * sizeof(int), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     (void)hipFree(d);
@@ -462,8 +456,7 @@ int mcpt_read_resolved(mcpt_ctx* c, float* rgb) {
   if (n) {
     float* d = nullptr;
     HIP_OR_RETURN(hipMalloc(&d, n * 3 * sizeof(float)));
-    hipError_t e = c->plane_valid ? mcpt_launch_resolve_plane(c->d_count_plane, c->d_accum, d, (long long)n, c->stream)
-                                  : mcpt_launch_adaptive_resolve(adaptive_target(c), c->d_accum, d, c->stream);
+    hipError_t e = mcpt_launch_resolve(count_source(c), c->d_accum, d, (long long)n, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(rgb, d, n * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     (void)hipFree(d);
@@ -566,126 +559,10 @@ int mcpt_last_adaptive_ms(mcpt_ctx* c, float* select_ms, float* render_ms) {
   return pair_ms(c->ad_render_timed, c->ad_ev[2], c->ad_ev[3], render_ms);
 }
 
-// ---- the multi-process counted gather's two ends (the collective between them is
-// the caller's: mcpt/dist.py)
-int mcpt_pass_count(mcpt_ctx* c, int* pass_count) {
-  if (!c || !pass_count) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
-  if (!c->has_target) return mcpt_err_bare(MCPT_ERR_NO_TARGET);
-  *pass_count = c->pass_count;
-  return MCPT_OK;
-}
-
-constexpr size_t kPackedBytes = 16;   // {r, g, b, count} per pixel
-
-int mcpt_pack_counted_device(mcpt_ctx* c, void* dst, size_t bytes) {
-  if (!c) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
-  if (!c->has_target) return mcpt_err_bare(MCPT_ERR_NO_TARGET);
-  const size_t need = (size_t)c->n_local_rows * c->W * kPackedBytes;
-  if (bytes < need) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_pack_counted_device: destination smaller than local pixels x 16 bytes");
-  if (need == 0) return MCPT_OK;
-  if (!dst || ((uintptr_t)dst & (kPackedBytes - 1)))
-    return set_err(MCPT_ERR_INVALID_ARG, "mcpt_pack_counted_device: destination must be a 16-byte aligned device pointer");
-  HIP_OR_RETURN(hipSetDevice(c->device));
-  // the count's source as the in-process counted gather picks it: the plane, the blocks, the pass count
-  mcpt::AdaptiveTarget t = adaptive_target(c);
-  if (!c->ad_on) { t.passes = nullptr; t.flags = nullptr; }
-  HIP_OR_RETURN(mcpt_launch_pack_counted(t, c->plane_valid ? c->d_count_plane : nullptr, c->pass_count, c->d_accum, dst,
-                                         c->stream));
-  return MCPT_OK;
-}
-
-// the loads' row index (H ints) on the device: uploaded when it differs from the host copy of the
-// previous load's, so mcpt_load_rows_counted and mcpt_load_rows_error_map with one index upload it once
-static int upload_load_index(mcpt_ctx* c, const int* src_row) {
-  const size_t index_bytes = (size_t)c->H * sizeof(int);
-  if (!c->d_load_index) {
-    HIP_OR_RETURN(hipMalloc(&c->d_load_index, index_bytes));
-    c->load_index.clear();
-  }
-  if (c->load_index.size() != (size_t)c->H || std::memcmp(c->load_index.data(), src_row, index_bytes) != 0) {
-    // on the stream after the loads that read the previous index; a queued upload of the previous
-    // index may still read the host copy, so replacing one waits for it (a first upload does not)
-    if (!c->load_index.empty()) HIP_OR_RETURN(hipStreamSynchronize(c->stream));
-    c->load_index.assign(src_row, src_row + c->H);
-    const hipError_t e = hipMemcpyAsync(c->d_load_index, c->load_index.data(), index_bytes, hipMemcpyHostToDevice, c->stream);
-    if (e != hipSuccess) {
-      c->load_index.clear();
-      return set_err(MCPT_ERR_HIP, "mcpt_load_rows: index upload", e);
-    }
-  }
-  return MCPT_OK;
-}
-
-int mcpt_load_rows_counted(mcpt_ctx* c, const void* src, long long src_rows, const int* src_row, int pass_count) {
-  if (!c || !src || !src_row || pass_count <= 0 || ((uintptr_t)src & (kPackedBytes - 1)))
-    return set_err(MCPT_ERR_INVALID_ARG, "mcpt_load_rows_counted: bad arguments (16-byte aligned source, pass_count > 0)");
-  if (!c->has_target) return set_err(MCPT_ERR_NO_TARGET, "mcpt_load_rows_counted: frame has no target");
-  if (c->n_local_rows != c->H) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_load_rows_counted: frame target is a shard");
-  for (int i = 0; i < c->H; ++i)
-    if (c->rows[(size_t)i] != i) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_load_rows_counted: frame target is not in row order");
-  for (int y = 0; y < c->H; ++y)
-    if (src_row[y] < 0 || src_row[y] >= src_rows)
-      return set_err(MCPT_ERR_INVALID_ARG, "mcpt_load_rows_counted: a source row lies outside the packed buffer");
-  invalidate_planes(c);   // (the accumulator is replaced)
-  if (c->H == 0 || c->W == 0) return MCPT_OK;
-  HIP_OR_RETURN(hipSetDevice(c->device));
-  const size_t n_px = (size_t)c->H * c->W;
-  if (!c->d_count_plane) HIP_OR_RETURN(hipMalloc(&c->d_count_plane, n_px * sizeof(int)));
-  OK_OR_RETURN(upload_load_index(c, src_row));
-  HIP_OR_RETURN(mcpt_launch_load_rows_counted(src, c->d_load_index, c->W, c->H, c->d_accum, c->d_count_plane, c->stream));
-  c->pass_count = pass_count;
-  c->plane_valid = true;
-  return MCPT_OK;
-}
-
-// ---- the gathered error map's multi-process ends, its record and its source
-constexpr size_t kMapBytes = sizeof(float2);   // {se, r} per pixel
-
-// the map a context currently holds: 2 the gathered plane, 1 its own window's, 0 none
-static int error_map_source(const mcpt_ctx* c) {
-  return c->emap_plane_valid ? 2 : (c->stats_on && c->emap_valid) ? 1 : 0;
-}
-
+// ---- the held error map's source and record (mcpt_ctx.h: held_error_map)
 int mcpt_error_map_source(mcpt_ctx* c, int* source) {
   if (!c || !source) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
   *source = error_map_source(c);
-  return MCPT_OK;
-}
-
-int mcpt_pack_error_map_device(mcpt_ctx* c, void* dst, size_t bytes) {
-  if (!c) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
-  if (!c->has_target) return mcpt_err_bare(MCPT_ERR_NO_TARGET);
-  if (!(c->stats_on && c->emap_valid))
-    return set_err(MCPT_ERR_NO_STATS, "mcpt_pack_error_map_device: no error map of the current statistics window");
-  const size_t need = (size_t)c->n_local_rows * c->W * kMapBytes;
-  if (bytes < need) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_pack_error_map_device: destination smaller than local pixels x 8 bytes");
-  if (need == 0) return MCPT_OK;
-  if (!dst || ((uintptr_t)dst & (kMapBytes - 1)))
-    return set_err(MCPT_ERR_INVALID_ARG, "mcpt_pack_error_map_device: destination must be an 8-byte aligned device pointer");
-  HIP_OR_RETURN(hipSetDevice(c->device));
-  // (the map is contiguous in local row order already: a copy on the stream, behind the select)
-  HIP_OR_RETURN(hipMemcpyAsync(dst, c->d_emap, need, hipMemcpyDeviceToDevice, c->stream));
-  return MCPT_OK;
-}
-
-int mcpt_load_rows_error_map(mcpt_ctx* c, const void* src, long long src_rows, const int* src_row) {
-  if (!c) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
-  c->emap_plane_valid = false;   // (on any error the frame holds no gathered map)
-  if (!src || !src_row || ((uintptr_t)src & (kMapBytes - 1)))
-    return set_err(MCPT_ERR_INVALID_ARG, "mcpt_load_rows_error_map: bad arguments (8-byte aligned source)");
-  if (!c->has_target) return set_err(MCPT_ERR_NO_TARGET, "mcpt_load_rows_error_map: frame has no target");
-  if (c->n_local_rows != c->H) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_load_rows_error_map: frame target is a shard");
-  for (int i = 0; i < c->H; ++i)
-    if (c->rows[(size_t)i] != i) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_load_rows_error_map: frame target is not in row order");
-  for (int y = 0; y < c->H; ++y)
-    if (src_row[y] < 0 || src_row[y] >= src_rows)
-      return set_err(MCPT_ERR_INVALID_ARG, "mcpt_load_rows_error_map: a source row lies outside the packed buffer");
-  if (c->H == 0 || c->W == 0) return MCPT_OK;
-  HIP_OR_RETURN(hipSetDevice(c->device));
-  if (!c->d_emap_plane) HIP_OR_RETURN(hipMalloc(&c->d_emap_plane, (size_t)c->H * c->W * kMapBytes));
-  OK_OR_RETURN(upload_load_index(c, src_row));
-  HIP_OR_RETURN(mcpt_launch_load_rows_error_map(src, c->d_load_index, c->W, c->H, c->d_emap_plane, c->stream));
-  c->emap_plane_valid = true;
   return MCPT_OK;
 }
 
@@ -698,8 +575,7 @@ int mcpt_error_map_record(mcpt_ctx* c, float threshold, mcpt_convergence_t* out)
   HIP_OR_RETURN(hipSetDevice(c->device));
   if (!c->d_emap_rec) HIP_OR_RETURN(hipMalloc(&c->d_emap_rec, sizeof(unsigned long long) * mcpt::kStatsRecWords));
   const long long n = (long long)c->n_local_rows * c->W;
-  HIP_OR_RETURN(mcpt_launch_error_map_record(source == 2 ? c->d_emap_plane : c->d_emap, n, threshold, c->d_emap_rec,
-                                             c->stream));
+  HIP_OR_RETURN(mcpt_launch_error_map_record(held_error_map(c), n, threshold, c->d_emap_rec, c->stream));
   unsigned long long part[mcpt::kStatsRecWords] = {};
   HIP_OR_RETURN(hipMemcpyAsync(part, c->d_emap_rec, sizeof(part), hipMemcpyDeviceToHost, c->stream));
   HIP_OR_RETURN(hipStreamSynchronize(c->stream));

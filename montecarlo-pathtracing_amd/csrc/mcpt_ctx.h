@@ -1,6 +1,8 @@
-// mcpt_ctx.h — the context of the C ABI's device half and the helpers its two translation units
+// mcpt_ctx.h — the context of the C ABI's device half and the helpers its three translation units
 // share (mcpt_capi.hip: lifetime, uploads, target, render, queries; mcpt_capi_post.hip: guides and
-// denoiser, noise statistics, adaptive sampling).
+// denoiser, noise statistics, adaptive sampling; mcpt_capi_gather.hip: what moves a shard into a
+// frame), among them where a pixel's sample count comes from (count_source) and which error map the
+// context holds (held_error_map): each chosen here, once.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -8,6 +10,7 @@
 #include <vector>
 
 #include "../../include/mcpt.h"
+#include "mcpt_gather_plan.h"
 #include "mcpt_internal.h"
 #include "mcpt_plan.h"
 
@@ -222,6 +225,25 @@ inline void invalidate_planes(mcpt_ctx* c) { c->plane_valid = false; c->emap_pla
 // a context has per-pixel sample counts: (b) a counted gather filled the count
 // plane, or (a) the adaptive mode is on; the plane describes the accumulator as long as it is valid
 inline bool has_pixel_counts(const mcpt_ctx* c) { return c->plane_valid || c->ad_on; }
+// ... and where they come from: the valid count plane, else the blocks' passes over p0 while the
+// adaptive mode is on, else the pass count for every pixel (mcpt_internal.h: count_at)
+inline mcpt::CountSource count_source(const mcpt_ctx* c) {
+  mcpt::CountSource src;
+  src.plane = c->plane_valid ? c->d_count_plane : nullptr;
+  src.passes = !c->plane_valid && c->ad_on ? c->d_ad_passes : nullptr;
+  src.W = c->W; src.blocks_x = c->ad_blocks_x;
+  src.base = src.passes ? c->ad_p0 : c->pass_count;
+  return src;
+}
+
+// the error map a context holds: 2 the gathered plane while it is valid, else 1
+// its own statistics window's, else 0 none; held_error_map: that map (null: none, or no pixels)
+inline bool has_own_error_map(const mcpt_ctx* c) { return c->stats_on && c->emap_valid; }
+inline int error_map_source(const mcpt_ctx* c) { return c->emap_plane_valid ? 2 : has_own_error_map(c) ? 1 : 0; }
+inline const float2* held_error_map(const mcpt_ctx* c) {
+  const int source = error_map_source(c);
+  return source == 2 ? c->d_emap_plane : source == 1 ? c->d_emap : nullptr;
+}
 
 // identity of a context's target for its checkpoints: FNV-1a (64 bit) over its image row ids
 inline unsigned long long rows_hash(const mcpt_ctx* c) {

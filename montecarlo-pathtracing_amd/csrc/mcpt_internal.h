@@ -277,23 +277,35 @@ hipError_t mcpt_launch_adaptive_compact(const mcpt::AdaptiveTarget& t, int* list
 // passes[b] += n for the listed blocks (list null: for every block)
 hipError_t mcpt_launch_adaptive_add_passes(const mcpt::AdaptiveTarget& t, const int* list, int n_list, int n,
                                            hipStream_t stream);
-// per local pixel: its sample count p0 + passes[its block] / accum / (float)that count
-hipError_t mcpt_launch_adaptive_counts(const mcpt::AdaptiveTarget& t, int* counts, hipStream_t stream);
-hipError_t mcpt_launch_adaptive_resolve(const mcpt::AdaptiveTarget& t, const float* accum, float* out,
-                                        hipStream_t stream);
-// mcpt_launch_average4's twin for a frame with per-pixel counts: out = {accum / (float)count, 0},
-// the count from `plane` (one int per pixel) or, plane null, from t's block arrays; t.W and
-// t.n_local_rows size the launch either way
-hipError_t mcpt_launch_resolve4(const mcpt::AdaptiveTarget& t, const int* plane, const float* accum, float4* out,
+// Where a pixel's sample count comes from (chosen on the host, mcpt_ctx.h
+// count_source): the count plane, else base (p0) + the passes of the pixel's 8x8 block, else base (the
+// pass count).  Passed by value: kernel arguments, so count_at's choice is uniform over the launch.
+namespace mcpt {
+struct CountSource {
+  const int* plane;             // one int per local pixel, or null
+  const int* passes;            // one int per block (plane null), or null
+  int W, blocks_x, base;
+};
+__device__ __forceinline__ int count_at(const CountSource& src, long long i) {
+  if (src.plane) return src.plane[i];
+  if (!src.passes) return src.base;
+  // (a target holds fewer than 2^31 pixels, mcpt_set_target*: the row from a 32-bit division)
+  const unsigned lr = (unsigned)i / (unsigned)src.W, x = (unsigned)i - lr * (unsigned)src.W;
+  return src.base + src.passes[(lr >> 3) * (unsigned)src.blocks_x + (x >> 3)];
+}
+}  // namespace mcpt
+// per local pixel (n_px of them, rows of src.W): its sample count / accum / (float)that count
+hipError_t mcpt_launch_counts(const mcpt::CountSource& src, int* counts, long long n_px, hipStream_t stream);
+hipError_t mcpt_launch_resolve(const mcpt::CountSource& src, const float* accum, float* out, long long n_px,
+                               hipStream_t stream);
+// mcpt_launch_average4's twin for a frame with per-pixel counts: out = {accum / (float)count, 0}
+hipError_t mcpt_launch_resolve4(const mcpt::CountSource& src, const float* accum, float4* out, long long n_px,
                                 hipStream_t stream);
-hipError_t mcpt_launch_resolve_plane(const int* plane, const float* accum, float* out, long long n_px,
-                                     hipStream_t stream);
 // the multi-process counted gather's ends: 16-byte records {r, g, b bits, int32 count} per pixel.
-// pack: t's local rows in order into `out` (16-byte aligned), the count from `plane` (non-null), else
-// from t's block arrays (t.passes non-null), else `uniform`.  load: frame row y of a W x H frame from
-// packed row src_row[y] of `src` (16-byte aligned), the sums to accum and the counts to plane.
-hipError_t mcpt_launch_pack_counted(const mcpt::AdaptiveTarget& t, const int* plane, int uniform, const float* accum,
-                                    void* out, hipStream_t stream);
+// pack: n_rows local rows of src.W pixels in order into `out`.  load: frame row y of a W x H frame
+// from packed row src_row[y] of `src`, the sums to accum, the counts to plane (16-byte aligned both).
+hipError_t mcpt_launch_pack_counted(const mcpt::CountSource& src, int n_rows, const float* accum, void* out,
+                                    hipStream_t stream);
 hipError_t mcpt_launch_load_rows_counted(const void* src, const int* src_row, int W, int H, float* accum, int* plane,
                                          hipStream_t stream);
 // the gathered error map's load: frame row y of `plane` (W x H x {se, r}) from row src_row[y] of the
