@@ -493,6 +493,27 @@ int mcpt_read_error_map(mcpt_ctx* ctx, float* se_r2);
 int mcpt_denoise_guided(mcpt_ctx* ctx, int iterations, float k_color, float sigma_plane);
 int mcpt_last_stats_ms(mcpt_ctx* ctx, float* update_ms, float* error_ms);
 
+/* The variance-propagating filter ("Variance filter"; no reference equivalent).
+ * The error map's se^2 is prefiltered over each pixel's 3x3 neighbours of its own key, rides in the
+ * filter image's fourth word and is filtered with the squared weights; iteration s takes its
+ * colour tolerance from the variance its input has: kc_p = 1 / (k_color^2 * var_p + 2^-40), not
+ * halved.  Plane and normal terms, taps and kernels are mcpt_denoise's.
+ *
+ * mcpt_denoise_variance: preconditions, error codes and error-map source exactly those of
+ * mcpt_denoise_guided (the gathered plane when valid, else the own window's map, else
+ * MCPT_ERR_NO_STATS; MCPT_ERR_INVALID_ARG once an adaptive block has retired).
+ * mcpt_denoise_resolved_variance: those of mcpt_denoise_resolved_guided (MCPT_ERR_NO_ADAPTIVE
+ * without per-pixel counts); with no block retired it gives mcpt_denoise_variance's bits.
+ * Both write mcpt_denoise's result buffers and allocate nothing beyond them: mcpt_read_denoised,
+ * mcpt_last_denoise_ms, mcpt_denoise_iteration_ms (-1: the averaging / resolve step, which holds
+ * the prefilter) and mcpt_last_denoise_path serve them.
+ * mcpt_read_denoised_variance: n_local f32, the fourth word of the last variance filter's image
+ * (iterations = 0: the prefiltered variance); MCPT_ERR_NO_STATS if the last filter run was not a
+ * variance filter.  Synchronizes. */
+int mcpt_denoise_variance(mcpt_ctx* ctx, int iterations, float k_color, float sigma_plane);
+int mcpt_denoise_resolved_variance(mcpt_ctx* ctx, int iterations, float k_color, float sigma_plane);
+int mcpt_read_denoised_variance(mcpt_ctx* ctx, float* v_out);
+
 /* Adaptive sampling of 8x8 pixel blocks guided by the error map (no reference
  * equivalent).  Opt-in, on top of the noise statistics; with the mode off nothing changes.
  *

@@ -419,6 +419,8 @@ class Renderer {
   // noise statistics, the convergence metric and the noise-guided filter (mcpt.h):
   // between stats_begin and stats_end every render call is one batch of the window
   static constexpr float kDenoiseKColor = 64.0f, kErrorMuFloor = 0.01f;
+  // the variance filter's colour width in standard deviations of the carried variance
+  static constexpr float kDenoiseKVariance = 16.0f;
   void stats_begin() { check(mcpt_stats_begin(c_), "mcpt_stats_begin"); }
   void stats_end() { check(mcpt_stats_end(c_), "mcpt_stats_end"); }
   void stats_add_batch(int n) { check(mcpt_stats_add_batch(c_, n), "mcpt_stats_add_batch"); }
@@ -445,6 +447,21 @@ class Renderer {
     std::vector<float> img((size_t)rows_ * W_ * 3);
     check(mcpt_read_denoised(c_, img.data()), "mcpt_read_denoised");
     return img;
+  }
+  // the variance-propagating filter (mcpt_denoise_variance): denoise_guided's preconditions; the
+  // error map's variance is prefiltered 3x3, carried in the image's fourth word and filtered along
+  std::vector<float> denoise_variance(int iterations = 5, float k_color = kDenoiseKVariance,
+                                      float sigma_plane = kDenoiseSigmaPlane) {
+    check(mcpt_denoise_variance(c_, iterations, k_color, sigma_plane), "mcpt_denoise_variance");
+    std::vector<float> img((size_t)rows_ * W_ * 3);
+    check(mcpt_read_denoised(c_, img.data()), "mcpt_read_denoised");
+    return img;
+  }
+  // local pixels x 1: the variance the last denoise_variance / denoise_resolved_variance carried
+  std::vector<float> read_denoised_variance() const {
+    std::vector<float> v((size_t)rows_ * W_);
+    check(mcpt_read_denoised_variance(c_, v.data()), "mcpt_read_denoised_variance");
+    return v;
   }
   void last_stats_ms(float& update_ms, float& error_ms) const {
     check(mcpt_last_stats_ms(c_, &update_ms, &error_ms), "mcpt_last_stats_ms");
@@ -559,6 +576,13 @@ class Renderer {
   std::vector<float> denoise_resolved_guided(int iterations = 5, float k_color = kDenoiseKColor,
                                              float sigma_plane = kDenoiseSigmaPlane) {
     check(mcpt_denoise_resolved_guided(c_, iterations, k_color, sigma_plane), "mcpt_denoise_resolved_guided");
+    std::vector<float> img((size_t)rows_ * W_ * 3);
+    check(mcpt_read_denoised(c_, img.data()), "mcpt_read_denoised");
+    return img;
+  }
+  std::vector<float> denoise_resolved_variance(int iterations = 5, float k_color = kDenoiseKVariance,
+                                               float sigma_plane = kDenoiseSigmaPlane) {
+    check(mcpt_denoise_resolved_variance(c_, iterations, k_color, sigma_plane), "mcpt_denoise_resolved_variance");
     std::vector<float> img((size_t)rows_ * W_ * 3);
     check(mcpt_read_denoised(c_, img.data()), "mcpt_read_denoised");
     return img;

@@ -23,6 +23,8 @@
 //   mcpt_render --scene 6 --spp 4096 --chunk 32 --adaptive --target-error 0.05 --devices 0,1,2,3 --aov s6
 //   mcpt_render --scene 8 --spp 512 --chunk 32 --devices 0,1,2,3 --denoise-guided 3 --out s8.png   (the shards'
 //       error maps are gathered after the rows, mcpt_gather_error_map, for the noise-guided filter)
+//   mcpt_render --scene 6 --spp 16 --chunk 4 --denoise-variance --aov s6 --out s6.png   (the variance-propagating
+//       filter; --aov also writes s6_variance.pfm)
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -47,6 +49,9 @@ struct Args {
   std::string aov;            // --aov PREFIX: PREFIX_normal.pfm, _albedo.pfm, _depth.pfm (+ _error.pfm with statistics)
   double target_error = 0.0;  // --target-error E: stop once the mean relative error <= E (--spp: the cap; 0: off)
   int denoise_guided = -1;    // --denoise-guided [N]: the noise-guided filter (-1: off; N defaults to 5)
+  int denoise_variance = -1;  // --denoise-variance [N]: the variance-propagating filter (-1: off; N defaults to 5)
+  // one of the filters that read the error map (statistics on, >= 2 chunks)
+  bool noise_filter() const { return denoise_guided >= 0 || denoise_variance >= 0; }
   bool adaptive = false;      // --adaptive: --target-error is the per-pixel threshold; retired 8x8 blocks stop receiving passes
 };
 
@@ -84,7 +89,12 @@ void usage() {
                "                   [--denoise-guided [N]]   (the a-trous filter with the colour width from each\n"
                "                                             pixel's standard error; >= 2 chunks; with --devices\n"
                "                                             the shards' error maps are gathered with the rows,\n"
-               "                                             not together with --adaptive)\n");
+               "                                             not together with --adaptive)\n"
+               "                   [--denoise-variance [N]]   (the variance-propagating a-trous filter: the error\n"
+               "                                               map's variance prefiltered 3x3 and filtered along\n"
+               "                                               with the colour; accepted and refused where\n"
+               "                                               --denoise-guided is; --aov also writes\n"
+               "                                               PREFIX_variance.pfm)\n");
 }
 
 bool parse(int argc, char** argv, Args& a) {
@@ -105,6 +115,12 @@ bool parse(int argc, char** argv, Args& a) {
       a.denoise_guided = 5;
       if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') a.denoise_guided = std::atoi(argv[++i]);
       if (a.denoise_guided > 8) return false;
+      continue;
+    }
+    if (k == "--denoise-variance") {
+      a.denoise_variance = 5;
+      if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') a.denoise_variance = std::atoi(argv[++i]);
+      if (a.denoise_variance > 8) return false;
       continue;
     }
     if (i + 1 >= argc) return false;
@@ -153,8 +169,8 @@ bool parse(int argc, char** argv, Args& a) {
   // (the guided filter on a gathered frame: the uniform shards' error maps travel with
   // mcpt_gather_error_map; with --adaptive the combination stays refused here, and the library calls
   // gather_rows_counted + gather_error_map + denoise_resolved_guided serve it)
-  if (!a.devices.empty() && a.adaptive && a.denoise_guided >= 0) return false;
-  if (a.denoise >= 0 && a.denoise_guided >= 0) return false;                                // one filter
+  if (!a.devices.empty() && a.adaptive && a.noise_filter()) return false;
+  if ((a.denoise >= 0) + (a.denoise_guided >= 0) + (a.denoise_variance >= 0) > 1) return false;   // one filter
   if (a.adaptive && !(a.target_error > 0.0)) return false;   // adaptive sampling needs its threshold
   return a.width > 0 && a.height > 0 && a.spp >= 0 && a.chunk > 0 && a.subsampling >= 0 && a.subsampling < 16;
 }
@@ -224,6 +240,15 @@ void post_process(const Args& a, mcpt::Renderer& r, const mcpt::Camera& cam, int
   if (a.denoise >= 0) img = a.adaptive ? r.denoise_resolved(a.denoise) : r.denoise(a.denoise);
   if (a.denoise_guided >= 0)   // (fewer than two chunks: an error)
     img = a.adaptive ? r.denoise_resolved_guided(a.denoise_guided) : r.denoise_guided(a.denoise_guided);
+  if (a.denoise_variance >= 0) {   // (fewer than two chunks: an error)
+    img = a.adaptive ? r.denoise_resolved_variance(a.denoise_variance) : r.denoise_variance(a.denoise_variance);
+    if (!a.aov.empty()) {
+      const std::vector<float> v = r.read_denoised_variance();
+      std::vector<float> var(v.size() * 3);
+      for (size_t i = 0; i < v.size(); ++i) var[3 * i] = var[3 * i + 1] = var[3 * i + 2] = v[i];
+      mcpt::write_pfm(a.aov + "_variance.pfm", var, W, H);
+    }
+  }
   float gm = 0.0f, fm = 0.0f;
   r.last_denoise_ms(gm, fm);
   guides_ms = gm; filter_ms = fm;
@@ -246,8 +271,8 @@ int main(int argc, char** argv) {
     const mcpt::Camera cam = mcpt::Camera::canonical(a.width, a.height);
 
     double kernel_ms = 0.0, wall_ms = 0.0, gather_ms = 0.0, guides_ms = 0.0, filter_ms = 0.0;
-    const bool post = a.denoise >= 0 || a.denoise_guided >= 0 || !a.aov.empty();
-    const bool stats = a.target_error > 0.0 || a.denoise_guided >= 0;
+    const bool post = a.denoise >= 0 || a.noise_filter() || !a.aov.empty();
+    const bool stats = a.target_error > 0.0 || a.noise_filter();
     std::vector<float> img;
     std::string shard_json;
     int rendered = a.spp;   // passes in the image (fewer with --target-error)
@@ -387,15 +412,15 @@ int main(int argc, char** argv) {
                 shard_done = shard_rec[(size_t)k].n_active_blocks == 0;
               }
             }
-            // uniform shards with --denoise-guided: a statistics window over the chunks and, after the
+            // uniform shards with --denoise-guided / --denoise-variance: a statistics window over the chunks and, after the
             // last, the shard's error map (fewer than two chunks: MCPT_ERR_NO_STATS, as on one device)
-            if (!a.adaptive && a.denoise_guided >= 0) s.stats_begin();
+            if (!a.adaptive && a.noise_filter()) s.stats_begin();
             for (int done = 0; !a.adaptive && done < a.spp; done += a.chunk) {
               const int n = std::min(a.chunk, a.spp - done);
               s.render(cam, a.first_pass + done, n, a.date, a.bounces, a.ior, a.variant);
               shard_ms[(size_t)k] += s.last_render_ms();   // (synchronizes this shard)
             }
-            if (!a.adaptive && a.denoise_guided >= 0) s.convergence(kMapThreshold);
+            if (!a.adaptive && a.noise_filter()) s.convergence(kMapThreshold);
           } catch (const std::exception& e) {
             errors[(size_t)k] = e.what();
           }
@@ -413,7 +438,7 @@ int main(int argc, char** argv) {
         frame.gather_rows(views);
         img = frame.read_image();
       }
-      if (a.denoise_guided >= 0) frame.gather_error_map(views);   // (after the rows: a row gather invalidates it)
+      if (a.noise_filter()) frame.gather_error_map(views);   // (after the rows: a row gather invalidates it)
       if (post) post_process(a, frame, cam, W, H, img, guides_ms, filter_ms);
       const auto t2 = std::chrono::steady_clock::now();
       wall_ms = std::chrono::duration<double, std::milli>(t2 - t0).count();
@@ -468,6 +493,7 @@ int main(int argc, char** argv) {
                     filter_ms);
       shard_json += buf;
       if (a.denoise_guided >= 0) shard_json += ", \"denoise_guided\": " + std::to_string(a.denoise_guided);
+      if (a.denoise_variance >= 0) shard_json += ", \"denoise_variance\": " + std::to_string(a.denoise_variance);
     }
     shard_json += ", \"passes\": " + std::to_string(rendered);
     std::printf("{\"scene\": %d, \"width\": %d, \"height\": %d, \"spp\": %d, \"bounces\": %d, \"ior\": %g, "

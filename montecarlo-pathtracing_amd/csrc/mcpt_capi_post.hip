@@ -108,9 +108,11 @@ int mcpt_read_guides(mcpt_ctx* c, float* guide8, float* albedo4) {
 // mcpt_denoise (guided false: sigma_color is the global width) and mcpt_denoise_guided (guided
 // true: sigma_color is k_color, the width per pixel k_color * 2^-s * se from the error map);
 // resolved: the mcpt_denoise_resolved* forms, whose input is accum / (float)count with every
-// pixel's own count in place of accum / pass_count
+// pixel's own count in place of accum / pass_count; variance: the
+// mcpt_denoise*_variance forms (guided's preconditions and map; sigma_color is k_color, the first
+// input carries the prefiltered se^2 in .w and every iteration filters it along)
 static int denoise_run(mcpt_ctx* c, int iterations, float sigma_color, float sigma_plane, bool guided,
-                       bool resolved = false) {
+                       bool resolved = false, bool variance = false) {
   if (!c || iterations < 0 || iterations > 8) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_denoise: iterations not in 0..8");
   if (!(sigma_color > 0.0f) || !(sigma_plane > 0.0f) || !std::isfinite(sigma_color) || !std::isfinite(sigma_plane))
     return set_err(MCPT_ERR_INVALID_ARG, "mcpt_denoise: sigmas must be positive and finite");
@@ -140,7 +142,11 @@ static int denoise_run(mcpt_ctx* c, int iterations, float sigma_color, float sig
   const long long n = (long long)c->H * c->W;
   // (the context's stream is ordered after all queued renders: their combines run on it)
   HIP_OR_RETURN(hipEventRecord(c->dn_ev[9], c->stream));
-  if (resolved)
+  const mcpt::CountSource counts = count_source(c);
+  if (variance)
+    HIP_OR_RETURN(mcpt_launch_variance_init(resolved ? &counts : nullptr, c->d_accum, c->d_dn[0], c->d_guide, emap, c->W,
+                                            c->H, c->pass_count, c->stream));
+  else if (resolved)
     HIP_OR_RETURN(mcpt_launch_resolve4(count_source(c), c->d_accum, c->d_dn[0], n, c->stream));
   else
     HIP_OR_RETURN(mcpt_launch_average4(c->d_accum, c->d_dn[0], n, c->pass_count, c->stream));
@@ -152,14 +158,19 @@ static int denoise_run(mcpt_ctx* c, int iterations, float sigma_color, float sig
     const float sp = sigma_plane * (float)step;
     // (guided: the kernel forms kc per pixel from sc = k_color * 2^-s and the pixel's se, §3.8)
     const float kc = guided ? sc : 1.0f / (sc * sc), kp = 1.0f / (sp * sp);
-    HIP_OR_RETURN(mcpt_launch_atrous(c->d_dn[s & 1], c->d_dn[(s + 1) & 1], c->d_guide, c->W, c->H, step, kc, kp,
-                                     guided ? emap : nullptr, naive, c->stream));
+    if (variance)   // (k_color^2, not halved: the width follows the variance the iteration's input has)
+      HIP_OR_RETURN(mcpt_launch_atrous_variance(c->d_dn[s & 1], c->d_dn[(s + 1) & 1], c->d_guide, c->W, c->H, step,
+                                                sigma_color * sigma_color, kp, naive, c->stream));
+    else
+      HIP_OR_RETURN(mcpt_launch_atrous(c->d_dn[s & 1], c->d_dn[(s + 1) & 1], c->d_guide, c->W, c->H, step, kc, kp,
+                                       guided ? emap : nullptr, naive, c->stream));
     HIP_OR_RETURN(hipEventRecord(c->dn_ev[s + 1], c->stream));
     if (!naive && step <= 2) lds_mask |= 1 << s;
   }
   c->dn_lds_mask = lds_mask;
   c->dn_result = iterations & 1;
   c->dn_iters = iterations;
+  c->dn_variance = variance;
   return MCPT_OK;
 }
 
@@ -177,6 +188,14 @@ int mcpt_denoise_resolved(mcpt_ctx* c, int iterations, float sigma_color, float 
 
 int mcpt_denoise_resolved_guided(mcpt_ctx* c, int iterations, float k_color, float sigma_plane) {
   return denoise_run(c, iterations, k_color, sigma_plane, true, true);
+}
+
+int mcpt_denoise_variance(mcpt_ctx* c, int iterations, float k_color, float sigma_plane) {
+  return denoise_run(c, iterations, k_color, sigma_plane, true, false, true);
+}
+
+int mcpt_denoise_resolved_variance(mcpt_ctx* c, int iterations, float k_color, float sigma_plane) {
+  return denoise_run(c, iterations, k_color, sigma_plane, true, true, true);
 }
 
 // ---- noise statistics and the convergence metric (mcpt_stats.hip)
@@ -601,6 +620,20 @@ int mcpt_read_denoised(mcpt_ctx* c, float* rgb_out) {
   for (size_t i = 0; i < n; ++i) {
     rgb_out[3 * i] = h[i].x; rgb_out[3 * i + 1] = h[i].y; rgb_out[3 * i + 2] = h[i].z;
   }
+  return MCPT_OK;
+}
+
+int mcpt_read_denoised_variance(mcpt_ctx* c, float* v_out) {
+  if (!c || !v_out) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  if (!c->has_target) return mcpt_err_bare(MCPT_ERR_NO_TARGET);
+  if (c->dn_result < 0 || !c->dn_variance)
+    return set_err(MCPT_ERR_NO_STATS, "mcpt_read_denoised_variance: the last filter run was no mcpt_denoise_variance");
+  HIP_OR_RETURN(hipSetDevice(c->device));
+  const size_t n = (size_t)c->n_local_rows * c->W;
+  std::vector<float4> h(n);
+  if (n) HIP_OR_RETURN(hipMemcpyAsync(h.data(), c->d_dn[c->dn_result], n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+  HIP_OR_RETURN(hipStreamSynchronize(c->stream));
+  for (size_t i = 0; i < n; ++i) v_out[i] = h[i].w;
   return MCPT_OK;
 }
 

@@ -133,6 +133,7 @@ struct mcpt_ctx {
   int dn_result = -1;               // which of d_dn holds the last mcpt_denoise's result (-1: none)
   int dn_iters = -1;                // its iterations (-1: none timed)
   int dn_lds_mask = 0;              // bit s: its iteration s ran the LDS-tile kernel
+  bool dn_variance = false;         // it was a mcpt_denoise*_variance: the result's .w holds the variance
   bool guides_timed = false;
   hipEvent_t guide_ev[2] = {nullptr, nullptr};
   hipEvent_t dn_ev[10] = {};        // before the first iteration, then after each (<= 8); [9]: before the average
@@ -191,7 +192,7 @@ inline int env_int(const char* name, int dflt) {
 inline void free_denoise(mcpt_ctx* c) {
   (void)hipFree(c->d_guide); (void)hipFree(c->d_albedo); (void)hipFree(c->d_dn[0]); (void)hipFree(c->d_dn[1]);
   c->d_guide = nullptr; c->d_albedo = nullptr; c->d_dn[0] = nullptr; c->d_dn[1] = nullptr;
-  c->guides_valid = false; c->dn_result = -1; c->dn_iters = -1; c->guides_timed = false;
+  c->guides_valid = false; c->dn_result = -1; c->dn_iters = -1; c->dn_variance = false; c->guides_timed = false;
 }
 
 inline void free_stats(mcpt_ctx* c) {

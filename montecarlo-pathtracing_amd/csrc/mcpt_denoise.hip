@@ -18,7 +18,11 @@
 //    Each has a noise-guided form (GUIDED, mcpt_denoise_guided): the colour term's
 //    kc is not the launch's constant but a value of the centre pixel, from one extra 4-byte load
 //    of its standard error (the error map of mcpt_convergence); the taps and atrous_pixel are the
-//    same.
+//    same.  The variance-propagating form (kAtrousVariance, mcpt_denoise_variance)
+//    carries each pixel's variance in the colour word's .w, which the tiles stage already: kc comes
+//    from the centre's .w, the taps' .w are filtered with the squared weights, no error-map load.
+//  * variance_init_kernel: that form's first input, the averaging (or the resolve) and the 3x3
+//    key-aware prefilter of se^2 in one pass.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "mcpt_device.h"
@@ -72,12 +76,19 @@ __host__ __device__ constexpr float atrous_h(int i) {
 
 // One output pixel (x, y) of one iteration (these operations, in this order).
 // fetch(qx, qy, c, g0, g1) loads the three words of the in-frame pixel (qx, qy).
-template <class Fetch>
+// VAR (the variance-propagating form): kc is k_color^2 and the colour term's factor
+// comes from the centre's carried variance cp.w; the taps' .w are summed with the squared weights.
+template <bool VAR, class Fetch>
 __device__ __forceinline__ float4 atrous_pixel(int x, int y, int W, int H, int step, float kc, float kp, float4 cp,
                                                float4 g0p, float4 g1p, Fetch fetch) {
   const int key_p = __float_as_int(g0p.w);
   constexpr float h22 = atrous_h(2) * atrous_h(2);
   float sx = h22 * cp.x, sy = h22 * cp.y, sz = h22 * cp.z, wsum = h22;
+  float vs = 0.0f;
+  if constexpr (VAR) {
+    vs = (h22 * h22) * cp.w;
+    kc = rcp_rn(kc * cp.w + 0x1p-40f);
+  }
 #pragma unroll
   for (int dy = -2; dy <= 2; ++dy) {
 #pragma unroll
@@ -104,23 +115,29 @@ __device__ __forceinline__ float4 atrous_pixel(int x, int y, int W, int H, int s
       const float w = (((atrous_h(dy + 2) * atrous_h(dx + 2)) * wn) * r) * r;
       sx += w * cq.x; sy += w * cq.y; sz += w * cq.z;
       wsum += w;
+      if constexpr (VAR) vs += (w * w) * cq.w;
     }
   }
+  if constexpr (VAR) return make_float4(sx / wsum, sy / wsum, sz / wsum, vs / (wsum * wsum));
   return make_float4(sx / wsum, sy / wsum, sz / wsum, 0.0f);
 }
 
+// The colour term's source: the launch's constant, the error map (GUIDED), the carried variance.
+enum { kAtrousFixed = 0, kAtrousGuided = 1, kAtrousVariance = 2 };
+
 // kc of the centre pixel px.  Fixed sigma: the launch's kc.  GUIDED: kc carries k_color * 2^-s
-// (formed on the host, exact) and the pixel's width is that times its standard error.
-template <bool GUIDED>
+// (formed on the host, exact) and the pixel's width is that times its standard error.  Variance:
+// the launch's k_color^2, which atrous_pixel scales by the centre's own variance.
+template <int MODE>
 __device__ __forceinline__ float atrous_kc(float kc, const float2* __restrict__ emap, size_t px) {
-  if constexpr (!GUIDED) return kc;
+  if constexpr (MODE != kAtrousGuided) return kc;
   const float sg = kc * emap[px].x;
   return rcp_rn(sg * sg + 0x1p-40f);
 }
 
 constexpr int kAtrousTile = 16;   // LDS kernels: 16x16 pixels (2x2 waves of 8x8) + the halo
 
-template <int STEP, bool GUIDED>
+template <int STEP, int MODE>
 __global__ __launch_bounds__(256) void atrous_lds_kernel(const float4* __restrict__ src, float4* __restrict__ dst,
                                                          const float4* __restrict__ guide, int W, int H, float kc,
                                                          float kp, const float2* __restrict__ emap) {
@@ -151,11 +168,12 @@ __global__ __launch_bounds__(256) void atrous_lds_kernel(const float4* __restric
     c = s_c[i]; g0 = s_g0[i]; g1 = s_g1[i];
   };
   const size_t px = (size_t)y * W + x;
-  dst[px] = atrous_pixel(x, y, W, H, STEP, atrous_kc<GUIDED>(kc, emap, px), kp, s_c[ci], s_g0[ci], s_g1[ci], fetch);
+  dst[px] = atrous_pixel<MODE == kAtrousVariance>(x, y, W, H, STEP, atrous_kc<MODE>(kc, emap, px), kp, s_c[ci],
+                                                  s_g0[ci], s_g1[ci], fetch);
 }
 
 // 64x4 pixels per workgroup, a wave = 64 pixels of one row
-template <bool GUIDED>
+template <int MODE>
 __global__ __launch_bounds__(256) void atrous_global_kernel(const float4* __restrict__ src, float4* __restrict__ dst,
                                                             const float4* __restrict__ guide, int W, int H, int step,
                                                             float kc, float kp, const float2* __restrict__ emap) {
@@ -166,8 +184,44 @@ __global__ __launch_bounds__(256) void atrous_global_kernel(const float4* __rest
     c = src[q]; g0 = guide[2 * q]; g1 = guide[2 * q + 1];
   };
   const size_t px = (size_t)y * W + x;
-  dst[px] = atrous_pixel(x, y, W, H, step, atrous_kc<GUIDED>(kc, emap, px), kp, src[px], guide[2 * px],
-                         guide[2 * px + 1], fetch);
+  dst[px] = atrous_pixel<MODE == kAtrousVariance>(x, y, W, H, step, atrous_kc<MODE>(kc, emap, px), kp, src[px],
+                                                  guide[2 * px], guide[2 * px + 1], fetch);
+}
+
+// The variance filter's first input: {accum / n, v0} with n the pass count
+// (RESOLVED: the pixel's own count, resolve4_kernel's division) and v0 the 3x3 prefilter of the
+// error map's se^2 over the neighbours of the centre's key, weights {1/4, 1/2, 1/4}^2, dy outer.
+// 64x4 pixels per workgroup as atrous_global_kernel; 9 taps of 4 + 4 bytes from global memory, once.
+constexpr float kVarianceMax = 0x1p60f;
+__host__ __device__ constexpr float variance_g(int i) { return i == 1 ? 0.5f : 0.25f; }
+
+template <bool RESOLVED>
+__global__ __launch_bounds__(256) void variance_init_kernel(CountSource cnt, const float* __restrict__ accum,
+                                                            float4* __restrict__ out,
+                                                            const float4* __restrict__ guide,
+                                                            const float2* __restrict__ emap, int W, int H, float nb) {
+  const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (x >= W || y >= H) return;
+  const size_t px = (size_t)y * W + x;
+  if constexpr (RESOLVED) nb = (float)count_at(cnt, (long long)px);
+  const int key_p = __float_as_int(guide[2 * px].w);
+  float sv = 0.0f, sg = 0.0f;
+#pragma unroll
+  for (int dy = -1; dy <= 1; ++dy) {
+#pragma unroll
+    for (int dx = -1; dx <= 1; ++dx) {
+      const int qx = x + dx, qy = y + dy;
+      if (qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
+      const size_t q = (size_t)qy * W + qx;
+      if (__float_as_int(guide[2 * q].w) != key_p) continue;
+      const float se = emap[q].x, t = se * se;
+      const float vraw = t < kVarianceMax ? t : kVarianceMax;   // NaN and +inf: kVarianceMax
+      const float gw = variance_g(dy + 1) * variance_g(dx + 1);
+      sv += gw * vraw;
+      sg += gw;
+    }
+  }
+  out[px] = make_float4(accum[3 * px] / nb, accum[3 * px + 1] / nb, accum[3 * px + 2] / nb, sv / sg);
 }
 
 }  // namespace mcpt
@@ -189,25 +243,45 @@ hipError_t mcpt_launch_average4(const float* accum, float4* out, long long n_px,
   return hipGetLastError();
 }
 
-template <bool GUIDED>
+template <int MODE>
 static void launch_atrous(const float4* src, float4* dst, const float4* guide, int W, int H, int step, float kc,
                           float kp, const float2* emap, bool naive, hipStream_t stream) {
   constexpr int T = mcpt::kAtrousTile;
   const dim3 tiles((unsigned)((W + T - 1) / T), (unsigned)((H + T - 1) / T));
   if (!naive && step == 1)
-    hipLaunchKernelGGL((mcpt::atrous_lds_kernel<1, GUIDED>), tiles, dim3(256), 0, stream, src, dst, guide, W, H, kc, kp,
+    hipLaunchKernelGGL((mcpt::atrous_lds_kernel<1, MODE>), tiles, dim3(256), 0, stream, src, dst, guide, W, H, kc, kp,
                        emap);
   else if (!naive && step == 2)
-    hipLaunchKernelGGL((mcpt::atrous_lds_kernel<2, GUIDED>), tiles, dim3(256), 0, stream, src, dst, guide, W, H, kc, kp,
+    hipLaunchKernelGGL((mcpt::atrous_lds_kernel<2, MODE>), tiles, dim3(256), 0, stream, src, dst, guide, W, H, kc, kp,
                        emap);
   else
-    hipLaunchKernelGGL((mcpt::atrous_global_kernel<GUIDED>), dim3((unsigned)((W + 63) / 64), (unsigned)((H + 3) / 4)),
+    hipLaunchKernelGGL((mcpt::atrous_global_kernel<MODE>), dim3((unsigned)((W + 63) / 64), (unsigned)((H + 3) / 4)),
                        dim3(256), 0, stream, src, dst, guide, W, H, step, kc, kp, emap);
 }
 
 hipError_t mcpt_launch_atrous(const float4* src, float4* dst, const float4* guide, int W, int H, int step, float kc,
                               float kp, const float2* emap, bool naive, hipStream_t stream) {
-  if (emap) launch_atrous<true>(src, dst, guide, W, H, step, kc, kp, emap, naive, stream);
-  else launch_atrous<false>(src, dst, guide, W, H, step, kc, kp, nullptr, naive, stream);
+  if (emap) launch_atrous<mcpt::kAtrousGuided>(src, dst, guide, W, H, step, kc, kp, emap, naive, stream);
+  else launch_atrous<mcpt::kAtrousFixed>(src, dst, guide, W, H, step, kc, kp, nullptr, naive, stream);
+  return hipGetLastError();
+}
+
+hipError_t mcpt_launch_atrous_variance(const float4* src, float4* dst, const float4* guide, int W, int H, int step,
+                                       float kk, float kp, bool naive, hipStream_t stream) {
+  launch_atrous<mcpt::kAtrousVariance>(src, dst, guide, W, H, step, kk, kp, nullptr, naive, stream);
+  return hipGetLastError();
+}
+
+hipError_t mcpt_launch_variance_init(const mcpt::CountSource* counts, const float* accum, float4* out,
+                                     const float4* guide, const float2* emap, int W, int H, int pass_count,
+                                     hipStream_t stream) {
+  if (W <= 0 || H <= 0) return hipSuccess;
+  const dim3 grid((unsigned)((W + 63) / 64), (unsigned)((H + 3) / 4));
+  if (counts)
+    hipLaunchKernelGGL((mcpt::variance_init_kernel<true>), grid, dim3(256), 0, stream, *counts, accum, out, guide, emap,
+                       W, H, 0.0f);
+  else
+    hipLaunchKernelGGL((mcpt::variance_init_kernel<false>), grid, dim3(256), 0, stream, mcpt::CountSource{}, accum, out,
+                       guide, emap, W, H, (float)pass_count);
   return hipGetLastError();
 }

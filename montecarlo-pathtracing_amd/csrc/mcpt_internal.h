@@ -232,6 +232,10 @@ hipError_t mcpt_launch_average4(const float* accum, float4* out, long long n_px,
 // emap the per-pixel {se, r} of mcpt_launch_stats_error
 hipError_t mcpt_launch_atrous(const float4* src, float4* dst, const float4* guide, int W, int H, int step, float kc,
                               float kp, const float2* emap, bool naive, hipStream_t stream);
+// the variance-propagating form: src and dst carry each pixel's variance in .w, kk
+// is k_color^2; no error-map load
+hipError_t mcpt_launch_atrous_variance(const float4* src, float4* dst, const float4* guide, int W, int H, int step,
+                                       float kk, float kp, bool naive, hipStream_t stream);
 // noise statistics (mcpt_stats.hip): per local pixel one float4 {Yacc, S2, Ybase, 0}
 hipError_t mcpt_launch_stats_begin(const float* accum, float4* state, long long n_px, hipStream_t stream);
 hipError_t mcpt_launch_stats_update(const float* accum, float4* state, long long n_px, int n, hipStream_t stream);
@@ -301,6 +305,11 @@ hipError_t mcpt_launch_resolve(const mcpt::CountSource& src, const float* accum,
 // mcpt_launch_average4's twin for a frame with per-pixel counts: out = {accum / (float)count, 0}
 hipError_t mcpt_launch_resolve4(const mcpt::CountSource& src, const float* accum, float4* out, long long n_px,
                                 hipStream_t stream);
+// the variance filter's first input over a full W x H frame: out = {accum / n, 3x3 prefilter of the
+// map's se^2 among the centre's key}; counts null: n = pass_count, else every pixel's own count
+hipError_t mcpt_launch_variance_init(const mcpt::CountSource* counts, const float* accum, float4* out,
+                                     const float4* guide, const float2* emap, int W, int H, int pass_count,
+                                     hipStream_t stream);
 // the multi-process counted gather's ends: 16-byte records {r, g, b bits, int32 count} per pixel.
 // pack: n_rows local rows of src.W pixels in order into `out`.  load: frame row y of a W x H frame
 // from packed row src_row[y] of `src`, the sums to accum, the counts to plane (16-byte aligned both).

@@ -28,7 +28,7 @@ __all__ = [
     "MONTECARLO", "MAT", "MAT_TR", "EVENT_NAMES", "SCENE_KEYS",
     "TRAVERSAL_AUTO", "TRAVERSAL_LANE", "TRAVERSAL_WAVE", "TRAVERSAL_STREAM",
     "Transfo", "average", "write_pfm", "write_png", "material", "light", "Hit", "HIT_DTYPE",
-    "Convergence", "DENOISE_K_COLOR", "ERROR_MU_FLOOR",
+    "Convergence", "DENOISE_K_COLOR", "ERROR_MU_FLOOR", "DENOISE_K_VARIANCE",
 ]
 
 MONTECARLO, MAT, MAT_TR = 0, 1, 2
@@ -51,6 +51,9 @@ DENOISE_SIGMA_COLOR = 4.0
 DENOISE_SIGMA_PLANE = 1.0
 # the noise-guided filter's colour width in standard errors of the pixel (the sweep of DESIGN.md §3.8)
 DENOISE_K_COLOR = 64.0
+# the variance filter's colour width in standard deviations of the pixel's carried variance (the
+# sweep of DESIGN.md §3.8: tools/variance_filter_sweep.py)
+DENOISE_K_VARIANCE = 16.0
 # the relative error's floor on the mean luminance: pixels darker than this are
 # measured against it, so that black pixels do not hold a render back
 ERROR_MU_FLOOR = 0.01
@@ -210,6 +213,9 @@ def _declare(L: ctypes.CDLL) -> None:
         "mcpt_last_adaptive_ms": (i, [_vp, fp, fp]),
         "mcpt_denoise_resolved": (i, [_vp, i, f, f]),
         "mcpt_denoise_resolved_guided": (i, [_vp, i, f, f]),
+        "mcpt_denoise_variance": (i, [_vp, i, f, f]),
+        "mcpt_denoise_resolved_variance": (i, [_vp, i, f, f]),
+        "mcpt_read_denoised_variance": (i, [_vp, fp]),
         "mcpt_gather_rows_counted": (i, [_vp, ctypes.POINTER(_vp), i]),
         "mcpt_pass_count": (i, [_vp, ip]),
         "mcpt_pack_counted_device": (i, [_vp, _vp, ctypes.c_size_t]),
@@ -816,6 +822,25 @@ class Renderer:
         _check(lib().mcpt_read_denoised(self._h, _fp(out)), "mcpt_read_denoised")
         return out
 
+    def denoise_variance(self, iterations: int = 5, k_color: float = DENOISE_K_VARIANCE,
+                         sigma_plane: float = DENOISE_SIGMA_PLANE) -> np.ndarray:
+        """mcpt_denoise_variance + mcpt_read_denoised: the variance-propagating filter (the error
+        map's se^2 prefiltered 3x3, carried and filtered through the iterations; the colour width
+        is k_color standard deviations of the variance the iteration's input has).  Needs what
+        denoise_guided needs; read_denoised_variance() returns the filtered variance."""
+        _check(lib().mcpt_denoise_variance(self._h, int(iterations), float(k_color), float(sigma_plane)),
+               "mcpt_denoise_variance")
+        out = np.zeros((self.n_local_rows, self.W, 3), np.float32)
+        _check(lib().mcpt_read_denoised(self._h, _fp(out)), "mcpt_read_denoised")
+        return out
+
+    def read_denoised_variance(self) -> np.ndarray:
+        """mcpt_read_denoised_variance: (local rows, W) f32, the variance the last denoise_variance /
+        denoise_resolved_variance carried to its result."""
+        out = np.zeros((self.n_local_rows, self.W), np.float32)
+        _check(lib().mcpt_read_denoised_variance(self._h, _fp(out)), "mcpt_read_denoised_variance")
+        return out
+
     def last_stats_ms(self) -> Tuple[float, float]:
         """(batch update ms, error kernel ms) of the last of each (0: none yet)."""
         u, e = ctypes.c_float(), ctypes.c_float()
@@ -956,6 +981,16 @@ class Renderer:
         colour, with the error map of the last adaptive_select()."""
         _check(lib().mcpt_denoise_resolved_guided(self._h, int(iterations), float(k_color), float(sigma_plane)),
                "mcpt_denoise_resolved_guided")
+        out = np.zeros((self.n_local_rows, self.W, 3), np.float32)
+        _check(lib().mcpt_read_denoised(self._h, _fp(out)), "mcpt_read_denoised")
+        return out
+
+    def denoise_resolved_variance(self, iterations: int = 5, k_color: float = DENOISE_K_VARIANCE,
+                                  sigma_plane: float = DENOISE_SIGMA_PLANE) -> np.ndarray:
+        """mcpt_denoise_resolved_variance + mcpt_read_denoised: denoise_variance() over the resolved
+        colour (adaptive mode on, or a counted gather with its gathered error map)."""
+        _check(lib().mcpt_denoise_resolved_variance(self._h, int(iterations), float(k_color), float(sigma_plane)),
+               "mcpt_denoise_resolved_variance")
         out = np.zeros((self.n_local_rows, self.W, 3), np.float32)
         _check(lib().mcpt_read_denoised(self._h, _fp(out)), "mcpt_read_denoised")
         return out

@@ -2,11 +2,12 @@
 """An adaptive render over N processes, one per GPU, gathered WITH its per-pixel sample counts
 (DESIGN.md §3.9.1): ShardedRenderer.render_adaptive_until on every rank, gather_counted() to rank 0,
 which writes PREFIX.png (the resolved image, or the filtered one with --denoise N or, with
---denoise-guided N, the noise-guided filter over the shards' gathered error maps) and
+--denoise-guided N / --denoise-variance N, the noise-guided / the variance-propagating filter over
+the shards' gathered error maps) and
 PREFIX_samples.pfm (every pixel's sample count in all three channels, as mcpt_render --aov does).
 
     python tools/adaptive_dist_render.py --gpus 8 --scene 6 --width 1920 --height 1080 \\
-        --spp 1024 --chunk 32 --target-error 0.05 [--denoise 3 | --denoise-guided 3] --out frame
+        --spp 1024 --chunk 32 --target-error 0.05 [--denoise 3 | --denoise-guided 3 | --denoise-variance 3] --out frame
     python -m torch.distributed.run --nproc-per-node 8 tools/adaptive_dist_render.py --gpus 8 ...
 
 Without a launcher (WORLD_SIZE unset) the tool starts its own --gpus N ranks, as
@@ -42,14 +43,19 @@ def parse():
     ap.add_argument("--denoise-guided", type=int, default=0,
                     help="noise-guided a-trous iterations over the resolved image, the colour width from the "
                          "shards' error maps, which travel with the gather (0: none)")
+    ap.add_argument("--denoise-variance", type=int, default=0,
+                    help="variance-propagating a-trous iterations over the resolved image, the variance from the "
+                         "shards' error maps, which travel with the gather (0: none)")
     ap.add_argument("--out", default="adaptive_dist", help="output prefix")
     ap.add_argument("--backend", choices=("auto", "nccl", "gloo"), default="auto")
     ap.add_argument("--timeout", type=float, default=300.0, help="seconds each child rank may run")
     a = ap.parse_args()
     if a.gpus < 1 or a.spp < 1 or a.chunk < 1 or not a.target_error > 0 or not 0 <= a.denoise <= 8:
         ap.error("--gpus, --spp, --chunk must be >= 1, --target-error > 0, --denoise in 0..8")
-    if not 0 <= a.denoise_guided <= 8 or (a.denoise and a.denoise_guided):
-        ap.error("--denoise-guided in 0..8, and one filter only")
+    if not 0 <= a.denoise_guided <= 8 or not 0 <= a.denoise_variance <= 8:
+        ap.error("--denoise-guided and --denoise-variance in 0..8")
+    if (a.denoise > 0) + (a.denoise_guided > 0) + (a.denoise_variance > 0) > 1:
+        ap.error("one filter only")
     return a
 
 
@@ -119,12 +125,15 @@ def rank_main(a) -> int:
         t0 = time.perf_counter()
         rec = sr.render_adaptive_until(ipv, iv, a.target_error, batch=a.chunk, max_passes=a.spp,
                                        min_passes=a.min_passes, bounces=a.bounces)
-        frame = sr.gather_counted(error_map=a.denoise_guided > 0)
+        frame = sr.gather_counted(error_map=a.denoise_guided > 0 or a.denoise_variance > 0)
         if frame is not None:
             counts = frame.read_sample_counts()
             if a.denoise_guided > 0:
                 frame.render_guides(ipv, iv)
                 img = frame.denoise_resolved_guided(a.denoise_guided)
+            elif a.denoise_variance > 0:      # (after both gathers: the rows with their counts, the error map)
+                frame.render_guides(ipv, iv)
+                img = frame.denoise_resolved_variance(a.denoise_variance)
             elif a.denoise > 0:
                 frame.render_guides(ipv, iv)
                 img = frame.denoise_resolved(a.denoise)
@@ -135,7 +144,8 @@ def rank_main(a) -> int:
             mcpt.write_pfm(a.out + "_samples.pfm", np.repeat(counts.astype(np.float32)[..., None], 3, axis=2))
             rec.pop("local")
             print(json.dumps(dict(rec, scene=a.scene, W=W, H=H, n_gpus=world, backend=backend if world > 1 else None,
-                                  denoise=a.denoise, denoise_guided=a.denoise_guided, mean_spp=rec["samples"] / rec["n_px"], wall_s=wall,
+                                  denoise=a.denoise, denoise_guided=a.denoise_guided, denoise_variance=a.denoise_variance,
+                                  mean_spp=rec["samples"] / rec["n_px"], wall_s=wall,
                                   png=a.out + ".png", samples=int(counts.sum()))), flush=True)
     finally:
         if sr is not None:

@@ -9,6 +9,13 @@ warm-up runs, interleaved A/B/A/B so drift hits both alike; HIP-event times
 and iteration (read colour 16 + guides 32, write 16) at the 8 TB/s HBM peak.
 
   python tools/denoise_bench.py [--out profiles/denoise_bench.json] [--repeats 20]
+
+--variance: the variance-propagating filter against the noise-guided one instead,
+same sizes and protocol (64 spp as 4 batches of 16 for the error map; the shipped kernel paths;
+guided / variance interleaved): the first step (slot -1: the averaging, for the variance filter
+with the 3x3 prefilter of se^2 fused in) and every iteration, with a verdict per slot as above.
+
+  python tools/denoise_bench.py --variance [--out profiles/variance_filter_bench.json]
 """
 import argparse
 import json
@@ -31,13 +38,60 @@ def spread(v):
     return {"median_ms": statistics.median(v), "q1_ms": q[0], "q3_ms": q[2], "min_ms": min(v), "max_ms": max(v)}
 
 
+def variance_ab(a):
+    r = mcpt.Renderer(0)
+    r.upload_scene(mcpt.Scene.reference(6))
+    res = {"scene": 6, "spp": a.spp, "batches": 4, "iterations": ITERS, "repeats": a.repeats, "warmup": a.warmup,
+           "k_color": mcpt.DENOISE_K_COLOR, "k_variance": mcpt.DENOISE_K_VARIANCE,
+           "sigma_plane": mcpt.DENOISE_SIGMA_PLANE, "device": torch.cuda.get_device_name(0), "sizes": []}
+    slots = ["first_step"] + [f"step_{1 << s}" for s in range(ITERS)] + ["filter_total"]
+    for W, H in ((1920, 1080), (3840, 2160)):
+        r.set_target(W, H)
+        cam = mcpt.camera_canonical(W, H)
+        r.stats_begin()
+        for k in range(4):
+            r.render(cam[0], cam[1], 1 + k * (a.spp // 4), a.spp // 4, 0.0, 8, 1.0, 0)
+        r.convergence(0.05)
+        r.render_guides(*cam)
+        forms = {"guided": r.denoise_guided, "variance": r.denoise_variance}
+        times = {name: {sl: [] for sl in slots} for name in forms}
+        for k in range(a.warmup + a.repeats):
+            for name, form in forms.items():
+                form(ITERS)
+                if k >= a.warmup:
+                    t = times[name]
+                    t["first_step"].append(r.denoise_iteration_ms(-1))
+                    for s in range(ITERS):
+                        t[f"step_{1 << s}"].append(r.denoise_iteration_ms(s))
+                    t["filter_total"].append(r.last_denoise_ms()[1])
+        r.stats_end()
+        entry = {"W": W, "H": H, "lds_mask": r.last_denoise_path(),
+                 "guided": {sl: spread(v) for sl, v in times["guided"].items()},
+                 "variance": {sl: spread(v) for sl, v in times["variance"].items()}, "verdicts": {}}
+        for sl in slots:
+            g, v = entry["guided"][sl], entry["variance"][sl]
+            entry["verdicts"][sl] = {
+                "verdict": "variance_faster" if v["q3_ms"] < g["q1_ms"] else ("guided_faster" if g["q3_ms"] < v["q1_ms"] else "tie"),
+                "variance_over_guided": v["median_ms"] / g["median_ms"]}
+        res["sizes"].append(entry)
+        print(json.dumps(entry), flush=True)
+    r.close()
+    with open(a.out or os.path.join(REPO, "profiles", "variance_filter_bench.json"), "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "denoise_bench.json"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--variance", action="store_true")
     ap.add_argument("--repeats", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--spp", type=int, default=64)
     a = ap.parse_args()
+    if a.variance:
+        return variance_ab(a)
+    a.out = a.out or os.path.join(REPO, "profiles", "denoise_bench.json")
     r = mcpt.Renderer(0)
     r.upload_scene(mcpt.Scene.reference(6))
     res = {"scene": 6, "spp": a.spp, "iterations": ITERS, "repeats": a.repeats, "warmup": a.warmup,
