@@ -605,6 +605,61 @@ int mcpt_last_adaptive_ms(mcpt_ctx* ctx, float* select_ms, float* render_ms);
 int mcpt_denoise_resolved(mcpt_ctx* ctx, int iterations, float sigma_color, float sigma_plane);
 int mcpt_denoise_resolved_guided(mcpt_ctx* ctx, int iterations, float k_color, float sigma_plane);
 
+/* Adaptive sampling that stops on the DENOISED frame's error (no reference
+ * equivalent): mcpt_adaptive_select's twin whose rule reads the variance the variance-propagating
+ * filter leaves in its image, so that a block retires once the image mcpt_denoise_resolved_variance
+ * shows of it meets the threshold.  One call, three steps on the context's stream:
+ *   A  for every active block the {se, r} of its pixels into the error map and the raw record, as
+ *      mcpt_adaptive_select computes them; no block retires.  Retired blocks keep their entries.
+ *   B  exactly what mcpt_denoise_resolved_variance(ctx, iterations, k_color, sigma_plane) would run
+ *      now: the resolve and the 3x3 prefilter of the map step A wrote, then the iterations, into the
+ *      same result buffers with the same bits.
+ *   C  for every local pixel, with c = {r, g, b, v} step B's result, in binary32 without
+ *      contraction in the order written:
+ *        Yf = (0.2126 c.r + 0.7152 c.g) + 0.0722 c.b;  sef = sqrt(c.v);
+ *        rf = sef / (max(0, Yf) + mu_floor);  rf = 64 if Yf is not finite or not rf <= 64.
+ *      An active block stays active iff its largest rf > threshold, or its largest r (step A's map
+ *      entries) > raw_cap, or it holds fewer than min_passes passes; the maxima run over the
+ *      block's in-frame pixels.  Retired blocks never return.  The active list is rebuilt as
+ *      mcpt_adaptive_select rebuilds it.
+ * raw_cap keeps a block whose filtered variance is small only because a wide colour tolerance
+ * blurred it while its raw error is still large; r is clamped to 64, so raw_cap = 64 turns the guard
+ * off, and raw_cap = threshold keeps every block mcpt_adaptive_select would keep.
+ *
+ * The record: `raw` is mcpt_adaptive_select's record of the same state (n_px, n_above, sum_q, max_r,
+ * mean_r, passes, batches, samples, n_blocks as that call defines them) with n_active_blocks = the
+ * blocks THIS rule keeps; n_above_f, sum_qf (sum of trunc(rf * 65536)), max_rf and mean_rf =
+ * sum_qf / 65536 / n_px are the same record of rf over ALL local pixels, retired blocks' included
+ * (their rf comes from the filter like everyone's).  Integer sums and a maximum: the bits do not
+ * depend on the order.
+ *
+ * Preconditions, in this order: adaptive mode on (else MCPT_ERR_NO_ADAPTIVE); threshold, raw_cap,
+ * mu_floor, k_color and sigma_plane positive and finite, iterations in 0..8, a full-frame target in
+ * row order that holds passes and no gathered count plane or gathered error map (else
+ * MCPT_ERR_INVALID_ARG); statistics on with two batches or more (else MCPT_ERR_NO_STATS); current
+ * guides (else MCPT_ERR_NO_GUIDES).  On any of these nothing changes: not the flags, the map or the
+ * result buffers.
+ *
+ * Afterwards the error map is valid as after a select (mcpt_read_error_map), and the filter's result
+ * buffers hold step B's image as a variance filter's: mcpt_read_denoised, mcpt_read_denoised_variance,
+ * mcpt_last_denoise_ms, mcpt_denoise_iteration_ms and mcpt_last_denoise_path serve it, so every check
+ * leaves the current denoised preview.  mcpt_last_adaptive_ms's select time is steps A + C with the
+ * list scan (step B's is mcpt_last_denoise_ms's filter time).  mcpt_adaptive_select and this call may
+ * alternate freely: both only retire.  Checkpoints need nothing new: the rule is a function of the
+ * accumulator, the counts, the statistics state, the stored map and the guides, and the guides are
+ * rendered again after mcpt_adaptive_checkpoint_load.  Device memory: one more block of partial
+ * records beside the statistics' (4 KiB), nothing per pixel.  Synchronizes once, at the end, for the
+ * record. */
+typedef struct mcpt_adaptive_filtered_t {
+  mcpt_adaptive_t raw;
+  long long n_above_f;
+  unsigned long long sum_qf;
+  float max_rf;
+  double mean_rf;
+} mcpt_adaptive_filtered_t;
+extern int mcpt_adaptive_select_filtered(mcpt_ctx* ctx, float threshold, float raw_cap, float mu_floor, int iterations,
+                                         float k_color, float sigma_plane, mcpt_adaptive_filtered_t* out);
+
 /* DrawSampling's point cloud (DrawSampling/draw_sampling.cpp:144-150, tp/sampling_base.vert
  * seeding, tp/hsphere.vert random_ray): point k = random_ray(normalize(normal), roughness)
  * with seed floatBitsToUint(fseed) + k * nb_used * (11, 43, 67).  out: n × 3 f32 (host). */

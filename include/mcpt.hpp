@@ -502,6 +502,25 @@ class Renderer {
     check(mcpt_adaptive_select(c_, threshold, mu_floor, &rec), "mcpt_adaptive_select");
     return rec;
   }
+  // the select on the denoised frame's error (mcpt_adaptive_select_filtered): the
+  // map, denoise_resolved_variance(iterations, k_color, sigma_plane) on it, then the rule on the
+  // filter's variance; read_denoised / read_denoised_variance return the filter's image.  Needs
+  // render_guides.  raw_cap = 64: no guard on the raw error
+  mcpt_adaptive_filtered_t adaptive_select_filtered(float threshold, float raw_cap = 64.0f,
+                                                    float mu_floor = kErrorMuFloor, int iterations = 5,
+                                                    float k_color = kDenoiseKVariance,
+                                                    float sigma_plane = kDenoiseSigmaPlane) {
+    mcpt_adaptive_filtered_t rec;
+    check(mcpt_adaptive_select_filtered(c_, threshold, raw_cap, mu_floor, iterations, k_color, sigma_plane, &rec),
+          "mcpt_adaptive_select_filtered");
+    return rec;
+  }
+  // local pixels x 3: the last filter run's image
+  std::vector<float> read_denoised() const {
+    std::vector<float> img((size_t)rows_ * W_ * 3);
+    check(mcpt_read_denoised(c_, img.data()), "mcpt_read_denoised");
+    return img;
+  }
   struct AdaptiveInfo { bool on; long long n_active, n_blocks; };
   AdaptiveInfo adaptive_info() const {
     int on = 0; long long a = 0, b = 0;

@@ -25,6 +25,8 @@
 //       error maps are gathered after the rows, mcpt_gather_error_map, for the noise-guided filter)
 //   mcpt_render --scene 6 --spp 16 --chunk 4 --denoise-variance --aov s6 --out s6.png   (the variance-propagating
 //       filter; --aov also writes s6_variance.pfm)
+//   mcpt_render --scene 6 --spp 1024 --chunk 32 --adaptive --target-error 0.05 --target-denoised --out s6.png
+//       (render until the DENOISED image meets the error: mcpt_adaptive_select_filtered; one device)
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -52,6 +54,8 @@ struct Args {
   int denoise_variance = -1;  // --denoise-variance [N]: the variance-propagating filter (-1: off; N defaults to 5)
   // one of the filters that read the error map (statistics on, >= 2 chunks)
   bool noise_filter() const { return denoise_guided >= 0 || denoise_variance >= 0; }
+  int target_denoised = -1;   // --target-denoised [N]: --adaptive selects on the variance filter's error (-1: off; N defaults to 5)
+  float raw_cap = 64.0f;      // --raw-cap R: with --target-denoised a block also stays while its largest raw r > R (64: off)
   bool adaptive = false;      // --adaptive: --target-error is the per-pixel threshold; retired 8x8 blocks stop receiving passes
 };
 
@@ -94,7 +98,18 @@ void usage() {
                "                                               map's variance prefiltered 3x3 and filtered along\n"
                "                                               with the colour; accepted and refused where\n"
                "                                               --denoise-guided is; --aov also writes\n"
-               "                                               PREFIX_variance.pfm)\n");
+               "                                               PREFIX_variance.pfm)\n"
+               "                   [--target-denoised [N]] [--raw-cap R]   (with --adaptive --target-error E, one\n"
+               "                                   device: E bounds the error of the variance-filtered image (N\n"
+               "                                   iterations, default 5) in place of the raw one; a block also stays\n"
+               "                                   while its largest raw r > R (default 64: off); writes the\n"
+               "                                   filtered image as --denoise-variance N would)\n");
+}
+
+// a refused combination: why, then the usage (parse's false)
+bool refuse(const char* why) {
+  std::fprintf(stderr, "mcpt_render: %s\n", why);
+  return false;
 }
 
 bool parse(int argc, char** argv, Args& a) {
@@ -123,6 +138,12 @@ bool parse(int argc, char** argv, Args& a) {
       if (a.denoise_variance > 8) return false;
       continue;
     }
+    if (k == "--target-denoised") {
+      a.target_denoised = 5;
+      if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') a.target_denoised = std::atoi(argv[++i]);
+      if (a.target_denoised > 8) return false;
+      continue;
+    }
     if (i + 1 >= argc) return false;
     const char* v = argv[++i];
     if (k == "--scene") a.scene = std::atoi(v);
@@ -149,6 +170,10 @@ bool parse(int argc, char** argv, Args& a) {
       a.target_error = std::atof(v);
       if (!(a.target_error > 0.0)) return false;
     }
+    else if (k == "--raw-cap") {
+      a.raw_cap = (float)std::atof(v);
+      if (!(a.raw_cap > 0.0f)) return false;
+    }
     else if (k == "--variant") {
       const std::string s = v;
       a.variant = s == "mat" ? MCPT_MAT : (s == "mat_tr" ? MCPT_MAT_TR : MCPT_MONTECARLO);
@@ -172,6 +197,15 @@ bool parse(int argc, char** argv, Args& a) {
   if (!a.devices.empty() && a.adaptive && a.noise_filter()) return false;
   if ((a.denoise >= 0) + (a.denoise_guided >= 0) + (a.denoise_variance >= 0) > 1) return false;   // one filter
   if (a.adaptive && !(a.target_error > 0.0)) return false;   // adaptive sampling needs its threshold
+  if (a.target_denoised >= 0) {
+    if (!a.adaptive || !(a.target_error > 0.0))
+      return refuse("--target-denoised is a rule of --adaptive --target-error E: give both");
+    if (!a.devices.empty())   // (a shard is not a full frame: the filter has no rows beyond its own)
+      return refuse("--target-denoised needs the full frame on one device: not with --devices");
+    if (a.denoise >= 0 || a.noise_filter())
+      return refuse("--target-denoised writes its own variance-filtered image: no other --denoise* with it");
+    a.denoise_variance = a.target_denoised;   // the image, the AOVs and the JSON fields of --denoise-variance N
+  }
   return a.width > 0 && a.height > 0 && a.spp >= 0 && a.chunk > 0 && a.subsampling >= 0 && a.subsampling < 16;
 }
 
@@ -291,7 +325,10 @@ int main(int argc, char** argv) {
                               "scene=%d W=%d H=%d bounces=%d ior=%a light=%a date=%a variant=%d first=%d chunk=%d", a.scene,
                               W, H, a.bounces, a.ior, a.light, a.date, a.variant, a.first_pass, a.chunk);
       // (adaptive: the threshold decides which blocks the later chunks reach)
-      if (a.adaptive) std::snprintf(tag + len, sizeof(tag) - (size_t)len, " adaptive=%a", a.target_error);
+      if (a.adaptive) len += std::snprintf(tag + len, sizeof(tag) - (size_t)len, " adaptive=%a", a.target_error);
+      // (the rule too: it decides which blocks the later chunks reach)
+      if (a.target_denoised >= 0)
+        std::snprintf(tag + len, sizeof(tag) - (size_t)len, " denoised=%d cap=%a", a.target_denoised, a.raw_cap);
       const bool resumed_adaptive = a.adaptive && !a.resume.empty();
       int next = a.first_pass;
       if (resumed_adaptive) next = r.load_adaptive_checkpoint(a.resume, tag);   // (statistics and the mode on, as saved)
@@ -304,7 +341,9 @@ int main(int argc, char** argv) {
       bool have_rec = false, converged = false;
       int calls = 0;
       mcpt_adaptive_t arec{};
+      mcpt_adaptive_filtered_t frec{};
       bool have_arec = false;
+      if (a.target_denoised >= 0) r.render_guides(cam);   // (after a resume too: a checkpoint holds no guides)
       if (a.adaptive && !resumed_adaptive) r.adaptive_begin(0);
       if (resumed_adaptive) {   // the chunks so far were one batch each; a select has run from the second on
         calls = r.stats_info().batches;
@@ -320,7 +359,13 @@ int main(int argc, char** argv) {
         kernel_ms += ren;
         rendered = done + n;
         if (++calls >= 2) {
-          arec = r.adaptive_select((float)a.target_error);
+          if (a.target_denoised >= 0) {
+            frec = r.adaptive_select_filtered((float)a.target_error, a.raw_cap, mcpt::Renderer::kErrorMuFloor,
+                                              a.target_denoised);
+            arec = frec.raw;
+          } else {
+            arec = r.adaptive_select((float)a.target_error);
+          }
           have_arec = true;
           converged = arec.n_active_blocks == 0;
         }
@@ -346,6 +391,13 @@ int main(int argc, char** argv) {
         char buf[400];
         if (have_arec) {
           shard_json += adaptive_json(a.target_error, converged, arec);
+          if (a.target_denoised >= 0) {
+            std::snprintf(buf, sizeof(buf),
+                          ", \"target_denoised\": %d, \"raw_cap\": %g, \"mean_rf\": %.6f, \"max_rf\": %.6f, "
+                          "\"n_above_f\": %lld, \"sum_qf\": %llu",
+                          a.target_denoised, a.raw_cap, frec.mean_rf, frec.max_rf, frec.n_above_f, frec.sum_qf);
+            shard_json += buf;
+          }
         } else {   // no select in this run (fewer than two chunks, or a resume with nothing left to do)
           long long samples = 0;
           for (int c : r.read_sample_counts()) samples += c;

@@ -11,6 +11,10 @@
 //    computed: their stored map entries enter the frame record.  The record's sums are integers and
 //    max_r a bit pattern, reduced per wave, per workgroup and into kStatsRecSlots partial records as
 //    the error kernel's are: the bits do not depend on the order.
+//  * select_kernel<false> and filtered_select_kernel: the select on the denoised frame's error
+//    (mcpt_adaptive_select_filtered): the first writes the map and the raw record
+//    and retires nobody, the variance filter runs on that map, the second reads the filter's
+//    {rgb, variance} and applies the rule.
 //  * compact_kernel: the active block ids, ascending, by a single-workgroup scan over the flags
 //    (ballots inside a wave, the waves' counts through LDS, a running base): no atomic append, so
 //    the list does not depend on timing.  4K has 129,600 blocks: 127 steps of 1,024.
@@ -43,6 +47,9 @@ __global__ __launch_bounds__(256) void adaptive_reset_kernel(AdaptiveTarget t, i
   list[b] = b;
 }
 
+// kRetire false: mcpt_adaptive_select_filtered's step A: the map and the record as
+// above, every flag left as it is and word 4 (the active blocks) left to filtered_select_kernel
+template <bool kRetire>
 __global__ __launch_bounds__(256) void select_kernel(AdaptiveTarget t, const float4* __restrict__ st,
                                                      float2* __restrict__ emap, float nf, float bm1f, float mu_floor,
                                                      float threshold, int min_passes,
@@ -82,9 +89,9 @@ __global__ __launch_bounds__(256) void select_kernel(AdaptiveTarget t, const flo
     const bool stay = act && (__uint_as_float(bmax) > threshold || passes < min_passes);
     const unsigned n_in = (unsigned)__popcll(__ballot(in));
     if (lane == 0) {
-      if (act) t.flags[blk] = stay ? 1 : 0;
+      if (kRetire && act) t.flags[blk] = stay ? 1 : 0;
       samples += (unsigned long long)n_in * (unsigned long long)((long long)t.p0 + passes);
-      n_act += stay ? 1u : 0u;
+      n_act += (kRetire && stay) ? 1u : 0u;
     }
   }
 #pragma unroll
@@ -112,6 +119,84 @@ __global__ __launch_bounds__(256) void select_kernel(AdaptiveTarget t, const flo
     if (m) atomicMax(reinterpret_cast<unsigned*>(slot + 2), m);
     if (v[2]) atomicAdd(slot + 3, v[2]);
     if (v[3]) atomicAdd(slot + 4, v[3]);
+  }
+}
+
+// mcpt_adaptive_select_filtered's step C: one wave per block, the grid capped and
+// stepped as select_kernel's.  dn is the variance filter's result over the full frame in row order
+// {r, g, b, v}; a pixel's filtered relative error is rf = sqrt(v) / (max(0, Y(rgb)) + mu_floor),
+// clamped to 64 as pixel_error clamps r (binary32, no contraction, in the order written).  The
+// filtered record {n_above_f, sum_qf, max_rf's bits} runs over every in-frame pixel, retired blocks
+// included; an active block stays active iff its largest rf > threshold or its largest r (the map
+// entries step A wrote) > raw_cap or it holds fewer than min_passes passes.  rec: select_kernel's
+// partial records, [0] n_above_f, [1] sum_qf, [2] max_rf's bits, [4] active blocks.
+__global__ __launch_bounds__(256) void filtered_select_kernel(AdaptiveTarget t, const float4* __restrict__ dn,
+                                                              const float2* __restrict__ emap, float mu_floor,
+                                                              float threshold, float raw_cap, int min_passes,
+                                                              unsigned long long* __restrict__ rec) {
+  __shared__ unsigned long long s_sum[4][3];   // per wave: n_above_f, sum_qf, active blocks
+  __shared__ unsigned s_max[4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  unsigned long long above = 0, qsum = 0;   // this lane's pixels
+  unsigned fmax = 0;
+  unsigned long long n_act = 0;   // this wave's blocks (lane 0 counts)
+  for (long long blk = (long long)blockIdx.x * 4 + wave; blk < t.n_blocks; blk += (long long)gridDim.x * 4) {
+    const int bx = (int)(blk % t.blocks_x), by = (int)(blk / t.blocks_x);
+    const int x = bx * 8 + (lane & 7), lr = by * 8 + (lane >> 3);
+    const bool in = x < t.W && lr < t.n_local_rows;
+    const long long i = (long long)lr * t.W + x;
+    const bool act = t.flags[blk] != 0;   // (wave-uniform)
+    const int passes = t.passes[blk];
+    float rf = 0.0f, r = 0.0f;
+    if (in) {
+      const float4 c = dn[i];
+      const float yf = (0.2126f * c.x + 0.7152f * c.y) + 0.0722f * c.z;
+      const float sef = sqrt_rn(c.w);
+      rf = sef / (gmax(0.0f, yf) + mu_floor);
+      if (!finite32(yf) || !(rf <= 64.0f)) rf = 64.0f;
+      r = emap[i].y;
+      above += (rf > threshold) ? 1u : 0u;
+      qsum += error_q(rf);
+    }
+    unsigned bf = __float_as_uint(rf), br = __float_as_uint(r);   // both >= 0: the bits order as the values
+    fmax = bf > fmax ? bf : fmax;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      const unsigned of = __shfl_xor(bf, off, 64), orr = __shfl_xor(br, off, 64);
+      bf = of > bf ? of : bf;
+      br = orr > br ? orr : br;
+    }
+    const bool stay =
+        act && (__uint_as_float(bf) > threshold || __uint_as_float(br) > raw_cap || passes < min_passes);
+    if (lane == 0) {
+      if (act) t.flags[blk] = stay ? 1 : 0;
+      n_act += stay ? 1u : 0u;
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    above += __shfl_down(above, off, 64);
+    qsum += __shfl_down(qsum, off, 64);
+    const unsigned o = __shfl_down(fmax, off, 64);
+    fmax = o > fmax ? o : fmax;
+  }
+  if (lane == 0) {
+    s_sum[wave][0] = above; s_sum[wave][1] = qsum; s_sum[wave][2] = n_act;
+    s_max[wave] = fmax;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long v[3] = {0, 0, 0};
+    unsigned m = 0;
+    for (int w = 0; w < 4; ++w) {
+      for (int k = 0; k < 3; ++k) v[k] += s_sum[w][k];
+      m = s_max[w] > m ? s_max[w] : m;
+    }
+    unsigned long long* slot = rec + (size_t)(blockIdx.x % kStatsRecSlots) * kStatsRecStride;
+    if (v[0]) atomicAdd(slot + 0, v[0]);
+    if (v[1]) atomicAdd(slot + 1, v[1]);
+    if (m) atomicMax(reinterpret_cast<unsigned*>(slot + 2), m);
+    if (v[2]) atomicAdd(slot + 4, v[2]);
   }
 }
 
@@ -252,15 +337,32 @@ hipError_t mcpt_launch_adaptive_reset(const mcpt::AdaptiveTarget& t, int* list, 
   return hipGetLastError();
 }
 
+// the select kernels' grid: a workgroup of four waves per four blocks, capped
+static dim3 select_grid(int n_blocks) {
+  return dim3((unsigned)std::min<long long>(((long long)n_blocks + 3) / 4, mcpt::kSelectMaxBlocks));
+}
+
 hipError_t mcpt_launch_adaptive_select(const mcpt::AdaptiveTarget& t, const float4* state, float2* emap,
                                        long long passes, int batches, float mu_floor, float threshold, int min_passes,
-                                       unsigned long long* rec, hipStream_t stream) {
+                                       bool retire, unsigned long long* rec, hipStream_t stream) {
   hipError_t e = hipMemsetAsync(rec, 0, sizeof(unsigned long long) * mcpt::kStatsRecWords, stream);
   if (e != hipSuccess || t.n_blocks <= 0) return e;
-  const long long groups = ((long long)t.n_blocks + 3) / 4;
-  hipLaunchKernelGGL(mcpt::select_kernel, dim3((unsigned)std::min<long long>(groups, mcpt::kSelectMaxBlocks)),
-                     dim3(256), 0, stream, t, state, emap, (float)passes, (float)(batches - 1), mu_floor, threshold,
-                     min_passes, rec);
+  if (retire)
+    hipLaunchKernelGGL(mcpt::select_kernel<true>, select_grid(t.n_blocks), dim3(256), 0, stream, t, state, emap,
+                       (float)passes, (float)(batches - 1), mu_floor, threshold, min_passes, rec);
+  else
+    hipLaunchKernelGGL(mcpt::select_kernel<false>, select_grid(t.n_blocks), dim3(256), 0, stream, t, state, emap,
+                       (float)passes, (float)(batches - 1), mu_floor, threshold, min_passes, rec);
+  return hipGetLastError();
+}
+
+hipError_t mcpt_launch_adaptive_select_filtered(const mcpt::AdaptiveTarget& t, const float4* dn, const float2* emap,
+                                                float mu_floor, float threshold, float raw_cap, int min_passes,
+                                                unsigned long long* rec, hipStream_t stream) {
+  hipError_t e = hipMemsetAsync(rec, 0, sizeof(unsigned long long) * mcpt::kStatsRecWords, stream);
+  if (e != hipSuccess || t.n_blocks <= 0) return e;
+  hipLaunchKernelGGL(mcpt::filtered_select_kernel, select_grid(t.n_blocks), dim3(256), 0, stream, t, dn, emap, mu_floor,
+                     threshold, raw_cap, min_passes, rec);
   return hipGetLastError();
 }
 

@@ -359,10 +359,11 @@ int mcpt_adaptive_select(mcpt_ctx* c, float threshold, float mu_floor, mcpt_adap
   int* d_count = c->d_ad_list + c->ad_n_blocks;
   HIP_OR_RETURN(hipEventRecord(c->ad_ev[0], c->stream));
   HIP_OR_RETURN(mcpt_launch_adaptive_select(t, c->d_stats, c->d_emap, c->stats_passes, c->stats_batches, mu_floor,
-                                            threshold, c->ad_min_passes, c->d_conv, c->stream));
+                                            threshold, c->ad_min_passes, true, c->d_conv, c->stream));
   HIP_OR_RETURN(mcpt_launch_adaptive_compact(t, c->d_ad_list, d_count, c->stream));
   HIP_OR_RETURN(hipEventRecord(c->ad_ev[1], c->stream));
   c->ad_select_timed = true;
+  c->ad_select_split = false;
   c->emap_valid = true;
   unsigned long long part[mcpt::kStatsRecWords] = {};
   int n_list = 0;
@@ -378,6 +379,79 @@ int mcpt_adaptive_select(mcpt_ctx* c, float threshold, float mu_floor, mcpt_adap
   out->n_active_blocks = n_list;
   out->n_blocks = c->ad_n_blocks;
   out->samples = (long long)h[3];
+  return MCPT_OK;
+}
+
+// The select on the denoised frame's error.  Step A: select_kernel<false>, the map
+// and the raw record, no flag changes.  Step B: denoise_run's resolved variance form on that map.
+// Step C: filtered_select_kernel on the filter's result, then the scan.  Every precondition is
+// checked before step A, so a refusal leaves the flags, the map and the result buffers alone.
+int mcpt_adaptive_select_filtered(mcpt_ctx* c, float threshold, float raw_cap, float mu_floor, int iterations,
+                                  float k_color, float sigma_plane, mcpt_adaptive_filtered_t* out) {
+  if (!c || !out) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  if (!c->ad_on)
+    return set_err(MCPT_ERR_NO_ADAPTIVE, "mcpt_adaptive_select_filtered: adaptive mode is off (mcpt_adaptive_begin)");
+  for (float v : {threshold, raw_cap, mu_floor, k_color, sigma_plane})
+    if (!(v > 0.0f) || !std::isfinite(v))
+      return set_err(MCPT_ERR_INVALID_ARG,
+                     "mcpt_adaptive_select_filtered: threshold, raw_cap, mu_floor, k_color and sigma_plane must be "
+                     "positive and finite");
+  if (iterations < 0 || iterations > 8)
+    return set_err(MCPT_ERR_INVALID_ARG, "mcpt_adaptive_select_filtered: iterations not in 0..8");
+  if (!plan::is_full_frame(c->rows, c->H))
+    return set_err(MCPT_ERR_INVALID_ARG, "mcpt_adaptive_select_filtered: needs a full-frame target (a shard is filtered after its gather)");
+  // (the filter would read a gathered frame's counts and map, the rule this window's)
+  if (c->plane_valid || c->emap_plane_valid)
+    return set_err(MCPT_ERR_INVALID_ARG, "mcpt_adaptive_select_filtered: the context holds a gathered frame's counts or error map");
+  if (c->pass_count <= 0)
+    return set_err(MCPT_ERR_INVALID_ARG, "mcpt_adaptive_select_filtered: the accumulator holds no passes");
+  if (!c->stats_on) return set_err(MCPT_ERR_NO_STATS, "mcpt_adaptive_select_filtered: statistics are off (mcpt_stats_begin)");
+  if (c->stats_batches < 2) return set_err(MCPT_ERR_NO_STATS, "mcpt_adaptive_select_filtered: needs two batches or more");
+  if (!c->guides_valid)
+    return set_err(MCPT_ERR_NO_GUIDES, "mcpt_adaptive_select_filtered: no guides rendered for this target and scene");
+  HIP_OR_RETURN(hipSetDevice(c->device));
+  HIP_OR_RETURN(ensure_timing_events(c->ad_ev, 2));
+  HIP_OR_RETURN(ensure_timing_events(c->ad_ev + 4, 2));
+  HIP_OR_RETURN(ensure_timing_events(c->dn_ev, 10));
+  HIP_OR_RETURN(ensure_denoise_buffers(c));
+  if (!c->d_conv_f) HIP_OR_RETURN(hipMalloc(&c->d_conv_f, sizeof(unsigned long long) * mcpt::kStatsRecWords));
+  const mcpt::AdaptiveTarget t = adaptive_target(c);
+  int* d_count = c->d_ad_list + c->ad_n_blocks;
+  HIP_OR_RETURN(hipEventRecord(c->ad_ev[0], c->stream));
+  HIP_OR_RETURN(mcpt_launch_adaptive_select(t, c->d_stats, c->d_emap, c->stats_passes, c->stats_batches, mu_floor,
+                                            threshold, c->ad_min_passes, false, c->d_conv, c->stream));
+  HIP_OR_RETURN(hipEventRecord(c->ad_ev[1], c->stream));
+  c->emap_valid = true;
+  OK_OR_RETURN(denoise_run(c, iterations, k_color, sigma_plane, true, true, true));
+  HIP_OR_RETURN(hipEventRecord(c->ad_ev[4], c->stream));
+  HIP_OR_RETURN(mcpt_launch_adaptive_select_filtered(t, c->d_dn[c->dn_result], c->d_emap, mu_floor, threshold, raw_cap,
+                                                     c->ad_min_passes, c->d_conv_f, c->stream));
+  HIP_OR_RETURN(mcpt_launch_adaptive_compact(t, c->d_ad_list, d_count, c->stream));
+  HIP_OR_RETURN(hipEventRecord(c->ad_ev[5], c->stream));
+  c->ad_select_timed = true;
+  c->ad_select_split = true;
+  unsigned long long part[mcpt::kStatsRecWords] = {}, part_f[mcpt::kStatsRecWords] = {};
+  int n_list = 0;
+  HIP_OR_RETURN(hipMemcpyAsync(part, c->d_conv, sizeof(part), hipMemcpyDeviceToHost, c->stream));
+  HIP_OR_RETURN(hipMemcpyAsync(part_f, c->d_conv_f, sizeof(part_f), hipMemcpyDeviceToHost, c->stream));
+  HIP_OR_RETURN(hipMemcpyAsync(&n_list, d_count, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIP_OR_RETURN(hipStreamSynchronize(c->stream));
+  unsigned long long h[5] = {0, 0, 0, 0, 0}, hf[5] = {0, 0, 0, 0, 0};
+  reduce_stats_records(part, 5, h);
+  reduce_stats_records(part_f, 5, hf);
+  if (n_list < 0 || n_list > c->ad_n_blocks || (unsigned long long)n_list != hf[4])
+    return set_err(MCPT_ERR_HIP, "mcpt_adaptive_select_filtered: the active list and the block flags disagree");
+  c->ad_n_list = n_list;
+  fill_frame_record(c, h, &out->raw);
+  out->raw.n_active_blocks = n_list;
+  out->raw.n_blocks = c->ad_n_blocks;
+  out->raw.samples = (long long)h[3];
+  const long long n = (long long)c->n_local_rows * c->W;
+  out->n_above_f = (long long)hf[0];
+  out->sum_qf = hf[1];
+  const unsigned mb = (unsigned)(hf[2] & 0xffffffffull);
+  std::memcpy(&out->max_rf, &mb, sizeof(float));
+  out->mean_rf = n > 0 ? (double)hf[1] / 65536.0 / (double)n : 0.0;
   return MCPT_OK;
 }
 
@@ -575,6 +649,11 @@ int mcpt_last_adaptive_ms(mcpt_ctx* c, float* select_ms, float* render_ms) {
   if (!c) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
   HIP_OR_RETURN(hipSetDevice(c->device));
   OK_OR_RETURN(pair_ms(c->ad_select_timed, c->ad_ev[0], c->ad_ev[1], select_ms));
+  if (select_ms && c->ad_select_timed && c->ad_select_split) {   // a filtered select: steps A + C, not the filter between
+    float tail = 0.0f;
+    OK_OR_RETURN(pair_ms(true, c->ad_ev[4], c->ad_ev[5], &tail));
+    *select_ms += tail;
+  }
   return pair_ms(c->ad_render_timed, c->ad_ev[2], c->ad_ev[3], render_ms);
 }
 

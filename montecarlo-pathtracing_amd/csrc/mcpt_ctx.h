@@ -160,7 +160,11 @@ struct mcpt_ctx {
   int ad_p0 = 0;                    // the accumulator's pass count at mcpt_adaptive_begin
   int ad_min_passes = 0;
   bool ad_select_timed = false, ad_render_timed = false;
-  hipEvent_t ad_ev[4] = {};         // around the last select [0, 1] and the last adaptive render [2, 3]
+  bool ad_select_split = false;     // the last select was a filtered one: its time is [0, 1] + [4, 5]
+  // around the last select [0, 1] and the last adaptive render [2, 3]; a filtered select
+  // (DESIGN.md §3.9.2): [0, 1] around its step A, [4, 5] around its step C and the scan
+  hipEvent_t ad_ev[6] = {};
+  unsigned long long* d_conv_f = nullptr;   // the filtered select's partial records (as d_conv; its lifetime)
   // per-pixel sample counts of a gathered frame (mcpt_gather_rows_counted): the
   // count plane, 4 B per local pixel, allocated by the first counted gather after a
   // mcpt_set_target*, freed by the next one and mcpt_destroy; valid until the accumulator changes
@@ -196,8 +200,8 @@ inline void free_denoise(mcpt_ctx* c) {
 }
 
 inline void free_stats(mcpt_ctx* c) {
-  (void)hipFree(c->d_stats); (void)hipFree(c->d_emap); (void)hipFree(c->d_conv);
-  c->d_stats = nullptr; c->d_emap = nullptr; c->d_conv = nullptr;
+  (void)hipFree(c->d_stats); (void)hipFree(c->d_emap); (void)hipFree(c->d_conv); (void)hipFree(c->d_conv_f);
+  c->d_stats = nullptr; c->d_emap = nullptr; c->d_conv = nullptr; c->d_conv_f = nullptr;
   c->stats_on = false; c->stats_passes = 0; c->stats_batches = 0; c->emap_valid = false;
   c->stats_update_timed = false; c->stats_error_timed = false;
 }
@@ -206,7 +210,7 @@ inline void free_adaptive(mcpt_ctx* c) {
   (void)hipFree(c->d_ad_flags); (void)hipFree(c->d_ad_passes); (void)hipFree(c->d_ad_list);
   c->d_ad_flags = nullptr; c->d_ad_passes = nullptr; c->d_ad_list = nullptr;
   c->ad_on = false; c->ad_n_blocks = 0; c->ad_n_list = 0;
-  c->ad_select_timed = false; c->ad_render_timed = false;
+  c->ad_select_timed = false; c->ad_render_timed = false; c->ad_select_split = false;
 }
 
 inline void free_count_plane(mcpt_ctx* c) {

@@ -272,10 +272,18 @@ hipError_t mcpt_launch_render_list(const mcpt::RenderParams& p, hipStream_t stre
 hipError_t mcpt_launch_combine_list(const mcpt::RenderParams& p, hipStream_t stream);
 hipError_t mcpt_launch_adaptive_reset(const mcpt::AdaptiveTarget& t, int* list, int* count, hipStream_t stream);
 // zeroes rec, then for every active block {se, r} of its pixels into emap and its new flag; every
-// block's share of the record from fresh (active) or stored (retired) map values
+// block's share of the record from fresh (active) or stored (retired) map values.  retire false: no
+// flag changes and word [4] stays 0 (the filtered select's step A)
 hipError_t mcpt_launch_adaptive_select(const mcpt::AdaptiveTarget& t, const float4* state, float2* emap,
                                        long long passes, int batches, float mu_floor, float threshold, int min_passes,
-                                       unsigned long long* rec, hipStream_t stream);
+                                       bool retire, unsigned long long* rec, hipStream_t stream);
+// the filtered select's step C: zeroes rec, then from the variance filter's result
+// dn (full frame, row order, {rgb, variance}) every pixel's rf into the record ([0] n_above_f, [1]
+// sum_qf, [2] max_rf's bits, [4] active blocks) and every active block's new flag: it stays iff its
+// largest rf > threshold, its largest map r > raw_cap or it holds fewer than min_passes passes
+hipError_t mcpt_launch_adaptive_select_filtered(const mcpt::AdaptiveTarget& t, const float4* dn, const float2* emap,
+                                                float mu_floor, float threshold, float raw_cap, int min_passes,
+                                                unsigned long long* rec, hipStream_t stream);
 // list = the ids of the flagged blocks, ascending; count[0] = how many (an ordered scan)
 hipError_t mcpt_launch_adaptive_compact(const mcpt::AdaptiveTarget& t, int* list, int* count, hipStream_t stream);
 // passes[b] += n for the listed blocks (list null: for every block)

@@ -57,6 +57,7 @@ DENOISE_K_VARIANCE = 16.0
 # the relative error's floor on the mean luminance: pixels darker than this are
 # measured against it, so that black pixels do not hold a render back
 ERROR_MU_FLOOR = 0.01
+NO_GUIDES = -7     # MCPT_ERR_NO_GUIDES
 NO_STATS = -8      # MCPT_ERR_NO_STATS
 NO_ADAPTIVE = -9   # MCPT_ERR_NO_ADAPTIVE
 
@@ -76,6 +77,13 @@ class Adaptive(ctypes.Structure):
     """mcpt_adaptive_t (include/mcpt.h): the frame record of an adaptive select."""
     _fields_ = Convergence._fields_ + [("n_active_blocks", ctypes.c_longlong), ("n_blocks", ctypes.c_longlong),
                                        ("samples", ctypes.c_longlong)]
+
+
+class AdaptiveFiltered(ctypes.Structure):
+    """mcpt_adaptive_filtered_t (include/mcpt.h): the raw and the filtered frame record of a select on
+    the denoised frame's error."""
+    _fields_ = [("raw", Adaptive), ("n_above_f", ctypes.c_longlong), ("sum_qf", ctypes.c_ulonglong),
+                ("max_rf", ctypes.c_float), ("mean_rf", ctypes.c_double)]
 
 
 class AdaptiveCheckpoint(ctypes.Structure):
@@ -205,6 +213,7 @@ def _declare(L: ctypes.CDLL) -> None:
         "mcpt_adaptive_begin": (i, [_vp, i]),
         "mcpt_adaptive_end": (i, [_vp]),
         "mcpt_adaptive_select": (i, [_vp, f, f, ctypes.POINTER(Adaptive)]),
+        "mcpt_adaptive_select_filtered": (i, [_vp, f, f, f, i, f, f, ctypes.POINTER(AdaptiveFiltered)]),
         "mcpt_read_active_blocks": (i, [_vp, ip, i, ip]),
         "mcpt_render_adaptive": (i, [_vp, fp, fp, i, i, f, i, f, i]),
         "mcpt_read_sample_counts": (i, [_vp, ip]),
@@ -897,6 +906,29 @@ class Renderer:
                "mcpt_adaptive_select")
         return {k: getattr(rec, k) for k, _ in Adaptive._fields_}
 
+    def adaptive_select_filtered(self, threshold: float, raw_cap: float = 64.0, mu_floor: float = ERROR_MU_FLOOR,
+                                 iterations: int = 5, k_color: float = DENOISE_K_VARIANCE,
+                                 sigma_plane: float = DENOISE_SIGMA_PLANE) -> dict:
+        """mcpt_adaptive_select_filtered: the select on the denoised frame's error.  Writes the error
+        map, runs denoise_resolved_variance(iterations, k_color, sigma_plane) on it and retires the
+        active blocks whose largest filtered error rf <= threshold and largest raw r <= raw_cap (and
+        that hold min_passes).  adaptive_select()'s keys (n_active_blocks: what this rule keeps) plus
+        n_above_f, sum_qf, max_rf, mean_rf of rf over all local pixels.  read_denoised() /
+        read_denoised_variance() then return the filter's image.  Needs render_guides.  Synchronizes."""
+        rec = AdaptiveFiltered()
+        _check(lib().mcpt_adaptive_select_filtered(self._h, float(threshold), float(raw_cap), float(mu_floor),
+                                                   int(iterations), float(k_color), float(sigma_plane),
+                                                   ctypes.byref(rec)), "mcpt_adaptive_select_filtered")
+        out = {k: getattr(rec.raw, k) for k, _ in Adaptive._fields_}
+        out.update({k: getattr(rec, k) for k in ("n_above_f", "sum_qf", "max_rf", "mean_rf")})
+        return out
+
+    def read_denoised(self) -> np.ndarray:
+        """mcpt_read_denoised: (local rows, W, 3) f32, the last filter run's image."""
+        out = np.zeros((self.n_local_rows, self.W, 3), np.float32)
+        _check(lib().mcpt_read_denoised(self._h, _fp(out)), "mcpt_read_denoised")
+        return out
+
     def adaptive_info(self) -> dict:
         """{"on", "n_active", "n_blocks"} of the adaptive mode."""
         on, a, b = ctypes.c_int(), ctypes.c_longlong(), ctypes.c_longlong()
@@ -938,15 +970,26 @@ class Renderer:
     def render_adaptive_until(self, invPV, invV, threshold: float, batch: int = 32, max_passes: int = 4096,
                               min_passes: int = 0, check_every: int = 1, first_pass: int = 1, date: float = 0.0,
                               bounces: int = 3, refract_ind: float = 1.0, variant: int = MONTECARLO,
-                              mu_floor: float = ERROR_MU_FLOOR) -> dict:
+                              mu_floor: float = ERROR_MU_FLOOR, filtered: bool = False, raw_cap: float = 64.0,
+                              iterations: int = 5, k_color: float = DENOISE_K_VARIANCE,
+                              sigma_plane: float = DENOISE_SIGMA_PLANE) -> dict:
         """Begin a statistics window and the adaptive mode, then render passes first_pass,
         first_pass + 1, ... in calls of `batch` passes for the active blocks only, selecting after
         every `check_every` calls (from the second batch on, and at the cap), until no block is
         active or `max_passes` passes are rendered.  Returns the last select's record plus
         "rendered" (the passes the longest-lived blocks received); the mode stays on, so that
-        read_resolved() and read_sample_counts() serve the result."""
+        read_resolved() and read_sample_counts() serve the result.  filtered: the selects are
+        adaptive_select_filtered(threshold, raw_cap, mu_floor, iterations, k_color, sigma_plane), the
+        guides are rendered first unless they are current, and read_denoised() serves the last
+        select's image."""
         if batch <= 0 or check_every <= 0 or max_passes <= 0 or not threshold > 0:
             raise MCPTError("render_adaptive_until: batch, check_every, max_passes and threshold must be positive")
+        if filtered:
+            select = lambda: self.adaptive_select_filtered(threshold, raw_cap, mu_floor, iterations, k_color, sigma_plane)
+            if lib().mcpt_read_guides(self._h, None, None) == NO_GUIDES:      # (copies nothing: the guides' state alone)
+                self.render_guides(invPV, invV)
+        else:
+            select = lambda: self.adaptive_select(threshold, mu_floor)
         self.stats_begin()
         self.adaptive_begin(min_passes)
         done, calls, rec = 0, 0, None
@@ -956,11 +999,11 @@ class Renderer:
             done += n
             calls += 1
             if calls >= 2 and (calls % check_every == 0 or done >= max_passes):
-                rec = self.adaptive_select(threshold, mu_floor)
+                rec = select()
                 if rec["n_active_blocks"] == 0:
                     break
         if rec is None:
-            rec = self.adaptive_select(threshold, mu_floor)     # (fewer than two batches: MCPT_ERR_NO_STATS)
+            rec = select()     # (fewer than two batches: MCPT_ERR_NO_STATS)
         rec["rendered"] = done
         return rec
 
