@@ -660,6 +660,49 @@ typedef struct mcpt_adaptive_filtered_t {
 extern int mcpt_adaptive_select_filtered(mcpt_ctx* ctx, float threshold, float raw_cap, float mu_floor, int iterations,
                                          float k_color, float sigma_plane, mcpt_adaptive_filtered_t* out);
 
+/* Queued adaptive runs (no reference equivalent): `rounds` rounds of an adaptive
+ * render loop on the context's stream with ONE host wait, at the end.  The call is equivalent, bit
+ * for bit in every piece of state and every record, to this loop over the calls above:
+ *   for i in 0 .. rounds-1:
+ *     if the active list is empty: stop
+ *     mcpt_render_adaptive(first_pass + i * n_passes, n_passes, ...)
+ *     if the window holds >= 2 batches and ((i + 1) % check_every == 0 or i == rounds - 1):
+ *       mcpt_adaptive_select(threshold, mu_floor, &records[k++])
+ * (mcpt_adaptive_run_filtered: mcpt_adaptive_select_filtered with its further arguments).  State is
+ * the accumulator, the block flags and passes, the active list and its length, the statistics state
+ * and the error map, the pass count, the window's passes and batches and, for the filtered form, the
+ * filter's result buffers: afterwards every other call continues as if the loop had run.  The host
+ * sizes the launches from the list's length on entry (lists only shrink); the kernels read the length
+ * each round has from the device, and the rounds queued behind the select that emptied the list leave
+ * every buffer as it is.  records[k] are the loop's, in order; out: rounds_queued = rounds,
+ * rounds_run / selects_run / passes_run what the loop would have rendered and selected, device_ms
+ * the whole run between two HIP events.  mcpt_last_adaptive_ms / mcpt_last_stats_ms /
+ * mcpt_last_denoise_ms report the last QUEUED round and select of the run.
+ * Preconditions, checked before anything is enqueued (a refusal changes nothing): those of
+ * mcpt_render_adaptive, then those of the matching select except its two batches (the schedule's),
+ * in those calls' order; then MCPT_ERR_INVALID_ARG for n_passes <= 0, rounds outside
+ * 1..MCPT_ADAPTIVE_RUN_MAX_ROUNDS, check_every <= 0, records_capacity below the selects the
+ * schedule can run, or records NULL with records_capacity > 0.  A list that is empty on entry
+ * enqueues nothing: MCPT_OK with rounds_run = 0.  Device memory: 1 MiB of partial records per rule
+ * (MCPT_ADAPTIVE_RUN_MAX_ROUNDS x 4 KiB) with the statistics buffers' lifetime. */
+#define MCPT_ADAPTIVE_RUN_MAX_ROUNDS 256
+typedef struct mcpt_adaptive_run_t {
+  int rounds_queued;      /* = rounds */
+  int rounds_run;         /* rounds the equivalent host loop would have rendered */
+  int selects_run;        /* records[] entries filled */
+  long long passes_run;   /* rounds_run * n_passes */
+  float device_ms;        /* HIP events around the whole run */
+} mcpt_adaptive_run_t;
+extern int mcpt_adaptive_run(mcpt_ctx* ctx, const float* invPV, const float* invV, int first_pass, int n_passes, int rounds,
+                             int check_every, float threshold, float mu_floor, float date, int bounces,
+                             float refract_ind, int variant, mcpt_adaptive_t* records, int records_capacity,
+                             mcpt_adaptive_run_t* out);
+extern int mcpt_adaptive_run_filtered(mcpt_ctx* ctx, const float* invPV, const float* invV, int first_pass, int n_passes,
+                               int rounds, int check_every, float threshold, float raw_cap, float mu_floor,
+                               int iterations, float k_color, float sigma_plane, float date, int bounces,
+                               float refract_ind, int variant, mcpt_adaptive_filtered_t* records, int records_capacity,
+                               mcpt_adaptive_run_t* out);
+
 /* DrawSampling's point cloud (DrawSampling/draw_sampling.cpp:144-150, tp/sampling_base.vert
  * seeding, tp/hsphere.vert random_ray): point k = random_ray(normalize(normal), roughness)
  * with seed floatBitsToUint(fseed) + k * nb_used * (11, 43, 67).  out: n × 3 f32 (host). */

@@ -554,6 +554,36 @@ class Renderer {
   void last_adaptive_ms(float& select_ms, float& render_ms) const {
     check(mcpt_last_adaptive_ms(c_, &select_ms, &render_ms), "mcpt_last_adaptive_ms");
   }
+  // Queued adaptive runs (mcpt_adaptive_run*): `rounds` rounds of {render_adaptive of
+  // n_passes passes, on the schedule's rounds a select} on the device with one host wait, the bits of
+  // that loop.  records: the selects' records in order (selects_run of them).
+  mcpt_adaptive_run_t adaptive_run(const Camera& cam, int first_pass, int n_passes, int rounds, int check_every,
+                                   float threshold, float date, int bounces, float refract_ind,
+                                   std::vector<mcpt_adaptive_t>& records, int variant = MCPT_MONTECARLO,
+                                   float mu_floor = kErrorMuFloor) {
+    mcpt_adaptive_run_t run;
+    records.assign((size_t)(rounds > 0 ? rounds : 1), mcpt_adaptive_t{});
+    check(mcpt_adaptive_run(c_, cam.invPV.m, cam.invV.m, first_pass, n_passes, rounds, check_every, threshold, mu_floor,
+                            date, bounces, refract_ind, variant, records.data(), (int)records.size(), &run),
+          "mcpt_adaptive_run");
+    records.resize((size_t)run.selects_run);
+    return run;
+  }
+  mcpt_adaptive_run_t adaptive_run_filtered(const Camera& cam, int first_pass, int n_passes, int rounds,
+                                            int check_every, float threshold, float raw_cap, int iterations, float date,
+                                            int bounces, float refract_ind,
+                                            std::vector<mcpt_adaptive_filtered_t>& records,
+                                            int variant = MCPT_MONTECARLO, float mu_floor = kErrorMuFloor,
+                                            float k_color = kDenoiseKVariance, float sigma_plane = kDenoiseSigmaPlane) {
+    mcpt_adaptive_run_t run;
+    records.assign((size_t)(rounds > 0 ? rounds : 1), mcpt_adaptive_filtered_t{});
+    check(mcpt_adaptive_run_filtered(c_, cam.invPV.m, cam.invV.m, first_pass, n_passes, rounds, check_every, threshold,
+                                     raw_cap, mu_floor, iterations, k_color, sigma_plane, date, bounces, refract_ind,
+                                     variant, records.data(), (int)records.size(), &run),
+          "mcpt_adaptive_run_filtered");
+    records.resize((size_t)run.selects_run);
+    return run;
+  }
   // Begin a statistics window and the adaptive mode, render calls of `batch` passes for the active
   // blocks only, select after every check_every calls (from the second on, and at the cap) until no
   // block is active or max_passes are rendered.  The mode stays on (read_resolved, read_sample_counts).

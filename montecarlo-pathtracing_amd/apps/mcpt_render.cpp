@@ -57,6 +57,7 @@ struct Args {
   int target_denoised = -1;   // --target-denoised [N]: --adaptive selects on the variance filter's error (-1: off; N defaults to 5)
   float raw_cap = 64.0f;      // --raw-cap R: with --target-denoised a block also stays while its largest raw r > R (64: off)
   bool adaptive = false;      // --adaptive: --target-error is the per-pixel threshold; retired 8x8 blocks stop receiving passes
+  int queue_rounds = 0;       // --queue-rounds K: with --adaptive, one device: the chunks go out as queued runs of up to K (0: off)
 };
 
 bool parse_list(const char* v, std::vector<int>& out) {
@@ -103,7 +104,10 @@ void usage() {
                "                                   device: E bounds the error of the variance-filtered image (N\n"
                "                                   iterations, default 5) in place of the raw one; a block also stays\n"
                "                                   while its largest raw r > R (default 64: off); writes the\n"
-               "                                   filtered image as --denoise-variance N would)\n");
+               "                                   filtered image as --denoise-variance N would)\n"
+               "                   [--queue-rounds K]   (with --adaptive, one device: up to K chunks and their selects\n"
+               "                                         are queued on the device per host wait, 1..256; the same\n"
+               "                                         image; a checkpoint is written after each run)\n");
 }
 
 // a refused combination: why, then the usage (parse's false)
@@ -170,6 +174,10 @@ bool parse(int argc, char** argv, Args& a) {
       a.target_error = std::atof(v);
       if (!(a.target_error > 0.0)) return false;
     }
+    else if (k == "--queue-rounds") {
+      a.queue_rounds = std::atoi(v);
+      if (a.queue_rounds < 1 || a.queue_rounds > MCPT_ADAPTIVE_RUN_MAX_ROUNDS) return false;
+    }
     else if (k == "--raw-cap") {
       a.raw_cap = (float)std::atof(v);
       if (!(a.raw_cap > 0.0f)) return false;
@@ -197,6 +205,10 @@ bool parse(int argc, char** argv, Args& a) {
   if (!a.devices.empty() && a.adaptive && a.noise_filter()) return false;
   if ((a.denoise >= 0) + (a.denoise_guided >= 0) + (a.denoise_variance >= 0) > 1) return false;   // one filter
   if (a.adaptive && !(a.target_error > 0.0)) return false;   // adaptive sampling needs its threshold
+  if (a.queue_rounds > 0) {
+    if (!a.adaptive) return refuse("--queue-rounds queues the chunks of --adaptive --target-error E: give both");
+    if (!a.devices.empty()) return refuse("--queue-rounds runs on one device: not with --devices");
+  }
   if (a.target_denoised >= 0) {
     if (!a.adaptive || !(a.target_error > 0.0))
       return refuse("--target-denoised is a rule of --adaptive --target-error E: give both");
@@ -350,7 +362,38 @@ int main(int argc, char** argv) {
         converged = calls >= 2 && r.adaptive_info().n_active == 0;
         rendered = next - a.first_pass;
       }
-      for (int done = next - a.first_pass; a.adaptive && done < a.spp && !converged; done += a.chunk) {
+      for (int done = next - a.first_pass; a.adaptive && done < a.spp && !converged;) {
+        // --queue-rounds: the whole chunks ahead, up to K of them, as one queued run (the same
+        // renders and selects, one host wait); a short last chunk goes through the calls below
+        const int whole = (a.spp - done) / a.chunk;
+        if (a.queue_rounds > 0 && whole > 0) {
+          const int k = std::min(a.queue_rounds, whole);
+          std::vector<mcpt_adaptive_t> recs;
+          std::vector<mcpt_adaptive_filtered_t> frecs;
+          const mcpt_adaptive_run_t run =
+              a.target_denoised >= 0
+                  ? r.adaptive_run_filtered(cam, a.first_pass + done, a.chunk, k, 1, (float)a.target_error, a.raw_cap,
+                                            a.target_denoised, a.date, a.bounces, a.ior, frecs, a.variant)
+                  : r.adaptive_run(cam, a.first_pass + done, a.chunk, k, 1, (float)a.target_error, a.date, a.bounces,
+                                   a.ior, recs, a.variant);
+          kernel_ms += run.device_ms;
+          calls += run.rounds_run;
+          done += run.rounds_run * a.chunk;
+          rendered = done;
+          if (run.selects_run > 0) {
+            if (a.target_denoised >= 0) {
+              frec = frecs.back();
+              arec = frec.raw;
+            } else {
+              arec = recs.back();
+            }
+            have_arec = true;
+            converged = arec.n_active_blocks == 0;
+          }
+          if (!a.checkpoint.empty()) r.save_adaptive_checkpoint(a.checkpoint, a.first_pass + done, tag);
+          if (run.rounds_run < k) break;   // (the list was empty on entry: nothing left to render)
+          continue;
+        }
         // adaptive sampling: the active blocks only, a select after every chunk from the second on
         const int n = std::min(a.chunk, a.spp - done);
         r.render_adaptive(cam, a.first_pass + done, n, a.date, a.bounces, a.ior, a.variant);
@@ -371,6 +414,7 @@ int main(int argc, char** argv) {
         }
         // (after the chunk's select: the resumed run continues with the next chunk's render)
         if (!a.checkpoint.empty()) r.save_adaptive_checkpoint(a.checkpoint, a.first_pass + done + n, tag);
+        done += a.chunk;
       }
       for (int done = next - a.first_pass; !a.adaptive && done < a.spp && !converged; done += a.chunk) {
         const int n = std::min(a.chunk, a.spp - done);

@@ -236,6 +236,18 @@ __global__ __launch_bounds__(256) void add_passes_kernel(int* __restrict__ passe
   if (b >= 0 && b < n_blocks) passes[b] += add;
 }
 
+// add_passes_kernel's twin of a queued adaptive run: the grid holds n_held list
+// entries, the list's length is read from count[0] (compact_kernel's, behind the list)
+__global__ __launch_bounds__(256) void add_passes_counted_kernel(int* __restrict__ passes,
+                                                                 const int* __restrict__ list,
+                                                                 const int* __restrict__ count, int n_held,
+                                                                 int n_blocks, int add) {
+  const int k = blockIdx.x * 256 + threadIdx.x;
+  if (k >= min(max(count[0], 0), n_held)) return;
+  const int b = list[k];
+  if (b >= 0 && b < n_blocks) passes[b] += add;
+}
+
 __global__ __launch_bounds__(256) void counts_kernel(CountSource src, int* __restrict__ counts, long long n_px) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i >= n_px) return;
@@ -307,13 +319,12 @@ __global__ __launch_bounds__(256) void load_rows_error_map_kernel(const uint2* _
     plane[(long long)y * W + x] = src[(long long)src_row[y] * W + x];
 }
 
-__global__ __launch_bounds__(256) void combine_list_kernel(float* __restrict__ accum, const float* __restrict__ partial,
-                                                           long long n_px, int n_seg, int W, int n_local_rows,
-                                                           int blocks_x, int n_blocks, const int* __restrict__ list,
-                                                           int n_list, unsigned long long* ev) {
+// one wave's block of the list: accum += the block's segment sums, in chunk order
+__device__ __forceinline__ void combine_list_block(float* __restrict__ accum, const float* __restrict__ partial,
+                                                   long long n_px, int n_seg, int W, int n_local_rows, int blocks_x,
+                                                   int n_blocks, const int* __restrict__ list, long long li,
+                                                   unsigned long long* ev) {
   const int lane = threadIdx.x & 63;
-  const long long li = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (li >= n_list) return;
   const int blk = list[li];
   if (!idx_ok(ev, CK_LIST, blk, n_blocks)) return;
   const int x = (blk % blocks_x) * 8 + (lane & 7), lr = (blk / blocks_x) * 8 + (lane >> 3);
@@ -325,6 +336,28 @@ __global__ __launch_bounds__(256) void combine_list_kernel(float* __restrict__ a
     a0 = a0 + q[0]; a1 = a1 + q[1]; a2 = a2 + q[2];
   }
   accum[i * 3] = a0; accum[i * 3 + 1] = a1; accum[i * 3 + 2] = a2;
+}
+
+__global__ __launch_bounds__(256) void combine_list_kernel(float* __restrict__ accum, const float* __restrict__ partial,
+                                                           long long n_px, int n_seg, int W, int n_local_rows,
+                                                           int blocks_x, int n_blocks, const int* __restrict__ list,
+                                                           int n_list, unsigned long long* ev) {
+  const long long li = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (li >= n_list) return;
+  combine_list_block(accum, partial, n_px, n_seg, W, n_local_rows, blocks_x, n_blocks, list, li, ev);
+}
+
+// combine_list_kernel's twin of a queued adaptive run: the grid holds n_held list
+// entries, the list's length is read from list[n_blocks] (compact_kernel's count)
+__global__ __launch_bounds__(256) void combine_list_counted_kernel(float* __restrict__ accum,
+                                                                   const float* __restrict__ partial, long long n_px,
+                                                                   int n_seg, int W, int n_local_rows, int blocks_x,
+                                                                   int n_blocks, const int* __restrict__ list,
+                                                                   int n_held, unsigned long long* ev) {
+  const long long li = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (li >= min(max(list[n_blocks], 0), n_held)) return;
+  if (!idx_ok(ev, CK_LIST, li, n_blocks)) return;
+  combine_list_block(accum, partial, n_px, n_seg, W, n_local_rows, blocks_x, n_blocks, list, li, ev);
 }
 
 }  // namespace mcpt
@@ -379,6 +412,14 @@ hipError_t mcpt_launch_adaptive_add_passes(const mcpt::AdaptiveTarget& t, const 
   return hipGetLastError();
 }
 
+hipError_t mcpt_launch_adaptive_add_passes_counted(const mcpt::AdaptiveTarget& t, const int* list, const int* count,
+                                                   int n_held, int n, hipStream_t stream) {
+  if (n_held <= 0) return hipSuccess;
+  hipLaunchKernelGGL(mcpt::add_passes_counted_kernel, dim3(grid256(n_held)), dim3(256), 0, stream, t.passes, list, count,
+                     n_held, t.n_blocks, n);
+  return hipGetLastError();
+}
+
 hipError_t mcpt_launch_counts(const mcpt::CountSource& src, int* counts, long long n_px, hipStream_t stream) {
   if (n_px <= 0) return hipSuccess;
   hipLaunchKernelGGL(mcpt::counts_kernel, dim3(grid256(n_px)), dim3(256), 0, stream, src, counts, n_px);
@@ -427,7 +468,13 @@ hipError_t mcpt_launch_load_rows_error_map(const void* src, const int* src_row, 
 }
 
 hipError_t mcpt_launch_combine_list(const mcpt::RenderParams& p, hipStream_t stream) {
-  if (p.n_segments <= 1 || p.n_list <= 0) return hipSuccess;   // (one segment: the render added it itself)
+  if (p.n_segments <= 1 || p.n_list == 0) return hipSuccess;   // (one segment: the render added it itself)
+  if (p.n_list < 0) {   // a queued adaptive run: a grid of -n_list entries, the length read on the device
+    hipLaunchKernelGGL(mcpt::combine_list_counted_kernel, dim3((unsigned)((-(long long)p.n_list + 3) / 4)), dim3(256), 0,
+                       stream, p.accum, p.partial, p.n_local_px, p.n_segments, p.W, p.n_local_rows, p.blocks_x,
+                       p.n_blocks, p.list, -p.n_list, p.events);
+    return hipGetLastError();
+  }
   hipLaunchKernelGGL(mcpt::combine_list_kernel, dim3((unsigned)(((long long)p.n_list + 3) / 4)), dim3(256), 0, stream,
                      p.accum, p.partial, p.n_local_px, p.n_segments, p.W, p.n_local_rows, p.blocks_x, p.n_blocks, p.list,
                      p.n_list, p.events);

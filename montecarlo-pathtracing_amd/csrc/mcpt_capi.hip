@@ -241,6 +241,7 @@ int mcpt_destroy(mcpt_ctx* c) {
   for (hipEvent_t e : c->stats_ev) if (e) (void)hipEventDestroy(e);
   free_adaptive(c);
   for (hipEvent_t e : c->ad_ev) if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : c->run_ev) if (e) (void)hipEventDestroy(e);
   free_count_plane(c);
   (void)hipFree(c->d_accum);
   (void)hipFree(c->d_rows);

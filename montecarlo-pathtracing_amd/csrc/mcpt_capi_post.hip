@@ -46,6 +46,15 @@ static void fill_frame_record(const mcpt_ctx* c, const unsigned long long* h, Re
   out->passes = c->stats_passes;
   out->batches = c->stats_batches;
 }
+// the filtered select's own fields from its step C's record
+static void fill_filtered_record(const mcpt_ctx* c, const unsigned long long* hf, mcpt_adaptive_filtered_t* out) {
+  const long long n = (long long)c->n_local_rows * c->W;
+  out->n_above_f = (long long)hf[0];
+  out->sum_qf = hf[1];
+  const unsigned mb = (unsigned)(hf[2] & 0xffffffffull);
+  std::memcpy(&out->max_rf, &mb, sizeof(float));
+  out->mean_rf = n > 0 ? (double)hf[1] / 65536.0 / (double)n : 0.0;
+}
 // elapsed ms of an optional event pair into *out (null: not asked for): 0 unless the pair was recorded
 static int pair_ms(bool timed, hipEvent_t ev_a, hipEvent_t ev_b, float* out) {
   if (!out) return MCPT_OK;
@@ -110,9 +119,10 @@ int mcpt_read_guides(mcpt_ctx* c, float* guide8, float* albedo4) {
 // resolved: the mcpt_denoise_resolved* forms, whose input is accum / (float)count with every
 // pixel's own count in place of accum / pass_count; variance: the
 // mcpt_denoise*_variance forms (guided's preconditions and map; sigma_color is k_color, the first
-// input carries the prefiltered se^2 in .w and every iteration filters it along)
+// input carries the prefiltered se^2 in .w and every iteration filters it along);
+// timed false: no events (a queued adaptive run's selects but its last)
 static int denoise_run(mcpt_ctx* c, int iterations, float sigma_color, float sigma_plane, bool guided,
-                       bool resolved = false, bool variance = false) {
+                       bool resolved = false, bool variance = false, bool timed = true) {
   if (!c || iterations < 0 || iterations > 8) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_denoise: iterations not in 0..8");
   if (!(sigma_color > 0.0f) || !(sigma_plane > 0.0f) || !std::isfinite(sigma_color) || !std::isfinite(sigma_plane))
     return set_err(MCPT_ERR_INVALID_ARG, "mcpt_denoise: sigmas must be positive and finite");
@@ -141,7 +151,7 @@ static int denoise_run(mcpt_ctx* c, int iterations, float sigma_color, float sig
   int lds_mask = 0;
   const long long n = (long long)c->H * c->W;
   // (the context's stream is ordered after all queued renders: their combines run on it)
-  HIP_OR_RETURN(hipEventRecord(c->dn_ev[9], c->stream));
+  if (timed) HIP_OR_RETURN(hipEventRecord(c->dn_ev[9], c->stream));
   const mcpt::CountSource counts = count_source(c);
   if (variance)
     HIP_OR_RETURN(mcpt_launch_variance_init(resolved ? &counts : nullptr, c->d_accum, c->d_dn[0], c->d_guide, emap, c->W,
@@ -150,7 +160,7 @@ static int denoise_run(mcpt_ctx* c, int iterations, float sigma_color, float sig
     HIP_OR_RETURN(mcpt_launch_resolve4(count_source(c), c->d_accum, c->d_dn[0], n, c->stream));
   else
     HIP_OR_RETURN(mcpt_launch_average4(c->d_accum, c->d_dn[0], n, c->pass_count, c->stream));
-  HIP_OR_RETURN(hipEventRecord(c->dn_ev[0], c->stream));
+  if (timed) HIP_OR_RETURN(hipEventRecord(c->dn_ev[0], c->stream));
   for (int s = 0; s < iterations; ++s) {
     const int step = 1 << s;
     // the iteration's constants in binary32: 2^-s and step are exact factors
@@ -164,7 +174,7 @@ static int denoise_run(mcpt_ctx* c, int iterations, float sigma_color, float sig
     else
       HIP_OR_RETURN(mcpt_launch_atrous(c->d_dn[s & 1], c->d_dn[(s + 1) & 1], c->d_guide, c->W, c->H, step, kc, kp,
                                        guided ? emap : nullptr, naive, c->stream));
-    HIP_OR_RETURN(hipEventRecord(c->dn_ev[s + 1], c->stream));
+    if (timed) HIP_OR_RETURN(hipEventRecord(c->dn_ev[s + 1], c->stream));
     if (!naive && step <= 2) lds_mask |= 1 << s;
   }
   c->dn_lds_mask = lds_mask;
@@ -446,12 +456,7 @@ int mcpt_adaptive_select_filtered(mcpt_ctx* c, float threshold, float raw_cap, f
   out->raw.n_active_blocks = n_list;
   out->raw.n_blocks = c->ad_n_blocks;
   out->raw.samples = (long long)h[3];
-  const long long n = (long long)c->n_local_rows * c->W;
-  out->n_above_f = (long long)hf[0];
-  out->sum_qf = hf[1];
-  const unsigned mb = (unsigned)(hf[2] & 0xffffffffull);
-  std::memcpy(&out->max_rf, &mb, sizeof(float));
-  out->mean_rf = n > 0 ? (double)hf[1] / 65536.0 / (double)n : 0.0;
+  fill_filtered_record(c, hf, out);
   return MCPT_OK;
 }
 
@@ -469,36 +474,58 @@ int mcpt_read_active_blocks(mcpt_ctx* c, int* ids, int capacity, int* n) {
 // The listed blocks' passes first_pass .. first_pass + n_passes - 1 on the context's stream (ordered
 // after the render lanes): the scene's per-lane kernel's LIST twin, one segment per item, dispatch
 // order.  No part in AUTO's trials, the item-cost sort, the render lanes or the timing ring.
-int mcpt_render_adaptive(mcpt_ctx* c, const float* invPV, const float* invV, int first_pass, int n_passes, float date,
-                         int bounces, float refract_ind, int variant) {
+// (adaptive_round: the round behind mcpt_render_adaptive and, counted, one round of a queued run,
+// the grids hold the list's length on the host, c->ad_n_list, the kernels read the
+// length it has by then on the device, and the statistics' batch skips once it is 0; timed false:
+// the round records no events)
+static int check_render_adaptive(const mcpt_ctx* c, const float* invPV, const float* invV, int n_passes, int variant,
+                                 const char* who) {
   const bool args_ok = invPV && invV && n_passes >= 0 && variant >= 0 && variant <= 2;
   if (c && args_ok && !c->ad_on)
     return set_err(MCPT_ERR_NO_ADAPTIVE, "mcpt_render_adaptive: adaptive mode is off (mcpt_adaptive_begin)");
-  OK_OR_RETURN(check_renderable(c, args_ok, "mcpt_render_adaptive"));
-  invalidate_planes(c);   // (a gathered frame's counts do not describe what is rendered into it)
-  if (c->ad_n_list == 0 || n_passes == 0) return MCPT_OK;   // every block retired: nothing to launch
-  HIP_OR_RETURN(hipSetDevice(c->device));
-  mcpt::RenderParams p;
+  return check_renderable(c, args_ok, who);
+}
+// the round's launch parameters except its pass range; returns the most segments a sub-launch holds
+static long long adaptive_round_params(const mcpt_ctx* c, const float* invPV, const float* invV, bool counted,
+                                       mcpt::RenderParams& p) {
   scene_params(c, invPV, invV, p);
-  pass_params(first_pass, n_passes, date, bounces, refract_ind, variant, p);
   p.walk_exit = plan::resolve_walk_exit(c->walk_exit, c->n_meshes, c->depth);
   p.leaf_batch = plan::resolve_leaf_batch(c->leaf_batch, c->depth);
   p.walk_min_done = 1;
   p.seg_per_item = 1;
   p.list = c->d_ad_list;
-  p.n_list = c->ad_n_list;
+  p.n_list = counted ? -c->ad_n_list : c->ad_n_list;
   p.blocks_x = c->ad_blocks_x;
   p.n_blocks = c->ad_n_blocks;
-  const int per_group = p.tile_w / 8;
-  p.n_tiles = (p.n_list + per_group - 1) / per_group;   // workgroup groups of the list
+  p.n_tiles = plan::run_list_groups(c->ad_n_list, p.tile_w);   // workgroup groups of the list
   plan::LimitsIn lin;   // (no spare workgroups, no pass stealing)
   lin.n_local_px = p.n_local_px; lin.n_tiles = p.n_tiles; lin.tile_w = p.tile_w; lin.n_cu = c->n_cu;
   lin.partial_budget = c->partial_budget; lin.mesh = c->n_meshes > 0; lin.steal = false; lin.spare = false;
-  const long long max_seg = plan::limits(lin).max_seg;
+  return plan::limits(lin).max_seg;
+}
+static hipError_t stats_batch_counted(mcpt_ctx* c, int n, bool timed) {
+  hipError_t e = hipSuccess;
+  if (timed) e = hipEventRecord(c->stats_ev[0], c->stream);
+  if (e == hipSuccess)
+    e = mcpt_launch_stats_update_counted(c->d_accum, c->d_stats, (long long)c->n_local_rows * c->W, n,
+                                         c->d_ad_list + c->ad_n_blocks, c->stream);
+  if (e == hipSuccess && timed) e = hipEventRecord(c->stats_ev[1], c->stream);
+  if (e != hipSuccess) return e;
+  c->stats_passes += n;
+  c->stats_batches += 1;
+  if (timed) c->stats_update_timed = true;
+  return hipSuccess;
+}
+static int adaptive_round(mcpt_ctx* c, const float* invPV, const float* invV, int first_pass, int n_passes, float date,
+                          int bounces, float refract_ind, int variant, bool counted, bool timed) {
+  HIP_OR_RETURN(hipSetDevice(c->device));
+  mcpt::RenderParams p;
+  const long long max_seg = adaptive_round_params(c, invPV, invV, counted, p);
+  pass_params(first_pass, n_passes, date, bounces, refract_ind, variant, p);
   const size_t seg_bytes = (size_t)p.n_local_px * 3 * sizeof(float);
-  HIP_OR_RETURN(ensure_timing_events(c->ad_ev + 2, 2));
+  if (timed) HIP_OR_RETURN(ensure_timing_events(c->ad_ev + 2, 2));
   mcpt_ctx::Lane& L = c->lanes[0];   // its segment-sum buffer (free: `stream` is ordered after the lanes' work)
-  HIP_OR_RETURN(hipEventRecord(c->ad_ev[2], c->stream));
+  if (timed) HIP_OR_RETURN(hipEventRecord(c->ad_ev[2], c->stream));
   // sub-launches at chunk boundaries, as launch() cuts them (segment-sum budget, grid size)
   plan::SubLaunch sub;
   int k = 0;
@@ -516,12 +543,191 @@ int mcpt_render_adaptive(mcpt_ctx* c, const float* invPV, const float* invV, int
 #endif
   }
   (void)k;
-  HIP_OR_RETURN(hipEventRecord(c->ad_ev[3], c->stream));
-  c->ad_render_timed = true;
-  HIP_OR_RETURN(mcpt_launch_adaptive_add_passes(adaptive_target(c), c->d_ad_list, c->ad_n_list, n_passes, c->stream));
+  if (timed) {
+    HIP_OR_RETURN(hipEventRecord(c->ad_ev[3], c->stream));
+    c->ad_render_timed = true;
+  }
+  if (counted)
+    HIP_OR_RETURN(mcpt_launch_adaptive_add_passes_counted(adaptive_target(c), c->d_ad_list, c->d_ad_list + c->ad_n_blocks,
+                                                          c->ad_n_list, n_passes, c->stream));
+  else
+    HIP_OR_RETURN(mcpt_launch_adaptive_add_passes(adaptive_target(c), c->d_ad_list, c->ad_n_list, n_passes, c->stream));
   c->pass_count += n_passes;   // the active blocks' count: the largest
-  if (c->stats_on) HIP_OR_RETURN(stats_batch(c, n_passes));
+  if (c->stats_on) HIP_OR_RETURN(counted ? stats_batch_counted(c, n_passes, timed) : stats_batch(c, n_passes));
   return MCPT_OK;
+}
+
+int mcpt_render_adaptive(mcpt_ctx* c, const float* invPV, const float* invV, int first_pass, int n_passes, float date,
+                         int bounces, float refract_ind, int variant) {
+  OK_OR_RETURN(check_render_adaptive(c, invPV, invV, n_passes, variant, "mcpt_render_adaptive"));
+  invalidate_planes(c);   // (a gathered frame's counts do not describe what is rendered into it)
+  if (c->ad_n_list == 0 || n_passes == 0) return MCPT_OK;   // every block retired: nothing to launch
+  return adaptive_round(c, invPV, invV, first_pass, n_passes, date, bounces, refract_ind, variant, false, true);
+}
+
+// ---- queued adaptive runs: `rounds` rounds of {the active blocks' passes, the
+// statistics' batch, on the schedule's rounds a select and the scan} on the stream, every list length
+// read on the device, one wait at the end for all the records.  f: the filtered rule's arguments
+// (null: mcpt_adaptive_select's rule); records: mcpt_adaptive_t or, with f, mcpt_adaptive_filtered_t.
+struct RunFilter { float raw_cap; int iterations; float k_color, sigma_plane; };
+
+static int adaptive_run(mcpt_ctx* c, const float* invPV, const float* invV, int first_pass, int n_passes, int rounds,
+                        int check_every, float threshold, float mu_floor, float date, int bounces, float refract_ind,
+                        int variant, const RunFilter* f, void* records, int records_capacity, mcpt_adaptive_run_t* out) {
+  const char* who = f ? "mcpt_adaptive_run_filtered" : "mcpt_adaptive_run";
+  // mcpt_render_adaptive's checks, then the select's, then the run's own: before anything is enqueued
+  OK_OR_RETURN(check_render_adaptive(c, invPV, invV, n_passes, variant, who));
+  if (!out) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  for (float v : {threshold, mu_floor, f ? f->raw_cap : 1.0f, f ? f->k_color : 1.0f, f ? f->sigma_plane : 1.0f})
+    if (!(v > 0.0f) || !std::isfinite(v))
+      return set_err(MCPT_ERR_INVALID_ARG, "mcpt_adaptive_run: threshold, mu_floor and the filter's widths must be positive and finite");
+  if (f) {
+    if (f->iterations < 0 || f->iterations > 8)
+      return set_err(MCPT_ERR_INVALID_ARG, "mcpt_adaptive_run_filtered: iterations not in 0..8");
+    if (!plan::is_full_frame(c->rows, c->H))
+      return set_err(MCPT_ERR_INVALID_ARG, "mcpt_adaptive_run_filtered: needs a full-frame target (a shard is filtered after its gather)");
+    if (c->plane_valid || c->emap_plane_valid)
+      return set_err(MCPT_ERR_INVALID_ARG, "mcpt_adaptive_run_filtered: the context holds a gathered frame's counts or error map");
+  }
+  if (!c->stats_on) return set_err(MCPT_ERR_NO_STATS, "mcpt_adaptive_run: statistics are off (mcpt_stats_begin)");
+  if (f && !c->guides_valid)
+    return set_err(MCPT_ERR_NO_GUIDES, "mcpt_adaptive_run_filtered: no guides rendered for this target and scene");
+  if (n_passes <= 0 || rounds < 1 || rounds > plan::kAdaptiveRunMaxRounds || check_every <= 0)
+    return set_err(MCPT_ERR_INVALID_ARG, "mcpt_adaptive_run: n_passes and check_every must be positive, rounds in 1..256");
+  const long long last_pass = (long long)first_pass + (long long)rounds * n_passes;
+  if (last_pass > 0x7fffffffLL || (long long)c->pass_count + (long long)rounds * n_passes > 0x7fffffffLL)
+    return set_err(MCPT_ERR_INVALID_ARG, "mcpt_adaptive_run: the run's passes do not fit the pass counters");
+  const int n_sel = plan::run_select_count(rounds, check_every, c->stats_batches);
+  if (records_capacity < n_sel || (records_capacity > 0 && !records))
+    return set_err(MCPT_ERR_INVALID_ARG, "mcpt_adaptive_run: records holds fewer selects than the schedule can run");
+  std::memset(out, 0, sizeof(*out));
+  out->rounds_queued = rounds;
+  if (c->ad_n_list == 0) return MCPT_OK;   // every block retired: the host loop stops before its first round
+
+  HIP_OR_RETURN(hipSetDevice(c->device));
+  HIP_OR_RETURN(ensure_timing_events(c->ad_ev, 6));
+  HIP_OR_RETURN(ensure_timing_events(c->stats_ev, 2));
+  HIP_OR_RETURN(ensure_timing_events(c->run_ev, 2));
+  const size_t ring_bytes = sizeof(unsigned long long) * mcpt::kStatsRecWords * (size_t)plan::kAdaptiveRunMaxRounds;
+  if (!c->d_run_rec) HIP_OR_RETURN(hipMalloc(&c->d_run_rec, ring_bytes));
+  if (!c->d_run_len) HIP_OR_RETURN(hipMalloc(&c->d_run_len, sizeof(int) * (size_t)plan::kAdaptiveRunMaxRounds));
+  if (f) {
+    if (!c->d_run_rec_f) HIP_OR_RETURN(hipMalloc(&c->d_run_rec_f, ring_bytes));
+    HIP_OR_RETURN(ensure_timing_events(c->dn_ev, 10));
+    HIP_OR_RETURN(ensure_denoise_buffers(c));
+  }
+  {   // the segment-sum buffer of the run's largest sub-launch now: growing it waits for the stream
+    mcpt::RenderParams p;
+    const long long max_seg = adaptive_round_params(c, invPV, invV, true, p);
+    int most = 1;
+    for (int i = 0; i < rounds; ++i) {
+      plan::SubLaunch sub;
+      for (long long lo = (long long)first_pass + (long long)i * n_passes, end = lo + n_passes; lo < end; lo = sub.end()) {
+        sub = plan::next_sub_launch(lo, end, max_seg, false);
+        most = std::max(most, sub.n_segments);
+      }
+    }
+    mcpt_ctx::Lane& L = c->lanes[0];
+    if (most > 1)
+      OK_OR_RETURN(ensure_lane_bytes(c, L.d_partial, L.partial_bytes, (size_t)most * (size_t)p.n_local_px * 3 * sizeof(float)));
+  }
+
+  const int list_in = c->ad_n_list, pass_in = c->pass_count, batches_in = c->stats_batches;
+  const long long window_in = c->stats_passes;
+  const bool emap_in = c->emap_valid;
+  const mcpt::AdaptiveTarget t = adaptive_target(c);
+  int* d_count = c->d_ad_list + c->ad_n_blocks;
+  int sel_round[plan::kAdaptiveRunMaxRounds];
+  invalidate_planes(c);
+  HIP_OR_RETURN(hipEventRecord(c->run_ev[0], c->stream));
+  int k = 0;
+  for (int i = 0; i < rounds; ++i) {
+    OK_OR_RETURN(adaptive_round(c, invPV, invV, first_pass + i * n_passes, n_passes, date, bounces, refract_ind, variant,
+                                true, i == rounds - 1));
+    if (!plan::run_round_selects(i, rounds, check_every, batches_in)) continue;
+    const bool timed = k == n_sel - 1;
+    unsigned long long* rec = c->d_run_rec + (size_t)k * mcpt::kStatsRecWords;
+    if (timed) HIP_OR_RETURN(hipEventRecord(c->ad_ev[0], c->stream));
+    HIP_OR_RETURN(mcpt_launch_adaptive_select(t, c->d_stats, c->d_emap, c->stats_passes, c->stats_batches, mu_floor,
+                                              threshold, c->ad_min_passes, f == nullptr, rec, c->stream));
+    c->emap_valid = true;
+    if (f) {
+      if (timed) HIP_OR_RETURN(hipEventRecord(c->ad_ev[1], c->stream));
+      OK_OR_RETURN(denoise_run(c, f->iterations, f->k_color, f->sigma_plane, true, true, true, timed));
+      if (timed) HIP_OR_RETURN(hipEventRecord(c->ad_ev[4], c->stream));
+      HIP_OR_RETURN(mcpt_launch_adaptive_select_filtered(t, c->d_dn[c->dn_result], c->d_emap, mu_floor, threshold,
+                                                         f->raw_cap, c->ad_min_passes,
+                                                         c->d_run_rec_f + (size_t)k * mcpt::kStatsRecWords, c->stream));
+    }
+    HIP_OR_RETURN(mcpt_launch_adaptive_compact(t, c->d_ad_list, d_count, c->stream));
+    if (timed) HIP_OR_RETURN(hipEventRecord(c->ad_ev[f ? 5 : 1], c->stream));
+    HIP_OR_RETURN(hipMemcpyAsync(c->d_run_len + k, d_count, sizeof(int), hipMemcpyDeviceToDevice, c->stream));
+    sel_round[k++] = i;
+  }
+  HIP_OR_RETURN(hipEventRecord(c->run_ev[1], c->stream));
+  if (n_sel > 0) {
+    c->ad_select_timed = true;
+    c->ad_select_split = f != nullptr;
+  }
+  std::vector<unsigned long long> part((size_t)k * mcpt::kStatsRecWords), part_f(f ? part.size() : 0);
+  std::vector<int> len((size_t)k);
+  if (k > 0) {
+    HIP_OR_RETURN(hipMemcpyAsync(part.data(), c->d_run_rec, part.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    if (f)
+      HIP_OR_RETURN(hipMemcpyAsync(part_f.data(), c->d_run_rec_f, part_f.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIP_OR_RETURN(hipMemcpyAsync(len.data(), c->d_run_len, len.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  }
+  HIP_OR_RETURN(hipStreamSynchronize(c->stream));   // the run's one wait
+  HIP_OR_RETURN(hipEventElapsedTime(&out->device_ms, c->run_ev[0], c->run_ev[1]));
+
+  // what the host loop would have done (mcpt_adaptive_run_plan.h): the rounds after the list emptied
+  // changed nothing on the device, and the host's counters follow the rounds that ran
+  const plan::RunOutcome o = plan::run_outcome(rounds, check_every, batches_in, list_in, len.data(), k);
+  c->pass_count = pass_in + o.rounds_run * n_passes;
+  c->stats_passes = window_in + (long long)o.rounds_run * n_passes;
+  c->stats_batches = batches_in + o.rounds_run;
+  c->emap_valid = emap_in || o.selects_run > 0;
+  out->rounds_run = o.rounds_run;
+  out->selects_run = o.selects_run;
+  out->passes_run = (long long)o.rounds_run * n_passes;
+  int status = MCPT_OK;
+  for (int s = 0; s < o.selects_run; ++s) {
+    unsigned long long h[5] = {0, 0, 0, 0, 0}, hf[5] = {0, 0, 0, 0, 0};
+    reduce_stats_records(part.data() + (size_t)s * mcpt::kStatsRecWords, 5, h);
+    if (f) reduce_stats_records(part_f.data() + (size_t)s * mcpt::kStatsRecWords, 5, hf);
+    const int n_list = len[(size_t)s];
+    if (n_list < 0 || n_list > c->ad_n_blocks || (unsigned long long)n_list != (f ? hf[4] : h[4])) {
+      status = set_err(MCPT_ERR_HIP, "mcpt_adaptive_run: the active list and the block flags disagree");
+      break;
+    }
+    c->ad_n_list = n_list;
+    mcpt_adaptive_t* raw = f ? &static_cast<mcpt_adaptive_filtered_t*>(records)[s].raw : &static_cast<mcpt_adaptive_t*>(records)[s];
+    fill_frame_record(c, h, raw);
+    raw->passes = window_in + (long long)(sel_round[s] + 1) * n_passes;
+    raw->batches = batches_in + sel_round[s] + 1;
+    raw->n_active_blocks = n_list;
+    raw->n_blocks = c->ad_n_blocks;
+    raw->samples = (long long)h[3];
+    if (f) fill_filtered_record(c, hf, &static_cast<mcpt_adaptive_filtered_t*>(records)[s]);
+  }
+  return status;
+}
+
+int mcpt_adaptive_run(mcpt_ctx* c, const float* invPV, const float* invV, int first_pass, int n_passes, int rounds,
+                      int check_every, float threshold, float mu_floor, float date, int bounces, float refract_ind,
+                      int variant, mcpt_adaptive_t* records, int records_capacity, mcpt_adaptive_run_t* out) {
+  return adaptive_run(c, invPV, invV, first_pass, n_passes, rounds, check_every, threshold, mu_floor, date, bounces,
+                      refract_ind, variant, nullptr, records, records_capacity, out);
+}
+
+int mcpt_adaptive_run_filtered(mcpt_ctx* c, const float* invPV, const float* invV, int first_pass, int n_passes,
+                               int rounds, int check_every, float threshold, float raw_cap, float mu_floor,
+                               int iterations, float k_color, float sigma_plane, float date, int bounces,
+                               float refract_ind, int variant, mcpt_adaptive_filtered_t* records, int records_capacity,
+                               mcpt_adaptive_run_t* out) {
+  const RunFilter f = {raw_cap, iterations, k_color, sigma_plane};
+  return adaptive_run(c, invPV, invV, first_pass, n_passes, rounds, check_every, threshold, mu_floor, date, bounces,
+                      refract_ind, variant, &f, records, records_capacity, out);
 }
 
 int mcpt_read_sample_counts(mcpt_ctx* c, int* counts) {

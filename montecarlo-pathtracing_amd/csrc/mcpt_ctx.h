@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/mcpt.h"
+#include "mcpt_adaptive_run_plan.h"
 #include "mcpt_gather_plan.h"
 #include "mcpt_internal.h"
 #include "mcpt_plan.h"
@@ -165,6 +166,14 @@ struct mcpt_ctx {
   // (DESIGN.md §3.9.2): [0, 1] around its step A, [4, 5] around its step C and the scan
   hipEvent_t ad_ev[6] = {};
   unsigned long long* d_conv_f = nullptr;   // the filtered select's partial records (as d_conv; its lifetime)
+  // a queued adaptive run (mcpt_adaptive_run*): every select of a run reduces into
+  // its own slice of a ring of kAdaptiveRunMaxRounds x kStatsRecWords words (the filtered selects'
+  // step C into a second ring) and its list length is copied into d_run_len beside them; allocated
+  // by the first run, the statistics buffers' lifetime.  run_ev: around the last run.
+  unsigned long long* d_run_rec = nullptr;
+  unsigned long long* d_run_rec_f = nullptr;
+  int* d_run_len = nullptr;
+  hipEvent_t run_ev[2] = {nullptr, nullptr};
   // per-pixel sample counts of a gathered frame (mcpt_gather_rows_counted): the
   // count plane, 4 B per local pixel, allocated by the first counted gather after a
   // mcpt_set_target*, freed by the next one and mcpt_destroy; valid until the accumulator changes
@@ -202,6 +211,8 @@ inline void free_denoise(mcpt_ctx* c) {
 inline void free_stats(mcpt_ctx* c) {
   (void)hipFree(c->d_stats); (void)hipFree(c->d_emap); (void)hipFree(c->d_conv); (void)hipFree(c->d_conv_f);
   c->d_stats = nullptr; c->d_emap = nullptr; c->d_conv = nullptr; c->d_conv_f = nullptr;
+  (void)hipFree(c->d_run_rec); (void)hipFree(c->d_run_rec_f); (void)hipFree(c->d_run_len);
+  c->d_run_rec = nullptr; c->d_run_rec_f = nullptr; c->d_run_len = nullptr;
   c->stats_on = false; c->stats_passes = 0; c->stats_batches = 0; c->emap_valid = false;
   c->stats_update_timed = false; c->stats_error_timed = false;
 }

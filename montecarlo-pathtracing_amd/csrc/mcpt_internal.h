@@ -131,7 +131,9 @@ struct RenderParams {
   double cull2_max;
   // adaptive launches (render_kernel<.., LIST>): wave w of workgroup group g renders
   // the 8x8 block list[g * (tile_w / 8) + w] (block id = by * blocks_x + bx over the local grid);
-  // waves past n_list are idle.  n_tiles = the workgroup groups; null in every other launch
+  // waves past n_list are idle.  n_tiles = the workgroup groups; null in every other launch.
+  // n_list < 0 (a queued adaptive run, §3.9.3): the launch holds -n_list entries and the kernels read
+  // the list's length from list[n_blocks]
   const int* list;
   int n_list, blocks_x, n_blocks;
 };
@@ -289,6 +291,15 @@ hipError_t mcpt_launch_adaptive_compact(const mcpt::AdaptiveTarget& t, int* list
 // passes[b] += n for the listed blocks (list null: for every block)
 hipError_t mcpt_launch_adaptive_add_passes(const mcpt::AdaptiveTarget& t, const int* list, int n_list, int n,
                                            hipStream_t stream);
+// The twins of a queued adaptive run (mcpt_adaptive_run*): their grids hold the
+// n_held list entries the list had when the run was queued, the length it has when they run is read
+// on the device from count[0] (compact_kernel's, at list[n_blocks]).  mcpt_launch_render_list and
+// mcpt_launch_combine_list take the same request as p.n_list = -n_held.  The statistics' batch
+// changes no pixel once the list is empty.
+hipError_t mcpt_launch_adaptive_add_passes_counted(const mcpt::AdaptiveTarget& t, const int* list, const int* count,
+                                                   int n_held, int n, hipStream_t stream);
+hipError_t mcpt_launch_stats_update_counted(const float* accum, float4* state, long long n_px, int n, const int* count,
+                                            hipStream_t stream);
 // Where a pixel's sample count comes from (chosen on the host, mcpt_ctx.h
 // count_source): the count plane, else base (p0) + the passes of the pixel's 8x8 block, else base (the
 // pass count).  Passed by value: kernel arguments, so count_at's choice is uniform over the launch.

@@ -152,7 +152,16 @@ __global__ __launch_bounds__(TW * kTileH, MESH && !WAVE ? kMinWavesMesh
     // live, and it still reaches the staging barrier
     static_assert(!COUNT && !WAVE, "LIST: the per-lane render kernels only");
     const long long li = (long long)tile * (TW / 8) + wave;
-    listed = li < p.n_list && idx_ok(p.events, CK_LIST, li, p.n_blocks);
+    // n_list < 0 (a queued adaptive run): the grid holds -n_list entries, the
+    // list's length when the run was queued; the length it has now is compact_kernel's count behind
+    // the list.  A workgroup whose first entry lies past it returns before the scene is staged (the
+    // same answer in all its waves: no wave is left at the barrier).
+    int n_list = p.n_list;
+    if (n_list < 0) {
+      n_list = min(max(p.list[p.n_blocks], 0), -n_list);
+      if ((long long)tile * (TW / 8) >= n_list) return;
+    }
+    listed = li < n_list && idx_ok(p.events, CK_LIST, li, p.n_blocks);
     const int blk = listed ? p.list[li] : 0;
     listed = listed && idx_ok(p.events, CK_LIST, blk, p.n_blocks);
     bx0 = (blk % p.blocks_x) * 8;
@@ -877,13 +886,15 @@ hipError_t mcpt_launch_render(const mcpt::RenderParams& p, bool count, hipStream
 }
 
 // adaptive launches: the LIST twin of the kernel mcpt_launch_render runs for per-lane walks
+// (p.n_list < 0: the grid of -p.n_list entries, the length read on the device)
 hipError_t mcpt_launch_render_list(const mcpt::RenderParams& p, hipStream_t stream) {
   const long long items = (long long)p.n_tiles * p.n_segments;
-  if (items <= 0 || p.n_list <= 0) return hipSuccess;
+  const long long held = p.n_list < 0 ? -(long long)p.n_list : p.n_list;   // entries the grid holds
+  if (items <= 0 || held <= 0) return hipSuccess;
   const bool mesh = p.n_meshes > 0, lds = p.lds_scene_bytes > 0;
   if (!p.list || p.wave_traversal || p.seg_per_item != 1 || p.pass_split || p.item_perm || p.tail_m || p.split_of ||
       p.steal_vals || p.n_items != items || p.tile_w != mcpt::tile_w_for(mesh, p.lds_scene_bytes) ||
-      (long long)p.n_tiles * (p.tile_w / 8) < p.n_list)
+      (long long)p.n_tiles * (p.tile_w / 8) < held)
     return hipErrorInvalidValue;
   dim3 block(p.tile_w * mcpt::kTileH), grid((unsigned)items);
   const size_t shm = lds ? (size_t)p.lds_scene_bytes : 0;

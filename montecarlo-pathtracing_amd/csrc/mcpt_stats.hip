@@ -52,6 +52,23 @@ __global__ __launch_bounds__(256) void stats_update_kernel(const float* __restri
   st[i] = s;
 }
 
+// stats_update_kernel's twin of a queued adaptive run: no pixel changes once the
+// active list is empty (count[0] == 0: the host loop stops there, and an update it never made would
+// turn an overflowed pixel's inf - inf into a NaN in S2); else the same update of every pixel
+__global__ __launch_bounds__(256) void stats_update_counted_kernel(const float* __restrict__ accum,
+                                                                   float4* __restrict__ st, long long n_px, float nf,
+                                                                   const int* __restrict__ count) {
+  if (count[0] <= 0) return;
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_px) return;
+  float4 s = st[i];
+  const float ynow = accum_luminance(accum, i);
+  const float d = ynow - s.x;
+  s.y = s.y + (d * d) / nf;
+  s.x = ynow;
+  st[i] = s;
+}
+
 constexpr int kErrorMaxBlocks = 2048;   // 8 workgroups per CU of a 256-CU chip
 
 // A workgroup's share of the frame record from its lanes' sums: wave shuffles, one LDS step, one
@@ -144,6 +161,14 @@ hipError_t mcpt_launch_stats_update(const float* accum, float4* state, long long
   if (n_px <= 0) return hipSuccess;
   hipLaunchKernelGGL(mcpt::stats_update_kernel, dim3((unsigned)((n_px + 255) / 256)), dim3(256), 0, stream, accum,
                      state, n_px, (float)n);
+  return hipGetLastError();
+}
+
+hipError_t mcpt_launch_stats_update_counted(const float* accum, float4* state, long long n_px, int n, const int* count,
+                                            hipStream_t stream) {
+  if (n_px <= 0) return hipSuccess;
+  hipLaunchKernelGGL(mcpt::stats_update_counted_kernel, dim3((unsigned)((n_px + 255) / 256)), dim3(256), 0, stream,
+                     accum, state, n_px, (float)n, count);
   return hipGetLastError();
 }
 

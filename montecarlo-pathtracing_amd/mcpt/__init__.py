@@ -86,6 +86,15 @@ class AdaptiveFiltered(ctypes.Structure):
                 ("max_rf", ctypes.c_float), ("mean_rf", ctypes.c_double)]
 
 
+class AdaptiveRun(ctypes.Structure):
+    """mcpt_adaptive_run_t (include/mcpt.h): what a queued adaptive run did."""
+    _fields_ = [("rounds_queued", ctypes.c_int), ("rounds_run", ctypes.c_int), ("selects_run", ctypes.c_int),
+                ("passes_run", ctypes.c_longlong), ("device_ms", ctypes.c_float)]
+
+
+ADAPTIVE_RUN_MAX_ROUNDS = 256   # MCPT_ADAPTIVE_RUN_MAX_ROUNDS
+
+
 class AdaptiveCheckpoint(ctypes.Structure):
     """mcpt_adaptive_checkpoint_t (include/mcpt.h): the header of an adaptive checkpoint file."""
     _fields_ = [("W", ctypes.c_int), ("rows", ctypes.c_int), ("pass_count", ctypes.c_int), ("next_pass", ctypes.c_int),
@@ -214,6 +223,10 @@ def _declare(L: ctypes.CDLL) -> None:
         "mcpt_adaptive_end": (i, [_vp]),
         "mcpt_adaptive_select": (i, [_vp, f, f, ctypes.POINTER(Adaptive)]),
         "mcpt_adaptive_select_filtered": (i, [_vp, f, f, f, i, f, f, ctypes.POINTER(AdaptiveFiltered)]),
+        "mcpt_adaptive_run": (i, [_vp, fp, fp, i, i, i, i, f, f, f, i, f, i, ctypes.POINTER(Adaptive), i,
+                                  ctypes.POINTER(AdaptiveRun)]),
+        "mcpt_adaptive_run_filtered": (i, [_vp, fp, fp, i, i, i, i, f, f, f, i, f, f, f, i, f, i,
+                                           ctypes.POINTER(AdaptiveFiltered), i, ctypes.POINTER(AdaptiveRun)]),
         "mcpt_read_active_blocks": (i, [_vp, ip, i, ip]),
         "mcpt_render_adaptive": (i, [_vp, fp, fp, i, i, f, i, f, i]),
         "mcpt_read_sample_counts": (i, [_vp, ip]),
@@ -967,12 +980,55 @@ class Renderer:
         _check(lib().mcpt_last_adaptive_ms(self._h, ctypes.byref(a), ctypes.byref(b)), "mcpt_last_adaptive_ms")
         return a.value, b.value
 
+    @staticmethod
+    def _filtered_dict(rec: AdaptiveFiltered) -> dict:
+        out = {k: getattr(rec.raw, k) for k, _ in Adaptive._fields_}
+        out.update({k: getattr(rec, k) for k in ("n_above_f", "sum_qf", "max_rf", "mean_rf")})
+        return out
+
+    def adaptive_run(self, invPV, invV, first_pass: int, n_passes: int, rounds: int, threshold: float,
+                     check_every: int = 1, mu_floor: float = ERROR_MU_FLOOR, date: float = 0.0, bounces: int = 3,
+                     refract_ind: float = 1.0, variant: int = MONTECARLO) -> dict:
+        """mcpt_adaptive_run: `rounds` rounds of {render_adaptive(first_pass + i * n_passes, n_passes),
+        on the schedule's rounds adaptive_select(threshold, mu_floor)} queued on the device, the same
+        bits as that loop, one wait at the end.  {"rounds_queued", "rounds_run", "selects_run",
+        "passes_run", "device_ms", "records": adaptive_select()'s dicts in order}."""
+        a, b = _f32(invPV, 16), _f32(invV, 16)
+        cap = max(int(rounds), 1)
+        recs, run = (Adaptive * cap)(), AdaptiveRun()
+        _check(lib().mcpt_adaptive_run(self._h, _fp(a), _fp(b), int(first_pass), int(n_passes), int(rounds),
+                                       int(check_every), float(threshold), float(mu_floor), float(date), int(bounces),
+                                       float(refract_ind), int(variant), recs, cap, ctypes.byref(run)),
+               "mcpt_adaptive_run")
+        out = {k: getattr(run, k) for k, _ in AdaptiveRun._fields_}
+        out["records"] = [{k: getattr(recs[j], k) for k, _ in Adaptive._fields_} for j in range(run.selects_run)]
+        return out
+
+    def adaptive_run_filtered(self, invPV, invV, first_pass: int, n_passes: int, rounds: int, threshold: float,
+                              check_every: int = 1, raw_cap: float = 64.0, mu_floor: float = ERROR_MU_FLOOR,
+                              iterations: int = 5, k_color: float = DENOISE_K_VARIANCE,
+                              sigma_plane: float = DENOISE_SIGMA_PLANE, date: float = 0.0, bounces: int = 3,
+                              refract_ind: float = 1.0, variant: int = MONTECARLO) -> dict:
+        """mcpt_adaptive_run_filtered: adaptive_run() whose selects are adaptive_select_filtered(threshold,
+        raw_cap, mu_floor, iterations, k_color, sigma_plane); the records are that call's dicts."""
+        a, b = _f32(invPV, 16), _f32(invV, 16)
+        cap = max(int(rounds), 1)
+        recs, run = (AdaptiveFiltered * cap)(), AdaptiveRun()
+        _check(lib().mcpt_adaptive_run_filtered(self._h, _fp(a), _fp(b), int(first_pass), int(n_passes), int(rounds),
+                                                int(check_every), float(threshold), float(raw_cap), float(mu_floor),
+                                                int(iterations), float(k_color), float(sigma_plane), float(date),
+                                                int(bounces), float(refract_ind), int(variant), recs, cap,
+                                                ctypes.byref(run)), "mcpt_adaptive_run_filtered")
+        out = {k: getattr(run, k) for k, _ in AdaptiveRun._fields_}
+        out["records"] = [self._filtered_dict(recs[j]) for j in range(run.selects_run)]
+        return out
+
     def render_adaptive_until(self, invPV, invV, threshold: float, batch: int = 32, max_passes: int = 4096,
                               min_passes: int = 0, check_every: int = 1, first_pass: int = 1, date: float = 0.0,
                               bounces: int = 3, refract_ind: float = 1.0, variant: int = MONTECARLO,
                               mu_floor: float = ERROR_MU_FLOOR, filtered: bool = False, raw_cap: float = 64.0,
                               iterations: int = 5, k_color: float = DENOISE_K_VARIANCE,
-                              sigma_plane: float = DENOISE_SIGMA_PLANE) -> dict:
+                              sigma_plane: float = DENOISE_SIGMA_PLANE, queued_rounds: int = 0) -> dict:
         """Begin a statistics window and the adaptive mode, then render passes first_pass,
         first_pass + 1, ... in calls of `batch` passes for the active blocks only, selecting after
         every `check_every` calls (from the second batch on, and at the cap), until no block is
@@ -981,19 +1037,43 @@ class Renderer:
         read_resolved() and read_sample_counts() serve the result.  filtered: the selects are
         adaptive_select_filtered(threshold, raw_cap, mu_floor, iterations, k_color, sigma_plane), the
         guides are rendered first unless they are current, and read_denoised() serves the last
-        select's image."""
-        if batch <= 0 or check_every <= 0 or max_passes <= 0 or not threshold > 0:
+        select's image.  queued_rounds K > 0: the calls go out as queued runs of up to K rounds
+        (adaptive_run / adaptive_run_filtered: one host wait per run instead of one per select);
+        the same record and the same "rendered" come back."""
+        if batch <= 0 or check_every <= 0 or max_passes <= 0 or not threshold > 0 or queued_rounds < 0:
             raise MCPTError("render_adaptive_until: batch, check_every, max_passes and threshold must be positive")
         if filtered:
             select = lambda: self.adaptive_select_filtered(threshold, raw_cap, mu_floor, iterations, k_color, sigma_plane)
+            run = lambda p, r: self.adaptive_run_filtered(invPV, invV, p, batch, r, threshold, check_every, raw_cap,
+                                                          mu_floor, iterations, k_color, sigma_plane, date, bounces,
+                                                          refract_ind, variant)
             if lib().mcpt_read_guides(self._h, None, None) == NO_GUIDES:      # (copies nothing: the guides' state alone)
                 self.render_guides(invPV, invV)
         else:
             select = lambda: self.adaptive_select(threshold, mu_floor)
+            run = lambda p, r: self.adaptive_run(invPV, invV, p, batch, r, threshold, check_every, mu_floor, date,
+                                                 bounces, refract_ind, variant)
         self.stats_begin()
         self.adaptive_begin(min_passes)
         done, calls, rec = 0, 0, None
         while done < max_passes:
+            # A run selects on the multiples of check_every counted from ITS first round and after its
+            # last round.  It therefore starts on a multiple of check_every calls, holds whole batches
+            # only, and ends on a multiple as well unless it ends at the cap; what does not fit (the
+            # short last batch, K below check_every) goes through the single calls below.
+            full = (max_passes - done) // batch
+            r = min(queued_rounds, full, ADAPTIVE_RUN_MAX_ROUNDS) if calls % check_every == 0 else 0
+            if r > 0 and not (r == full and done + r * batch == max_passes):
+                r -= r % check_every
+            if r > 0:
+                got = run(first_pass + done, r)
+                done += got["rounds_run"] * batch
+                calls += got["rounds_run"]
+                if got["records"]:
+                    rec = got["records"][-1]
+                if got["rounds_run"] < r or (rec is not None and rec["n_active_blocks"] == 0):
+                    break
+                continue
             n = min(batch, max_passes - done)
             self.render_adaptive(invPV, invV, first_pass + done, n, date, bounces, refract_ind, variant)
             done += n

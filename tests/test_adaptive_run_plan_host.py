@@ -1,0 +1,24 @@
+"""The schedule of a queued adaptive run (csrc/mcpt_adaptive_run_plan.h: which rounds select, the grid
+that holds the list on entry, the host loop's outcome from the selects' list lengths) is plain host
+C++: tests/cpp/adaptive_run_plan_test.cpp checks it against known answers on the CPU, as a plain
+build and as a stand-alone AddressSanitizer + UBSan build."""
+import os
+import subprocess
+
+import pytest
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(REPO, "montecarlo-pathtracing_amd", "csrc")
+CASES = ("schedule", "outcome", "list_groups")
+
+
+@pytest.mark.parametrize("flags", [["-O1"], ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]],
+                         ids=["plain", "sanitized"])
+def test_adaptive_run_plan_known_answers(tmp_path, flags):
+    out = str(tmp_path / "adaptive_run_plan_test")
+    subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror"] + flags + ["-I", CSRC,
+                    os.path.join(REPO, "tests", "cpp", "adaptive_run_plan_test.cpp"), "-o", out], check=True)
+    r = subprocess.run([out], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0, r.stdout + r.stderr
+    for name in CASES:
+        assert f"{name}: ok" in r.stdout, r.stdout
