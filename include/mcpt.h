@@ -37,6 +37,7 @@ enum mcpt_status {
   MCPT_ERR_NO_GUIDES = -7,   /* mcpt_denoise / mcpt_read_guides without current guide buffers */
   MCPT_ERR_NO_STATS = -8,    /* a statistics query with statistics off, fewer than two batches or no error map */
   MCPT_ERR_NO_ADAPTIVE = -9, /* an adaptive-sampling call with the adaptive mode off (mcpt_adaptive_begin) */
+  MCPT_ERR_NO_TEMPORAL = -10, /* a temporal call with the temporal mode off (mcpt_temporal_begin) */
 };
 
 /* integrator variants: the SrcLoader list of MontecarloGPU/montecarlo.cpp:27 */
@@ -703,6 +704,68 @@ extern int mcpt_adaptive_run_filtered(mcpt_ctx* ctx, const float* invPV, const f
                                float refract_ind, int variant, mcpt_adaptive_filtered_t* records, int records_capacity,
                                mcpt_adaptive_run_t* out);
 
+/* Temporal reprojection: carry the integrated frame across camera moves of a
+ * static scene.  A context in temporal mode keeps, per pixel of a full frame, the integrated colour,
+ * the variance of its mean, the history length and the guides of the frame the history was made with
+ * (104 B per pixel; 72 B when the guides are copied, MCPT_TEMPORAL_COPY=1).  Per camera k a caller
+ * runs: mcpt_clear_accum, mcpt_stats_begin, two or more mcpt_render batches (first_pass advancing
+ * across frames), mcpt_convergence, mcpt_render_guides(camera k), mcpt_temporal_accumulate(P·V of
+ * camera k-1), mcpt_denoise_temporal, mcpt_read_denoised.
+ *
+ * mcpt_temporal_begin: needs a target (else MCPT_ERR_NO_TARGET); allocates the history on the first
+ * call and marks it empty (on every call).  Asynchronous.  mcpt_temporal_end: mode off, buffers freed.
+ * mcpt_set_target* and mcpt_destroy end the mode; mcpt_upload_scene, mcpt_upload_meshes and
+ * mcpt_set_flat_face leave it on and mark the history empty; the accumulator, statistics and render
+ * calls do not touch the history.  With the mode off the other calls here return
+ * MCPT_ERR_NO_TEMPORAL and no other call does any work for it.
+ *
+ * mcpt_temporal_accumulate: for every pixel the current colour accum / (float)pass_count and the
+ * variance min(se^2, 2^60) of the held error map; its world position through prevPV16 (the FORWARD
+ * matrix P·V of the camera the history was made with, column-major: mcpt_mat4_inverse of that
+ * camera's invPV) gives a position in the previous frame, whose 2x2 history taps count when they
+ * show the same primitive key, lie within plane_tol * dist of the pixel's tangent plane and have a
+ * normal within N·Nq >= 0.875.  A pixel with surviving taps blends their bilinear mean h with weight
+ * 1 - 1/L, L = min(shortest tap history + 1, max_history): rgb = (1 - 1/L) h + c / L, variance =
+ * (1 - 1/L)^2 h.v + v / L^2; every other pixel starts over at {c, v}, length 1.  The history then
+ * holds the result and the current guides.  Preconditions, in this order, a refusal changing
+ * nothing: the mode on (else MCPT_ERR_NO_TEMPORAL); max_history in 1..65535, positive finite
+ * plane_tol, prevPV16 non-NULL unless the history is empty, a full-frame target in row order that
+ * holds passes, no gathered count plane, no retired adaptive block (else MCPT_ERR_INVALID_ARG); an
+ * error map, the gathered plane when valid else the own window's (else MCPT_ERR_NO_STATS); current
+ * guides (else MCPT_ERR_NO_GUIDES).  Asynchronous up to one wait for the record.
+ *
+ * mcpt_denoise_temporal: the variance filter (mcpt_denoise_variance's iterations, unchanged) from the
+ * temporal image, first input {rgb, the 3x3 key-aware prefilter of its variance}.  Needs, in this
+ * order: the mode on; iterations in 0..8, positive finite k_color and sigma_plane (else
+ * MCPT_ERR_INVALID_ARG); an accumulate since the history was last empty (else MCPT_ERR_NO_STATS);
+ * current guides (else MCPT_ERR_NO_GUIDES).  Its result is a variance filter's: mcpt_read_denoised,
+ * mcpt_read_denoised_variance and the mcpt_*denoise*_ms / _path queries serve it.  On a first frame
+ * it gives mcpt_denoise_variance's bits. */
+#define MCPT_TEMPORAL_MAX_HISTORY 65535
+typedef struct mcpt_temporal_t {
+  long long n_px;
+  long long n_history;    /* pixels that blended a history in */
+  long long n_new;        /* = n_px - n_history = n_miss + n_offscreen + n_rejected */
+  long long n_miss;       /* no primary hit (key < 0) */
+  long long n_offscreen;  /* behind the previous camera or outside its frame */
+  long long n_rejected;   /* no tap survived (on an empty history: every pixel with a hit) */
+  long long sum_len;      /* of the new history lengths */
+  int max_len;
+  long long frames;       /* accumulates since the history was last empty, this one included */
+} mcpt_temporal_t;
+int mcpt_temporal_begin(mcpt_ctx* ctx);
+int mcpt_temporal_end(mcpt_ctx* ctx);
+int mcpt_temporal_accumulate(mcpt_ctx* ctx, const float* prevPV16, int max_history, float plane_tol,
+                             mcpt_temporal_t* out);
+int mcpt_denoise_temporal(mcpt_ctx* ctx, int iterations, float k_color, float sigma_plane);
+/* the history: rgbv4 n x 4 f32 {rgb, variance}, history_len n i32 (either NULL); MCPT_ERR_NO_STATS
+ * while the history is empty.  Synchronizes. */
+int mcpt_read_temporal(mcpt_ctx* ctx, float* rgbv4, int* history_len);
+int mcpt_temporal_info(mcpt_ctx* ctx, int* on, int* history_valid, long long* frames);
+/* device ms of the last accumulate: its kernel, and the guides' copy behind it (0 in the ping-pong
+ * form); either NULL */
+int mcpt_last_temporal_ms(mcpt_ctx* ctx, float* accumulate_ms, float* copy_ms);
+
 /* DrawSampling's point cloud (DrawSampling/draw_sampling.cpp:144-150, tp/sampling_base.vert
  * seeding, tp/hsphere.vert random_ray): point k = random_ray(normalize(normal), roughness)
  * with seed floatBitsToUint(fseed) + k * nb_used * (11, 43, 67).  out: n × 3 f32 (host). */
@@ -785,6 +848,9 @@ int mcpt_transfo_translate(float x, float y, float z, float* out16);           /
 int mcpt_transfo_scale(float x, float y, float z, float* out16);               /* Transfo::scale */
 int mcpt_transfo_rotate(int axis, float degrees, float* out16);                /* rotateX/Y/Z: axis 0/1/2 */
 int mcpt_mat4_mul(const float* a16, const float* b16, float* out16);           /* GLMat4 a * b */
+/* a^-1 computed in double (cofactors) and rounded to f32; MCPT_ERR_INVALID_ARG for a singular or
+ * non-finite matrix.  Turns a camera's invPV into the P·V mcpt_temporal_accumulate takes. */
+int mcpt_mat4_inverse(const float* a16, float* out16);
 /* fs_frag (montecarlo.cpp:59-70): out = accum / pass_count, per channel */
 int mcpt_average(const float* accum, long long n_values, int pass_count, float* out);
 /* averaged image (H rows × W × RGB f32, row 0 = bottom) to a little-endian PFM */

@@ -65,6 +65,12 @@ struct GLMat4 {
     check(mcpt_mat4_mul(m, b.m, r.m), "mcpt_mat4_mul");
     return r;
   }
+  // mcpt_mat4_inverse (double arithmetic, rounded once); throws for a singular matrix
+  GLMat4 inverse() const {
+    GLMat4 r;
+    check(mcpt_mat4_inverse(m, r.m), "mcpt_mat4_inverse");
+    return r;
+  }
 };
 
 namespace Transfo {
@@ -273,6 +279,18 @@ struct Camera {
     check(mcpt_camera_canonical(W, H, c.invPV.m, c.invV.m), "mcpt_camera_canonical");
     return c;
   }
+  // the canonical camera with the world turned `deg` degrees about the scene's up axis (z): P·V
+  // becomes P·V·R, so both inverses get R^-1 in front
+  static Camera orbit(int W, int H, float deg) {
+    const Camera c = canonical(W, H);
+    const GLMat4 rinv = Transfo::rotateZ(-deg);
+    Camera o;
+    o.invPV = rinv * c.invPV;
+    o.invV = rinv * c.invV;
+    return o;
+  }
+  // the forward matrix P·V (what temporal_accumulate takes for the previous frame's camera)
+  GLMat4 PV() const { return invPV.inverse(); }
 };
 
 // prg_ray + the RGB32F accumulation FBO (montecarlo.cpp:384-386, 408-477), one GPU
@@ -465,6 +483,32 @@ class Renderer {
   }
   void last_stats_ms(float& update_ms, float& error_ms) const {
     check(mcpt_last_stats_ms(c_, &update_ms, &error_ms), "mcpt_last_stats_ms");
+  }
+  // ---- temporal reprojection across camera moves (mcpt.h): the defaults are the
+  // sweep's (tools/temporal_bench.py)
+  static constexpr int kTemporalMaxHistory = 8;
+  static constexpr float kTemporalPlaneTol = 0.01f;
+  void temporal_begin() { check(mcpt_temporal_begin(c_), "mcpt_temporal_begin"); }
+  void temporal_end() { check(mcpt_temporal_end(c_), "mcpt_temporal_end"); }
+  // device ms of the last accumulate: its kernel and the guides' copy behind it (0: ping-pong)
+  void last_temporal_ms(float& accumulate_ms, float& copy_ms) const {
+    check(mcpt_last_temporal_ms(c_, &accumulate_ms, &copy_ms), "mcpt_last_temporal_ms");
+  }
+  // prevPV: the P·V of the camera the history was made with (null only while the history is empty)
+  mcpt_temporal_t temporal_accumulate(const GLMat4* prevPV, int max_history = kTemporalMaxHistory,
+                                      float plane_tol = kTemporalPlaneTol) {
+    mcpt_temporal_t rec;
+    check(mcpt_temporal_accumulate(c_, prevPV ? prevPV->m : nullptr, max_history, plane_tol, &rec),
+          "mcpt_temporal_accumulate");
+    return rec;
+  }
+  // the variance filter from the temporal image; read_denoised_variance() serves its variance
+  std::vector<float> denoise_temporal(int iterations = 5, float k_color = kDenoiseKVariance,
+                                      float sigma_plane = kDenoiseSigmaPlane) {
+    check(mcpt_denoise_temporal(c_, iterations, k_color, sigma_plane), "mcpt_denoise_temporal");
+    std::vector<float> img((size_t)rows_ * W_ * 3);
+    check(mcpt_read_denoised(c_, img.data()), "mcpt_read_denoised");
+    return img;
   }
   // Render passes first_pass, first_pass + 1, ... in calls of `batch` passes until the mean relative
   // error is at most target_error or max_passes are rendered; the convergence is queried after every

@@ -27,6 +27,8 @@
 //       filter; --aov also writes s6_variance.pfm)
 //   mcpt_render --scene 6 --spp 1024 --chunk 32 --adaptive --target-error 0.05 --target-denoised --out s6.png
 //       (render until the DENOISED image meets the error: mcpt_adaptive_select_filtered; one device)
+//   mcpt_render --scene 6 --spp 4 --frames 100 --orbit-deg 1 --temporal --denoise-variance --out orbit.png
+//       (an orbit of 100 cameras, 4 spp each, every frame reprojected into the next: orbit_000.png ...)
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -58,6 +60,9 @@ struct Args {
   float raw_cap = 64.0f;      // --raw-cap R: with --target-denoised a block also stays while its largest raw r > R (64: off)
   bool adaptive = false;      // --adaptive: --target-error is the per-pixel threshold; retired 8x8 blocks stop receiving passes
   int queue_rounds = 0;       // --queue-rounds K: with --adaptive, one device: the chunks go out as queued runs of up to K (0: off)
+  int frames = 0;             // --frames N: N cameras, one image each (0: off; with --temporal alone: 1)
+  float orbit_deg = 0.0f;     // --orbit-deg D: frame k's world is turned k * D degrees about the up axis
+  int temporal = -1;          // --temporal [max_history]: every frame is reprojected into the next (-1: off)
 };
 
 bool parse_list(const char* v, std::vector<int>& out) {
@@ -107,7 +112,15 @@ void usage() {
                "                                   filtered image as --denoise-variance N would)\n"
                "                   [--queue-rounds K]   (with --adaptive, one device: up to K chunks and their selects\n"
                "                                         are queued on the device per host wait, 1..256; the same\n"
-               "                                         image; a checkpoint is written after each run)\n");
+               "                                         image; a checkpoint is written after each run)\n"
+               "                   [--temporal [max_history]] [--frames N] [--orbit-deg D]   (N cameras, frame k with the\n"
+               "                                   world turned k * D degrees about the up axis, --spp passes each in\n"
+               "                                   two batches or more; every frame's result is reprojected into the\n"
+               "                                   next and blended over at most max_history frames (default 8, 1..65535),\n"
+               "                                   then filtered: needs --denoise-variance; writes NAME_000.png, ...\n"
+               "                                   for --out NAME.png (default out.png); one device, not with\n"
+               "                                   --adaptive, --target-error, --checkpoint, --resume, --aov,\n"
+               "                                   --denoise or --denoise-guided)\n");
 }
 
 // a refused combination: why, then the usage (parse's false)
@@ -140,6 +153,12 @@ bool parse(int argc, char** argv, Args& a) {
       a.denoise_variance = 5;
       if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') a.denoise_variance = std::atoi(argv[++i]);
       if (a.denoise_variance > 8) return false;
+      continue;
+    }
+    if (k == "--temporal") {
+      a.temporal = mcpt::Renderer::kTemporalMaxHistory;
+      if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') a.temporal = std::atoi(argv[++i]);
+      if (a.temporal < 1 || a.temporal > MCPT_TEMPORAL_MAX_HISTORY) return false;
       continue;
     }
     if (k == "--target-denoised") {
@@ -178,6 +197,11 @@ bool parse(int argc, char** argv, Args& a) {
       a.queue_rounds = std::atoi(v);
       if (a.queue_rounds < 1 || a.queue_rounds > MCPT_ADAPTIVE_RUN_MAX_ROUNDS) return false;
     }
+    else if (k == "--frames") {
+      a.frames = std::atoi(v);
+      if (a.frames < 1 || a.frames > 100000) return false;
+    }
+    else if (k == "--orbit-deg") a.orbit_deg = (float)std::atof(v);
     else if (k == "--raw-cap") {
       a.raw_cap = (float)std::atof(v);
       if (!(a.raw_cap > 0.0f)) return false;
@@ -195,6 +219,22 @@ bool parse(int argc, char** argv, Args& a) {
     } else {
       return false;
     }
+  }
+  // (first: these refusals carry a message)
+  if (a.temporal < 0 && (a.frames > 0 || a.orbit_deg != 0.0f))
+    return refuse("--frames and --orbit-deg move the camera of a --temporal render: give --temporal");
+  if (a.temporal >= 0) {
+    if (a.frames == 0) a.frames = 1;
+    if (!a.devices.empty()) return refuse("--temporal keeps its history on one device: not with --devices (not built)");
+    if (a.adaptive || a.target_error > 0.0)
+      return refuse("--temporal blends frames of one sample count: not with --adaptive or --target-error (not built)");
+    if (!a.checkpoint.empty() || !a.resume.empty())
+      return refuse("--temporal: the history is not part of a checkpoint: not with --checkpoint or --resume (not built)");
+    if (a.denoise >= 0 || a.denoise_guided >= 0)
+      return refuse("--temporal filters with the variance filter alone: not with --denoise or --denoise-guided");
+    if (!a.aov.empty()) return refuse("--temporal writes its frames only: not with --aov (not built)");
+    if (a.denoise_variance < 0) return refuse("--temporal filters with the variance filter: give --denoise-variance [N]");
+    if (a.spp < 2) return refuse("--temporal needs two batches per frame for its error map: --spp 2 or more");
   }
   if (!a.devices.empty() && (!a.checkpoint.empty() || !a.resume.empty())) return false;   // one device only
   // (stopping N host threads on a merged record is not built: a uniform --target-error is one device's)
@@ -221,6 +261,74 @@ bool parse(int argc, char** argv, Args& a) {
   return a.width > 0 && a.height > 0 && a.spp >= 0 && a.chunk > 0 && a.subsampling >= 0 && a.subsampling < 16;
 }
 
+// the threshold of a convergence query that is made for its error map alone (no --target-error): the
+// map does not depend on it
+constexpr float kMapThreshold = 0.05f;
+
+// NAME.ext -> NAME_007.ext
+std::string frame_path(const std::string& path, int k) {
+  const size_t dot = path.find_last_of('.'), slash = path.find_last_of('/');
+  const bool ext = dot != std::string::npos && (slash == std::string::npos || dot > slash);
+  char num[16];
+  std::snprintf(num, sizeof(num), "_%03d", k);
+  return ext ? path.substr(0, dot) + num + path.substr(dot) : path + num;
+}
+
+// --temporal: a.frames cameras on one device, the loop of mcpt.h's temporal section per camera.  The
+// passes keep advancing across the frames (independent samples); a frame's passes go out in batches
+// of at most --chunk, two at the least.
+int run_temporal(const Args& a, mcpt::BVH_GPU_Scene& scene, int W, int H) {
+  mcpt::Renderer r(a.device);
+  r.set_traversal(a.traversal);
+  r.upload(scene);
+  r.set_target(W, H);
+  r.temporal_begin();
+  const int batch = std::min(a.chunk, (a.spp + 1) / 2);
+  const std::string png = a.png.empty() && a.pfm.empty() ? "out.png" : a.png;
+  double kernel_ms = 0.0, temporal_ms = 0.0, filter_ms = 0.0;
+  mcpt_temporal_t rec{};
+  mcpt::GLMat4 prev;
+  int pass = a.first_pass;
+  double mean = 0.0;
+  const auto t0 = std::chrono::steady_clock::now();
+  for (int k = 0; k < a.frames; ++k) {
+    const mcpt::Camera cam = mcpt::Camera::orbit(a.width, a.height, (float)k * a.orbit_deg);
+    r.clear_accum();
+    r.stats_begin();
+    for (int done = 0; done < a.spp; done += batch) {
+      const int n = std::min(batch, a.spp - done);
+      r.render(cam, pass, n, a.date, a.bounces, a.ior, a.variant);
+      kernel_ms += r.last_render_ms();
+      pass += n;
+    }
+    r.convergence(kMapThreshold);
+    r.render_guides(cam);
+    rec = r.temporal_accumulate(k ? &prev : nullptr, a.temporal);
+    const std::vector<float> img = r.denoise_temporal(a.denoise_variance);
+    float am = 0.0f, cm = 0.0f, gm = 0.0f, fm = 0.0f;
+    r.last_temporal_ms(am, cm);
+    r.last_denoise_ms(gm, fm);
+    temporal_ms += am + cm;
+    filter_ms += fm;
+    prev = cam.PV();
+    if (!png.empty()) mcpt::write_png(frame_path(png, k), img, W, H);
+    if (!a.pfm.empty()) mcpt::write_pfm(frame_path(a.pfm, k), img, W, H);
+    mean = 0.0;
+    for (float v : img) mean += v;
+    mean /= (double)(img.size() ? img.size() : 1);
+  }
+  const double wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  std::printf("{\"scene\": %d, \"width\": %d, \"height\": %d, \"spp\": %d, \"bounces\": %d, \"frames\": %d, "
+              "\"orbit_deg\": %g, \"temporal\": %d, \"denoise_variance\": %d, \"kernel_ms\": %.3f, \"temporal_ms\": %.3f, "
+              "\"filter_ms\": %.3f, \"wall_ms\": %.3f, \"mean\": %.6f, \"n_history\": %lld, \"n_new\": %lld, "
+              "\"n_miss\": %lld, \"n_offscreen\": %lld, \"n_rejected\": %lld, \"max_len\": %d, \"mean_len\": %.4f, "
+              "\"passes\": %d}\n",
+              a.scene, W, H, a.spp, a.bounces, a.frames, a.orbit_deg, a.temporal, a.denoise_variance, kernel_ms, temporal_ms,
+              filter_ms, wall_ms, mean, rec.n_history, rec.n_new, rec.n_miss, rec.n_offscreen, rec.n_rejected, rec.max_len,
+              rec.n_px > 0 ? (double)rec.sum_len / (double)rec.n_px : 0.0, pass - a.first_pass);
+  return 0;
+}
+
 // the adaptive part of the JSON line from a select's record (a frame's, or the shards' combined)
 std::string adaptive_json(double target_error, bool converged, const mcpt_adaptive_t& rec) {
   char buf[400];
@@ -234,10 +342,6 @@ std::string adaptive_json(double target_error, bool converged, const mcpt_adapti
                 rec.n_px > 0 ? (double)rec.samples / (double)rec.n_px : 0.0);
   return buf;
 }
-
-// the threshold of a convergence query that is made for its error map alone (no --target-error): the
-// map does not depend on it
-constexpr float kMapThreshold = 0.05f;
 
 // --denoise / --aov on the context that holds the whole frame: the guide buffers, the AOV files,
 // and the filtered image in place of the averaged one
@@ -314,6 +418,7 @@ int main(int argc, char** argv) {
     // sub-sampling renders the FBO at (W>>k) x (H>>k) with the window's aspect (montecarlo.cpp:616-626)
     const int W = a.width >> a.subsampling, H = a.height >> a.subsampling;
     if (W <= 0 || H <= 0) throw std::runtime_error("sub-sampled framebuffer is empty");
+    if (a.temporal >= 0) return run_temporal(a, scene, W, H);
     const mcpt::Camera cam = mcpt::Camera::canonical(a.width, a.height);
 
     double kernel_ms = 0.0, wall_ms = 0.0, gather_ms = 0.0, guides_ms = 0.0, filter_ms = 0.0;

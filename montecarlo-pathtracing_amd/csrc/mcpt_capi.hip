@@ -124,6 +124,7 @@ const char* mcpt_error_string(int status) {
                        : status == MCPT_ERR_NO_GUIDES ? "no current guide buffers"
                        : status == MCPT_ERR_NO_STATS  ? "no noise statistics"
                        : status == MCPT_ERR_NO_ADAPTIVE ? "adaptive mode is off"
+                       : status == MCPT_ERR_NO_TEMPORAL ? "temporal mode is off"
                                                       : "error";
     std::snprintf(g_detail, sizeof(g_detail), "%s (%s)", base, g_last_error);
     return g_detail;
@@ -139,6 +140,7 @@ const char* mcpt_error_string(int status) {
     case MCPT_ERR_NO_GUIDES: return "no current guide buffers (call mcpt_render_guides)";
     case MCPT_ERR_NO_STATS: return "no noise statistics (mcpt_stats_begin, two batches, mcpt_convergence)";
     case MCPT_ERR_NO_ADAPTIVE: return "adaptive mode is off (mcpt_adaptive_begin)";
+    case MCPT_ERR_NO_TEMPORAL: return "temporal mode is off (mcpt_temporal_begin)";
     default: return "unknown status";
   }
 }
@@ -243,6 +245,8 @@ int mcpt_destroy(mcpt_ctx* c) {
   for (hipEvent_t e : c->ad_ev) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->run_ev) if (e) (void)hipEventDestroy(e);
   free_count_plane(c);
+  free_temporal(c);
+  for (hipEvent_t e : c->tp_ev) if (e) (void)hipEventDestroy(e);
   (void)hipFree(c->d_accum);
   (void)hipFree(c->d_rows);
   (void)hipFree(c->d_events);
@@ -344,6 +348,7 @@ int mcpt_upload_scene(mcpt_ctx* c, const float* prims, int n_prims, const float*
   c->n_prims = n_prims; c->depth = c->tuner.depth = depth; c->nb_emissive = nb_emissives;
   c->mesh_ids = mesh_ids;
   c->guides_valid = false;
+  c->tp_frames = 0;               // (temporal mode: the history shows another scene)
   free_meshes(c);                 // a new scene drops the previous meshes (upload them again)
   c->has_scene = true;
   reset_tuning(c);
@@ -407,6 +412,7 @@ int mcpt_upload_meshes(mcpt_ctx* c, int n_meshes, const int* info, int n_nodes, 
   HIP_OR_RETURN(hipStreamSynchronize(c->stream));
   free_meshes(c);
   c->guides_valid = false;
+  c->tp_frames = 0;
   if (n_meshes == 0) {
     for (int id : c->mesh_ids)
       if (id >= 0) return set_err(MCPT_ERR_BAD_SCENE, "the scene has mesh instances but no meshes were uploaded");
@@ -500,6 +506,7 @@ int mcpt_set_flat_face(mcpt_ctx* c, int flat_face) {
   if (!c) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
   c->flat_face = flat_face ? 1 : 0;
   c->guides_valid = false;
+  c->tp_frames = 0;
   return MCPT_OK;
 }
 
@@ -516,6 +523,7 @@ static int set_target_rows(mcpt_ctx* c, int W, int H, const int* rows, int n_row
   free_stats(c);     // (statistics off: a new target begins again)
   free_adaptive(c);  // (adaptive mode off: its blocks are the old target's)
   free_count_plane(c);   // (a gathered frame's counts are the old target's)
+  free_temporal(c);  // (temporal mode off: its history is the old target's)
   size_t bytes = (size_t)n_rows * W * 3 * sizeof(float);
   if (bytes != c->accum_bytes) {
     (void)hipFree(c->d_accum);

@@ -114,6 +114,10 @@ int mcpt_read_guides(mcpt_ctx* c, float* guide8, float* albedo4) {
   return MCPT_OK;
 }
 
+// the filter's iterations from the first input in d_dn[0] (defined behind denoise_run)
+static int atrous_iterations(mcpt_ctx* c, int iterations, float sigma_color, float sigma_plane, bool guided,
+                             bool variance, const float2* emap, bool naive, bool timed);
+
 // mcpt_denoise (guided false: sigma_color is the global width) and mcpt_denoise_guided (guided
 // true: sigma_color is k_color, the width per pixel k_color * 2^-s * se from the error map);
 // resolved: the mcpt_denoise_resolved* forms, whose input is accum / (float)count with every
@@ -148,7 +152,6 @@ static int denoise_run(mcpt_ctx* c, int iterations, float sigma_color, float sig
   // which kernel runs steps 1 and 2 (same bits): MCPT_DENOISE_NAIVE=1 the
   // global-tap kernel, =0 the LDS-tile kernels, unset the measured default
   const bool naive = env_int("MCPT_DENOISE_NAIVE", kAtrousNaiveDefault) != 0;
-  int lds_mask = 0;
   const long long n = (long long)c->H * c->W;
   // (the context's stream is ordered after all queued renders: their combines run on it)
   if (timed) HIP_OR_RETURN(hipEventRecord(c->dn_ev[9], c->stream));
@@ -161,6 +164,13 @@ static int denoise_run(mcpt_ctx* c, int iterations, float sigma_color, float sig
   else
     HIP_OR_RETURN(mcpt_launch_average4(c->d_accum, c->d_dn[0], n, c->pass_count, c->stream));
   if (timed) HIP_OR_RETURN(hipEventRecord(c->dn_ev[0], c->stream));
+  return atrous_iterations(c, iterations, sigma_color, sigma_plane, guided, variance, emap, naive, timed);
+}
+
+// (denoise_run, mcpt_denoise_temporal)
+static int atrous_iterations(mcpt_ctx* c, int iterations, float sigma_color, float sigma_plane, bool guided,
+                             bool variance, const float2* emap, bool naive, bool timed) {
+  int lds_mask = 0;
   for (int s = 0; s < iterations; ++s) {
     const int step = 1 << s;
     // the iteration's constants in binary32: 2^-s and step are exact factors
@@ -891,6 +901,165 @@ int mcpt_error_map_record(mcpt_ctx* c, float threshold, mcpt_convergence_t* out)
     out->batches = 0;
   }
   return MCPT_OK;
+}
+
+// ---- temporal reprojection (mcpt_temporal.hip)
+// which form keeps the history's guides when MCPT_TEMPORAL_COPY is unset: 0 the ping-pong (the
+// kernel writes them), 1 a device copy behind the kernel (the A/B: tools/temporal_bench.py,
+// profiles/temporal_bench.json); read by mcpt_temporal_begin when it allocates
+constexpr int kTemporalCopyDefault = 0;
+
+int mcpt_temporal_begin(mcpt_ctx* c) {
+  if (!c) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  if (!c->has_target) return set_err(MCPT_ERR_NO_TARGET, "no render target");
+  HIP_OR_RETURN(hipSetDevice(c->device));
+  if (!c->d_tp_rec) {
+    const size_t n = (size_t)c->n_local_rows * c->W;
+    c->tp_copy = env_int("MCPT_TEMPORAL_COPY", kTemporalCopyDefault) != 0;
+    hipError_t e = hipMalloc(&c->d_tp_rec, sizeof(unsigned long long) * mcpt::kStatsRecWords);
+    for (int k = 0; k < 2 && e == hipSuccess && n; ++k) {
+      e = hipMalloc(&c->d_tp_c[k], n * sizeof(float4));
+      if (e == hipSuccess) e = hipMalloc(&c->d_tp_len[k], n * sizeof(int));
+      if (e == hipSuccess && (k == 0 || !c->tp_copy)) e = hipMalloc(&c->d_tp_g[k], n * 2 * sizeof(float4));
+    }
+    if (e != hipSuccess) {
+      free_temporal(c);
+      return set_err(MCPT_ERR_HIP, "mcpt_temporal_begin: hipMalloc", e);
+    }
+  }
+  c->tp_on = true;
+  c->tp_frames = 0;
+  return MCPT_OK;
+}
+
+int mcpt_temporal_end(mcpt_ctx* c) {
+  if (!c) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  HIP_OR_RETURN(hipSetDevice(c->device));
+  if (c->d_tp_rec) HIP_OR_RETURN(hipStreamSynchronize(c->stream));   // (a queued filter still reads the history)
+  free_temporal(c);
+  return MCPT_OK;
+}
+
+int mcpt_temporal_info(mcpt_ctx* c, int* on, int* history_valid, long long* frames) {
+  if (!c) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  if (on) *on = c->tp_on ? 1 : 0;
+  if (history_valid) *history_valid = c->tp_on && c->tp_frames > 0 ? 1 : 0;
+  if (frames) *frames = c->tp_on ? c->tp_frames : 0;
+  return MCPT_OK;
+}
+
+int mcpt_temporal_accumulate(mcpt_ctx* c, const float* prevPV16, int max_history, float plane_tol,
+                             mcpt_temporal_t* out) {
+  if (!c) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  if (!c->tp_on) return set_err(MCPT_ERR_NO_TEMPORAL, "mcpt_temporal_accumulate: temporal mode is off (mcpt_temporal_begin)");
+  if (!out) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  if (max_history < 1 || max_history > MCPT_TEMPORAL_MAX_HISTORY)
+    return set_err(MCPT_ERR_INVALID_ARG, "mcpt_temporal_accumulate: max_history not in 1..65535");
+  if (!(plane_tol > 0.0f) || !std::isfinite(plane_tol))
+    return set_err(MCPT_ERR_INVALID_ARG, "mcpt_temporal_accumulate: plane_tol must be positive and finite");
+  const bool empty = c->tp_frames == 0;
+  if (!empty && !prevPV16)
+    return set_err(MCPT_ERR_INVALID_ARG, "mcpt_temporal_accumulate: the history needs the previous camera's P*V");
+  if (!plan::is_full_frame(c->rows, c->H))
+    return set_err(MCPT_ERR_INVALID_ARG, "mcpt_temporal_accumulate: needs a full-frame target (gather the shards first)");
+  if (c->pass_count <= 0)
+    return set_err(MCPT_ERR_INVALID_ARG, "mcpt_temporal_accumulate: the accumulator holds no passes");
+  if (c->plane_valid)
+    return set_err(MCPT_ERR_INVALID_ARG, "mcpt_temporal_accumulate: the context holds a gathered frame's counts");
+  if (c->ad_on && c->ad_n_list < c->ad_n_blocks)
+    return set_err(MCPT_ERR_INVALID_ARG, "mcpt_temporal_accumulate: adaptive mode has retired blocks (per-pixel sample counts)");
+  const float2* emap = held_error_map(c);
+  if (error_map_source(c) == 0)
+    return set_err(MCPT_ERR_NO_STATS, "mcpt_temporal_accumulate: no error map (mcpt_convergence) of the current statistics");
+  if (!c->guides_valid)
+    return set_err(MCPT_ERR_NO_GUIDES, "mcpt_temporal_accumulate: no guides rendered for this target and scene");
+  HIP_OR_RETURN(hipSetDevice(c->device));
+  HIP_OR_RETURN(ensure_timing_events(c->tp_ev, 3));
+  const int in = c->tp_cur, to = in ^ 1;
+  mcpt::TemporalParams p;
+  std::memset(&p, 0, sizeof(p));
+  p.accum = c->d_accum; p.emap = emap; p.guide = c->d_guide;
+  p.hc_in = c->d_tp_c[in]; p.hl_in = c->d_tp_len[in]; p.hg_in = c->d_tp_g[c->tp_copy ? 0 : in];
+  p.hc_out = c->d_tp_c[to]; p.hl_out = c->d_tp_len[to]; p.hg_out = c->tp_copy ? nullptr : c->d_tp_g[to];
+  p.rec = c->d_tp_rec;
+  p.W = c->W; p.H = c->H; p.nb = (float)c->pass_count;
+  p.max_history = max_history; p.plane_tol = plane_tol; p.empty = empty ? 1 : 0;
+  if (!empty) std::memcpy(p.M, prevPV16, sizeof(p.M));
+  const size_t n = (size_t)c->H * c->W;
+  // (the context's stream is ordered after all queued renders: their combines run on it)
+  // (the record is zeroed before the timed interval: the events enclose the kernel alone)
+  HIP_OR_RETURN(hipMemsetAsync(c->d_tp_rec, 0, sizeof(unsigned long long) * mcpt::kStatsRecWords, c->stream));
+  HIP_OR_RETURN(hipEventRecord(c->tp_ev[0], c->stream));
+  HIP_OR_RETURN(mcpt_launch_temporal(p, c->stream));
+  HIP_OR_RETURN(hipEventRecord(c->tp_ev[1], c->stream));
+  if (c->tp_copy) {
+    if (n)
+      HIP_OR_RETURN(hipMemcpyAsync(c->d_tp_g[0], c->d_guide, n * 2 * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
+    HIP_OR_RETURN(hipEventRecord(c->tp_ev[2], c->stream));
+  }
+  c->tp_cur = to;
+  c->tp_frames += 1;
+  c->tp_timed = true;
+  unsigned long long part[mcpt::kStatsRecWords] = {};
+  HIP_OR_RETURN(hipMemcpyAsync(part, c->d_tp_rec, sizeof(part), hipMemcpyDeviceToHost, c->stream));
+  HIP_OR_RETURN(hipStreamSynchronize(c->stream));
+  unsigned long long h[6] = {0, 0, 0, 0, 0, 0};
+  for (int s = 0; s < mcpt::kStatsRecSlots; ++s) {
+    const unsigned long long* q = part + (size_t)s * mcpt::kStatsRecStride;
+    for (int w = 0; w < 5; ++w) h[w] += q[w];
+    h[5] = std::max(h[5], q[5] & 0xffffffffull);
+  }
+  out->n_px = (long long)n;
+  out->n_history = (long long)h[0];
+  out->n_miss = (long long)h[1];
+  out->n_offscreen = (long long)h[2];
+  out->n_rejected = (long long)h[3];
+  out->n_new = out->n_miss + out->n_offscreen + out->n_rejected;
+  out->sum_len = (long long)h[4];
+  out->max_len = (int)h[5];
+  out->frames = c->tp_frames;
+  return MCPT_OK;
+}
+
+int mcpt_denoise_temporal(mcpt_ctx* c, int iterations, float k_color, float sigma_plane) {
+  if (!c) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  if (!c->tp_on) return set_err(MCPT_ERR_NO_TEMPORAL, "mcpt_denoise_temporal: temporal mode is off (mcpt_temporal_begin)");
+  if (iterations < 0 || iterations > 8) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_denoise_temporal: iterations not in 0..8");
+  if (!(k_color > 0.0f) || !(sigma_plane > 0.0f) || !std::isfinite(k_color) || !std::isfinite(sigma_plane))
+    return set_err(MCPT_ERR_INVALID_ARG, "mcpt_denoise_temporal: k_color and sigma_plane must be positive and finite");
+  if (c->tp_frames == 0)
+    return set_err(MCPT_ERR_NO_STATS, "mcpt_denoise_temporal: the history is empty (mcpt_temporal_accumulate)");
+  if (!c->guides_valid) return set_err(MCPT_ERR_NO_GUIDES, "mcpt_denoise_temporal: no guides rendered for this target and scene");
+  HIP_OR_RETURN(hipSetDevice(c->device));
+  HIP_OR_RETURN(ensure_denoise_buffers(c));
+  HIP_OR_RETURN(ensure_timing_events(c->dn_ev, 10));
+  const bool naive = env_int("MCPT_DENOISE_NAIVE", kAtrousNaiveDefault) != 0;
+  HIP_OR_RETURN(hipEventRecord(c->dn_ev[9], c->stream));
+  HIP_OR_RETURN(mcpt_launch_temporal_init(c->d_tp_c[c->tp_cur], c->d_dn[0], c->d_guide, c->W, c->H, c->stream));
+  HIP_OR_RETURN(hipEventRecord(c->dn_ev[0], c->stream));
+  return atrous_iterations(c, iterations, k_color, sigma_plane, true, true, nullptr, naive, true);
+}
+
+int mcpt_read_temporal(mcpt_ctx* c, float* rgbv4, int* history_len) {
+  if (!c) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  if (!c->tp_on) return set_err(MCPT_ERR_NO_TEMPORAL, "mcpt_read_temporal: temporal mode is off (mcpt_temporal_begin)");
+  if (c->tp_frames == 0) return set_err(MCPT_ERR_NO_STATS, "mcpt_read_temporal: the history is empty (mcpt_temporal_accumulate)");
+  HIP_OR_RETURN(hipSetDevice(c->device));
+  const size_t n = (size_t)c->n_local_rows * c->W;
+  if (rgbv4 && n)
+    HIP_OR_RETURN(hipMemcpyAsync(rgbv4, c->d_tp_c[c->tp_cur], n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+  if (history_len && n)
+    HIP_OR_RETURN(hipMemcpyAsync(history_len, c->d_tp_len[c->tp_cur], n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIP_OR_RETURN(hipStreamSynchronize(c->stream));
+  return MCPT_OK;
+}
+
+int mcpt_last_temporal_ms(mcpt_ctx* c, float* accumulate_ms, float* copy_ms) {
+  if (!c) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  if (!c->tp_on) return set_err(MCPT_ERR_NO_TEMPORAL, "mcpt_last_temporal_ms: temporal mode is off (mcpt_temporal_begin)");
+  HIP_OR_RETURN(hipSetDevice(c->device));
+  OK_OR_RETURN(pair_ms(c->tp_timed, c->tp_ev[0], c->tp_ev[1], accumulate_ms));
+  return pair_ms(c->tp_timed && c->tp_copy, c->tp_ev[1], c->tp_ev[2], copy_ms);   // (ping-pong: no copy, 0)
 }
 
 int mcpt_read_denoised(mcpt_ctx* c, float* rgb_out) {

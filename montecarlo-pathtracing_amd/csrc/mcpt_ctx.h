@@ -193,6 +193,21 @@ struct mcpt_ctx {
   bool emap_plane_valid = false;
   // mcpt_error_map_record's partial records (as d_conv; the plane's lifetime)
   unsigned long long* d_emap_rec = nullptr;
+  // temporal reprojection (mcpt_temporal.hip): per pixel of a full frame the
+  // integrated {rgb, variance} (16 B), the history length (4 B) and the guides of the frame the history
+  // was made with (32 B), the first two twice (the kernel reads one set and writes the other), the
+  // guides twice in the ping-pong form and once in the copy form: 104 / 72 B per pixel.  Allocated by
+  // mcpt_temporal_begin, freed by mcpt_temporal_end, the next mcpt_set_target* and mcpt_destroy.
+  bool tp_on = false;
+  bool tp_copy = false;             // the history's guides are copied behind the kernel (else ping-pong)
+  float4* d_tp_c[2] = {nullptr, nullptr};
+  int* d_tp_len[2] = {nullptr, nullptr};
+  float4* d_tp_g[2] = {nullptr, nullptr};   // [1] null in the copy form
+  int tp_cur = 0;                   // which set holds the history
+  long long tp_frames = 0;          // accumulates since the history was last empty (0: it is empty)
+  unsigned long long* d_tp_rec = nullptr;   // the accumulate kernel's partial records (as d_conv)
+  bool tp_timed = false;
+  hipEvent_t tp_ev[3] = {};         // before the kernel, behind it, behind the guides' copy
   int next_lane = 0;               // the lane of the next sub-launch
   int prev_lane = -1;               // the lane of the previous sub-launch if it was a lane launch, else -1
 };
@@ -232,6 +247,16 @@ inline void free_count_plane(mcpt_ctx* c) {
   c->load_index.clear();
   c->plane_valid = false;
   c->emap_plane_valid = false;
+}
+
+inline void free_temporal(mcpt_ctx* c) {
+  for (int k = 0; k < 2; ++k) {
+    (void)hipFree(c->d_tp_c[k]); (void)hipFree(c->d_tp_len[k]); (void)hipFree(c->d_tp_g[k]);
+    c->d_tp_c[k] = nullptr; c->d_tp_len[k] = nullptr; c->d_tp_g[k] = nullptr;
+  }
+  (void)hipFree(c->d_tp_rec);
+  c->d_tp_rec = nullptr;
+  c->tp_on = false; c->tp_cur = 0; c->tp_frames = 0; c->tp_timed = false;
 }
 
 // the accumulator changes: what a gather stored about its pixels (the count plane, the gathered

@@ -31,6 +31,7 @@
 #include <unistd.h>
 
 #include "../../include/mcpt.h"
+#include "mcpt_mat4.h"
 
 // mcpt_capi.hip: an error return without a detail (drops the thread's unread detail)
 int mcpt_err_bare(int status);
@@ -352,6 +353,11 @@ int mcpt_transfo_rotate(int axis, float degrees, float* out16) {
 int mcpt_mat4_mul(const float* a16, const float* b16, float* out16) {
   if (!a16 || !b16 || !out16) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
   mcpt::host::mat4_mul(a16, b16, out16);
+  return MCPT_OK;
+}
+
+int mcpt_mat4_inverse(const float* a16, float* out16) {
+  if (!a16 || !out16 || !mcpt::host::mat4_inverse(a16, out16)) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
   return MCPT_OK;
 }
 

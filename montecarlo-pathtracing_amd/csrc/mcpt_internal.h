@@ -329,6 +329,37 @@ hipError_t mcpt_launch_resolve4(const mcpt::CountSource& src, const float* accum
 hipError_t mcpt_launch_variance_init(const mcpt::CountSource* counts, const float* accum, float4* out,
                                      const float4* guide, const float2* emap, int W, int H, int pass_count,
                                      hipStream_t stream);
+// temporal reprojection (mcpt_temporal.hip) over a full W x H frame in row order.
+// The history per pixel: hc {rgb, variance of the mean}, hl its length, hg the two guide words of the
+// frame it was made with; read from *_in, written to *_out (other buffers).  hg_out null: the caller
+// copies the current guides into the history behind the kernel.
+namespace mcpt {
+struct TemporalParams {
+  const float* accum;           // the current frame's sums, nb passes each
+  const float2* emap;           // its error map {se, r}
+  const float4* guide;          // its guides, 2 per pixel
+  const float4* hc_in;
+  const int* hl_in;
+  const float4* hg_in;
+  float4* hc_out;
+  int* hl_out;
+  float4* hg_out;
+  unsigned long long* rec;      // kStatsRecWords: [0] n_history [1] n_miss [2] n_offscreen [3] n_rejected
+                                // [4] sum_len [5] max_len per slot
+  int W, H;
+  float nb;                     // (float)pass_count
+  int max_history;
+  float plane_tol;
+  int empty;                    // the history holds nothing: every pixel is new
+  float M[16];                  // P·V of the camera the history was made with, column-major
+};
+}  // namespace mcpt
+// one accumulate; adds into p.rec, which the caller has zeroed
+hipError_t mcpt_launch_temporal(const mcpt::TemporalParams& p, hipStream_t stream);
+// the variance filter's first input from the temporal image: out = {hc.rgb, 3x3 prefilter of hc.w
+// among the centre's key} (mcpt_launch_variance_init's taps and weights)
+hipError_t mcpt_launch_temporal_init(const float4* hc, float4* out, const float4* guide, int W, int H,
+                                     hipStream_t stream);
 // the multi-process counted gather's ends: 16-byte records {r, g, b bits, int32 count} per pixel.
 // pack: n_rows local rows of src.W pixels in order into `out`.  load: frame row y of a W x H frame
 // from packed row src_row[y] of `src`, the sums to accum, the counts to plane (16-byte aligned both).

@@ -29,6 +29,7 @@ __all__ = [
     "TRAVERSAL_AUTO", "TRAVERSAL_LANE", "TRAVERSAL_WAVE", "TRAVERSAL_STREAM",
     "Transfo", "average", "write_pfm", "write_png", "material", "light", "Hit", "HIT_DTYPE",
     "Convergence", "DENOISE_K_COLOR", "ERROR_MU_FLOOR", "DENOISE_K_VARIANCE",
+    "TemporalRecord", "TEMPORAL_MAX_HISTORY", "TEMPORAL_PLANE_TOL", "mat4_inverse",
 ]
 
 MONTECARLO, MAT, MAT_TR = 0, 1, 2
@@ -60,6 +61,12 @@ ERROR_MU_FLOOR = 0.01
 NO_GUIDES = -7     # MCPT_ERR_NO_GUIDES
 NO_STATS = -8      # MCPT_ERR_NO_STATS
 NO_ADAPTIVE = -9   # MCPT_ERR_NO_ADAPTIVE
+NO_TEMPORAL = -10  # MCPT_ERR_NO_TEMPORAL
+# temporal reprojection's defaults (the sweep of DESIGN.md §3.10: tools/temporal_bench.py): the longest
+# history a pixel blends, and the tangent-plane distance, relative to the pixel's distance from the
+# camera, within which a history tap shows the same surface point
+TEMPORAL_MAX_HISTORY = 8
+TEMPORAL_PLANE_TOL = 0.01
 
 
 class MCPTError(RuntimeError):
@@ -93,6 +100,13 @@ class AdaptiveRun(ctypes.Structure):
 
 
 ADAPTIVE_RUN_MAX_ROUNDS = 256   # MCPT_ADAPTIVE_RUN_MAX_ROUNDS
+
+
+class TemporalRecord(ctypes.Structure):
+    """mcpt_temporal_t (include/mcpt.h): the frame record of a temporal accumulate."""
+    _fields_ = [("n_px", ctypes.c_longlong), ("n_history", ctypes.c_longlong), ("n_new", ctypes.c_longlong),
+                ("n_miss", ctypes.c_longlong), ("n_offscreen", ctypes.c_longlong), ("n_rejected", ctypes.c_longlong),
+                ("sum_len", ctypes.c_longlong), ("max_len", ctypes.c_int), ("frames", ctypes.c_longlong)]
 
 
 class AdaptiveCheckpoint(ctypes.Structure):
@@ -238,6 +252,14 @@ def _declare(L: ctypes.CDLL) -> None:
         "mcpt_denoise_variance": (i, [_vp, i, f, f]),
         "mcpt_denoise_resolved_variance": (i, [_vp, i, f, f]),
         "mcpt_read_denoised_variance": (i, [_vp, fp]),
+        "mcpt_temporal_begin": (i, [_vp]),
+        "mcpt_temporal_end": (i, [_vp]),
+        "mcpt_temporal_accumulate": (i, [_vp, fp, i, f, ctypes.POINTER(TemporalRecord)]),
+        "mcpt_denoise_temporal": (i, [_vp, i, f, f]),
+        "mcpt_read_temporal": (i, [_vp, fp, ip]),
+        "mcpt_temporal_info": (i, [_vp, ip, ip, ctypes.POINTER(ctypes.c_longlong)]),
+        "mcpt_last_temporal_ms": (i, [_vp, fp, fp]),
+        "mcpt_mat4_inverse": (i, [fp, fp]),
         "mcpt_gather_rows_counted": (i, [_vp, ctypes.POINTER(_vp), i]),
         "mcpt_pass_count": (i, [_vp, ip]),
         "mcpt_pack_counted_device": (i, [_vp, _vp, ctypes.c_size_t]),
@@ -489,6 +511,15 @@ class Transfo:
             _check(lib().mcpt_mat4_mul(_fp(acc), _fp(b), _fp(out)), "mcpt_mat4_mul")
             acc = out
         return acc
+
+
+def mat4_inverse(m) -> np.ndarray:
+    """mcpt_mat4_inverse: the inverse of 16 f32 (computed in double, rounded once); MCPTError for a
+    singular matrix.  mat4_inverse(invPV) is the P·V Renderer.temporal_accumulate takes."""
+    a = _f32(m, 16)
+    out = np.zeros(16, np.float32)
+    _check(lib().mcpt_mat4_inverse(_fp(a), _fp(out)), "mcpt_mat4_inverse")
+    return out
 
 
 # ---- output step (SURVEY §8f row 1)
@@ -1086,6 +1117,85 @@ class Renderer:
             rec = select()     # (fewer than two batches: MCPT_ERR_NO_STATS)
         rec["rendered"] = done
         return rec
+
+    # ---- temporal reprojection across camera moves (mcpt.h)
+    def temporal_begin(self) -> None:
+        """mcpt_temporal_begin: temporal mode on, the history allocated and empty (asynchronous)."""
+        _check(lib().mcpt_temporal_begin(self._h), "mcpt_temporal_begin")
+
+    def temporal_end(self) -> None:
+        """mcpt_temporal_end: temporal mode off, the history freed."""
+        _check(lib().mcpt_temporal_end(self._h), "mcpt_temporal_end")
+
+    def temporal_info(self) -> dict:
+        """{"on", "history_valid", "frames"} of the temporal mode."""
+        on, v, n = ctypes.c_int(), ctypes.c_int(), ctypes.c_longlong()
+        _check(lib().mcpt_temporal_info(self._h, ctypes.byref(on), ctypes.byref(v), ctypes.byref(n)), "mcpt_temporal_info")
+        return {"on": bool(on.value), "history_valid": bool(v.value), "frames": n.value}
+
+    def temporal_accumulate(self, prevPV=None, max_history: int = TEMPORAL_MAX_HISTORY,
+                            plane_tol: float = TEMPORAL_PLANE_TOL) -> dict:
+        """mcpt_temporal_accumulate: reproject the history through prevPV (the P·V of the camera it was
+        made with, 16 f32 column-major; None only while the history is empty) and blend the current
+        frame in; the record {n_px, n_history, n_new, n_miss, n_offscreen, n_rejected, sum_len, max_len,
+        frames}.  Needs a convergence() and render_guides() of the current frame.  Synchronizes."""
+        rec = TemporalRecord()
+        m = None if prevPV is None else _f32(prevPV, 16)
+        _check(lib().mcpt_temporal_accumulate(self._h, None if m is None else _fp(m), int(max_history), float(plane_tol),
+                                              ctypes.byref(rec)), "mcpt_temporal_accumulate")
+        return {k: getattr(rec, k) for k, _ in TemporalRecord._fields_}
+
+    def read_temporal(self) -> Tuple[np.ndarray, np.ndarray]:
+        """mcpt_read_temporal: ((local rows, W, 4) f32 {rgb, variance of the mean}, (local rows, W) i32
+        history lengths) of the history."""
+        c = np.zeros((self.n_local_rows, self.W, 4), np.float32)
+        n = np.zeros((self.n_local_rows, self.W), np.int32)
+        _check(lib().mcpt_read_temporal(self._h, _fp(c), _ip(n)), "mcpt_read_temporal")
+        return c, n
+
+    def denoise_temporal(self, iterations: int = 5, k_color: float = DENOISE_K_VARIANCE,
+                         sigma_plane: float = DENOISE_SIGMA_PLANE) -> np.ndarray:
+        """mcpt_denoise_temporal + mcpt_read_denoised: the variance filter from the temporal image;
+        read_denoised_variance() returns the filtered variance."""
+        _check(lib().mcpt_denoise_temporal(self._h, int(iterations), float(k_color), float(sigma_plane)),
+               "mcpt_denoise_temporal")
+        out = np.zeros((self.n_local_rows, self.W, 3), np.float32)
+        _check(lib().mcpt_read_denoised(self._h, _fp(out)), "mcpt_read_denoised")
+        return out
+
+    def last_temporal_ms(self) -> Tuple[float, float]:
+        """(accumulate kernel ms, guides copy ms) of the last temporal_accumulate."""
+        a, b = ctypes.c_float(), ctypes.c_float()
+        _check(lib().mcpt_last_temporal_ms(self._h, ctypes.byref(a), ctypes.byref(b)), "mcpt_last_temporal_ms")
+        return a.value, b.value
+
+    def render_frame_temporal(self, invPV, invV, prevPV, first_pass: int, spp: int = 4, batches: int = 2,
+                              date: float = 0.0, bounces: int = 3, refract_ind: float = 1.0,
+                              variant: int = MONTECARLO, max_history: int = TEMPORAL_MAX_HISTORY,
+                              plane_tol: float = TEMPORAL_PLANE_TOL, iterations: int = 5,
+                              k_color: float = DENOISE_K_VARIANCE, sigma_plane: float = DENOISE_SIGMA_PLANE,
+                              threshold: float = 0.05, mu_floor: float = ERROR_MU_FLOOR) -> Tuple[np.ndarray, dict]:
+        """One frame of a moving-camera render: clear the accumulator, `spp` passes from `first_pass` on
+        in `batches` render calls (two or more: the error map needs them) under a fresh statistics
+        window, the error map, the guides of this camera, temporal_accumulate(prevPV) and
+        denoise_temporal.  Begins the temporal mode unless it is on.  Returns (the filtered H x W x 3
+        image, the accumulate's record); the next frame's first_pass is first_pass + spp and its
+        prevPV is mat4_inverse(invPV) of this one."""
+        if batches < 2 or spp < batches:
+            raise MCPTError("render_frame_temporal: two batches or more, one pass or more each")
+        if not self.temporal_info()["on"]:
+            self.temporal_begin()
+        self.clear_accum()
+        self.stats_begin()
+        done = 0
+        for b in range(batches):
+            n = spp // batches + (1 if b < spp % batches else 0)
+            self.render(invPV, invV, first_pass + done, n, date, bounces, refract_ind, variant)
+            done += n
+        self.convergence(threshold, mu_floor)
+        self.render_guides(invPV, invV)
+        rec = self.temporal_accumulate(prevPV, max_history, plane_tol)
+        return self.denoise_temporal(iterations, k_color, sigma_plane), rec
 
     # ---- frames with per-pixel sample counts: filter, checkpoint, gather (mcpt.h; DESIGN.md §3.9)
     def denoise_resolved(self, iterations: int = 5, sigma_color: float = DENOISE_SIGMA_COLOR,
