@@ -3,35 +3,66 @@
 // error map's record).  The gathers that fill a frame's planes are mcpt_capi_gather.hip's.
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
 #include <cstring>
+#include <initializer_list>
 
 #include "mcpt_ctx.h"
 
 namespace plan = mcpt::plan;
 
+static bool positive_finite(std::initializer_list<float> values) {
+  for (float v : values)
+    if (!(v > 0.0f) || !std::isfinite(v)) return false;
+  return true;
+}
+// a refusal whose detail names the entry point the caller called: "<who>: <why>"
+static int refuse(int status, const char* who, const char* why) {
+  char what[256];
+  std::snprintf(what, sizeof(what), "%s: %s", who, why);
+  return set_err(status, what);
+}
+
 // One batch of the noise statistics: "the accumulator now holds n more passes than
 // at the previous batch", enqueued on the context's stream (which is ordered after every queued
-// render's combine), no host wait.
-hipError_t stats_batch(mcpt_ctx* c, int n) {
-  hipError_t e = ensure_timing_events(c->stats_ev, 2);
-  if (e == hipSuccess) e = hipEventRecord(c->stats_ev[0], c->stream);
+// render's combine), no host wait.  d_count: a queued adaptive run's batch (§3.9.3), which changes
+// nothing once the list's length on the device is 0; timed false: it records no events.
+hipError_t stats_batch(mcpt_ctx* c, int n, const int* d_count, bool timed) {
+  const long long n_px = (long long)c->n_local_rows * c->W;
+  hipError_t e = timed ? ensure_timing_events(c->stats_ev, 2) : hipSuccess;
+  if (e == hipSuccess && timed) e = hipEventRecord(c->stats_ev[0], c->stream);
   if (e == hipSuccess)
-    e = mcpt_launch_stats_update(c->d_accum, c->d_stats, (long long)c->n_local_rows * c->W, n, c->stream);
-  if (e == hipSuccess) e = hipEventRecord(c->stats_ev[1], c->stream);
+    e = d_count ? mcpt_launch_stats_update_counted(c->d_accum, c->d_stats, n_px, n, d_count, c->stream)
+                : mcpt_launch_stats_update(c->d_accum, c->d_stats, n_px, n, c->stream);
+  if (e == hipSuccess && timed) e = hipEventRecord(c->stats_ev[1], c->stream);
   if (e != hipSuccess) return e;
   c->stats_passes += n;
   c->stats_batches += 1;
-  c->stats_update_timed = true;
+  if (timed) c->stats_update_timed = true;
   return hipSuccess;
 }
 
-// the frame's record from the kStatsRecSlots partial records of the error / select kernels: the
-// words add (max for word 2, max_r's bits)
-static void reduce_stats_records(const unsigned long long* part, int n_words, unsigned long long* h) {
+// the frame's record from the kStatsRecSlots partial records of a reducing kernel: the words add,
+// but word max_word is a maximum of bit patterns (max_r's bits, the longest history)
+static void reduce_stats_records(const unsigned long long* part, int n_words, int max_word, unsigned long long* h) {
   for (int s = 0; s < mcpt::kStatsRecSlots; ++s) {
     const unsigned long long* q = part + (size_t)s * mcpt::kStatsRecStride;
-    for (int w = 0; w < n_words; ++w) h[w] = w == 2 ? std::max(h[2], q[2] & 0xffffffffull) : h[w] + q[w];
+    for (int w = 0; w < n_words; ++w) h[w] = w == max_word ? std::max(h[w], q[w] & 0xffffffffull) : h[w] + q[w];
   }
+}
+// a kernel's partial records back and reduced into h (zeroed by the caller), with them a second
+// kernel's into hf and a list length into *len (null: none): every copy is issued, then one wait
+static int read_stats_records(mcpt_ctx* c, int n_words, int max_word, const unsigned long long* d_rec,
+                              unsigned long long* h, const unsigned long long* d_rec_f = nullptr,
+                              unsigned long long* hf = nullptr, const int* d_len = nullptr, int* len = nullptr) {
+  unsigned long long part[mcpt::kStatsRecWords] = {}, part_f[mcpt::kStatsRecWords] = {};
+  HIP_OR_RETURN(hipMemcpyAsync(part, d_rec, sizeof(part), hipMemcpyDeviceToHost, c->stream));
+  if (d_rec_f) HIP_OR_RETURN(hipMemcpyAsync(part_f, d_rec_f, sizeof(part_f), hipMemcpyDeviceToHost, c->stream));
+  if (d_len) HIP_OR_RETURN(hipMemcpyAsync(len, d_len, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIP_OR_RETURN(hipStreamSynchronize(c->stream));
+  reduce_stats_records(part, n_words, max_word, h);
+  if (d_rec_f) reduce_stats_records(part_f, n_words, max_word, hf);
+  return MCPT_OK;
 }
 // ... into the leading fields mcpt_convergence_t and mcpt_adaptive_t share
 template <class Rec>
@@ -114,38 +145,50 @@ int mcpt_read_guides(mcpt_ctx* c, float* guide8, float* albedo4) {
   return MCPT_OK;
 }
 
-// the filter's iterations from the first input in d_dn[0] (defined behind denoise_run)
-static int atrous_iterations(mcpt_ctx* c, int iterations, float sigma_color, float sigma_plane, bool guided,
-                             bool variance, const float2* emap, bool naive, bool timed);
+// Which filter a run is: the six public forms by name, `who` for a refusal's detail.  guided false:
+// sigma_color is the global width; guided true: it is k_color, the width per pixel k_color * 2^-s * se
+// from the error map; resolved: the input is accum / (float)count with every pixel's own count
+//  in place of accum / pass_count; variance: guided's preconditions and map, the
+// first input carries the prefiltered se^2 in .w and every iteration filters it along (DESIGN.md
+// §3.8); timed false: no events (a queued adaptive run's selects but its last)
+struct FilterForm {
+  const char* who;
+  bool guided, resolved, variance;
+  bool timed = true;
+};
+constexpr FilterForm kPlain = {"mcpt_denoise", false, false, false};
+constexpr FilterForm kGuided = {"mcpt_denoise_guided", true, false, false};
+constexpr FilterForm kResolved = {"mcpt_denoise_resolved", false, true, false};
+constexpr FilterForm kResolvedGuided = {"mcpt_denoise_resolved_guided", true, true, false};
+constexpr FilterForm kVariance = {"mcpt_denoise_variance", true, false, true};
+constexpr FilterForm kResolvedVariance = {"mcpt_denoise_resolved_variance", true, true, true};
 
-// mcpt_denoise (guided false: sigma_color is the global width) and mcpt_denoise_guided (guided
-// true: sigma_color is k_color, the width per pixel k_color * 2^-s * se from the error map);
-// resolved: the mcpt_denoise_resolved* forms, whose input is accum / (float)count with every
-// pixel's own count in place of accum / pass_count; variance: the
-// mcpt_denoise*_variance forms (guided's preconditions and map; sigma_color is k_color, the first
-// input carries the prefiltered se^2 in .w and every iteration filters it along);
-// timed false: no events (a queued adaptive run's selects but its last)
-static int denoise_run(mcpt_ctx* c, int iterations, float sigma_color, float sigma_plane, bool guided,
-                       bool resolved = false, bool variance = false, bool timed = true) {
-  if (!c || iterations < 0 || iterations > 8) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_denoise: iterations not in 0..8");
-  if (!(sigma_color > 0.0f) || !(sigma_plane > 0.0f) || !std::isfinite(sigma_color) || !std::isfinite(sigma_plane))
-    return set_err(MCPT_ERR_INVALID_ARG, "mcpt_denoise: sigmas must be positive and finite");
+// the filter's iterations from the first input in d_dn[0] (defined behind denoise_run)
+static int atrous_iterations(mcpt_ctx* c, int iterations, float sigma_color, float sigma_plane, const FilterForm& form,
+                             const float2* emap, bool naive);
+
+static int denoise_run(mcpt_ctx* c, int iterations, float sigma_color, float sigma_plane, const FilterForm& form) {
+  const bool guided = form.guided, resolved = form.resolved, variance = form.variance, timed = form.timed;
+  const char* who = form.who;
+  if (!c || iterations < 0 || iterations > 8) return refuse(MCPT_ERR_INVALID_ARG, who, "iterations not in 0..8");
+  if (!positive_finite({sigma_color, sigma_plane}))
+    return refuse(MCPT_ERR_INVALID_ARG, who, "sigmas must be positive and finite");
   if (!c->has_target) return set_err(MCPT_ERR_NO_TARGET, "no render target");
   if (resolved && !has_pixel_counts(c))
-    return set_err(MCPT_ERR_NO_ADAPTIVE, "mcpt_denoise_resolved: no per-pixel sample counts (adaptive mode off, no counted gather)");
+    return refuse(MCPT_ERR_NO_ADAPTIVE, who, "no per-pixel sample counts (adaptive mode off, no counted gather)");
   if (!plan::is_full_frame(c->rows, c->H))
-    return set_err(MCPT_ERR_INVALID_ARG, "mcpt_denoise: needs a full-frame target (gather the shards first)");
-  if (c->pass_count <= 0) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_denoise: the accumulator holds no passes");
+    return refuse(MCPT_ERR_INVALID_ARG, who, "needs a full-frame target (gather the shards first)");
+  if (c->pass_count <= 0) return refuse(MCPT_ERR_INVALID_ARG, who, "the accumulator holds no passes");
   if (!resolved && c->ad_on && c->ad_n_list < c->ad_n_blocks)
-    return set_err(MCPT_ERR_INVALID_ARG, "mcpt_denoise: adaptive mode has retired blocks (per-pixel sample counts)");
-  if (!c->guides_valid) return set_err(MCPT_ERR_NO_GUIDES, "mcpt_denoise: no guides rendered for this target and scene");
+    return refuse(MCPT_ERR_INVALID_ARG, who, "adaptive mode has retired blocks (per-pixel sample counts)");
+  if (!c->guides_valid) return refuse(MCPT_ERR_NO_GUIDES, who, "no guides rendered for this target and scene");
   // the guided forms' map: the one the context holds (the gathered plane, else the own window's);
   // a frame with gathered counts holds no window of its pixels, so its own map never serves the
   // resolved form of it
   const float2* emap = held_error_map(c);
   const int source = error_map_source(c);
   if (guided && (source == 0 || (resolved && c->plane_valid && source != 2)))
-    return set_err(MCPT_ERR_NO_STATS, "mcpt_denoise_guided: no error map (mcpt_convergence) of the current statistics");
+    return refuse(MCPT_ERR_NO_STATS, who, "no error map (mcpt_convergence) of the current statistics");
   HIP_OR_RETURN(hipSetDevice(c->device));
   HIP_OR_RETURN(ensure_denoise_buffers(c));
   HIP_OR_RETURN(ensure_timing_events(c->dn_ev, 10));
@@ -164,12 +207,13 @@ static int denoise_run(mcpt_ctx* c, int iterations, float sigma_color, float sig
   else
     HIP_OR_RETURN(mcpt_launch_average4(c->d_accum, c->d_dn[0], n, c->pass_count, c->stream));
   if (timed) HIP_OR_RETURN(hipEventRecord(c->dn_ev[0], c->stream));
-  return atrous_iterations(c, iterations, sigma_color, sigma_plane, guided, variance, emap, naive, timed);
+  return atrous_iterations(c, iterations, sigma_color, sigma_plane, form, emap, naive);
 }
 
-// (denoise_run, mcpt_denoise_temporal)
-static int atrous_iterations(mcpt_ctx* c, int iterations, float sigma_color, float sigma_plane, bool guided,
-                             bool variance, const float2* emap, bool naive, bool timed) {
+// (denoise_run, mcpt_denoise_temporal; of the form: guided, variance, timed)
+static int atrous_iterations(mcpt_ctx* c, int iterations, float sigma_color, float sigma_plane, const FilterForm& form,
+                             const float2* emap, bool naive) {
+  const bool guided = form.guided, variance = form.variance, timed = form.timed;
   int lds_mask = 0;
   for (int s = 0; s < iterations; ++s) {
     const int step = 1 << s;
@@ -195,27 +239,27 @@ static int atrous_iterations(mcpt_ctx* c, int iterations, float sigma_color, flo
 }
 
 int mcpt_denoise(mcpt_ctx* c, int iterations, float sigma_color, float sigma_plane) {
-  return denoise_run(c, iterations, sigma_color, sigma_plane, false);
+  return denoise_run(c, iterations, sigma_color, sigma_plane, kPlain);
 }
 
 int mcpt_denoise_guided(mcpt_ctx* c, int iterations, float k_color, float sigma_plane) {
-  return denoise_run(c, iterations, k_color, sigma_plane, true);
+  return denoise_run(c, iterations, k_color, sigma_plane, kGuided);
 }
 
 int mcpt_denoise_resolved(mcpt_ctx* c, int iterations, float sigma_color, float sigma_plane) {
-  return denoise_run(c, iterations, sigma_color, sigma_plane, false, true);
+  return denoise_run(c, iterations, sigma_color, sigma_plane, kResolved);
 }
 
 int mcpt_denoise_resolved_guided(mcpt_ctx* c, int iterations, float k_color, float sigma_plane) {
-  return denoise_run(c, iterations, k_color, sigma_plane, true, true);
+  return denoise_run(c, iterations, k_color, sigma_plane, kResolvedGuided);
 }
 
 int mcpt_denoise_variance(mcpt_ctx* c, int iterations, float k_color, float sigma_plane) {
-  return denoise_run(c, iterations, k_color, sigma_plane, true, false, true);
+  return denoise_run(c, iterations, k_color, sigma_plane, kVariance);
 }
 
 int mcpt_denoise_resolved_variance(mcpt_ctx* c, int iterations, float k_color, float sigma_plane) {
-  return denoise_run(c, iterations, k_color, sigma_plane, true, true, true);
+  return denoise_run(c, iterations, k_color, sigma_plane, kResolvedVariance);
 }
 
 // ---- noise statistics and the convergence metric (mcpt_stats.hip)
@@ -275,7 +319,7 @@ int mcpt_stats_info(mcpt_ctx* c, int* on, long long* passes, int* batches) {
 
 int mcpt_convergence(mcpt_ctx* c, float threshold, float mu_floor, mcpt_convergence_t* out) {
   if (!c || !out) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
-  if (!(threshold > 0.0f) || !(mu_floor > 0.0f) || !std::isfinite(threshold) || !std::isfinite(mu_floor))
+  if (!positive_finite({threshold, mu_floor}))
     return set_err(MCPT_ERR_INVALID_ARG, "mcpt_convergence: threshold and mu_floor must be positive and finite");
   if (!c->stats_on) return set_err(MCPT_ERR_NO_STATS, "mcpt_convergence: statistics are off (mcpt_stats_begin)");
   if (c->stats_batches < 2) return set_err(MCPT_ERR_NO_STATS, "mcpt_convergence: needs two batches or more");
@@ -288,11 +332,8 @@ int mcpt_convergence(mcpt_ctx* c, float threshold, float mu_floor, mcpt_converge
   HIP_OR_RETURN(hipEventRecord(c->stats_ev[3], c->stream));
   c->stats_error_timed = true;
   c->emap_valid = true;
-  unsigned long long part[mcpt::kStatsRecWords] = {};
-  HIP_OR_RETURN(hipMemcpyAsync(part, c->d_conv, sizeof(part), hipMemcpyDeviceToHost, c->stream));
-  HIP_OR_RETURN(hipStreamSynchronize(c->stream));
   unsigned long long h[3] = {0, 0, 0};
-  reduce_stats_records(part, 3, h);
+  OK_OR_RETURN(read_stats_records(c, 3, 2, c->d_conv, h));
   fill_frame_record(c, h, out);
   return MCPT_OK;
 }
@@ -366,108 +407,127 @@ int mcpt_adaptive_info(mcpt_ctx* c, int* on, long long* n_active, long long* n_b
   return MCPT_OK;
 }
 
-int mcpt_adaptive_select(mcpt_ctx* c, float threshold, float mu_floor, mcpt_adaptive_t* out) {
-  if (!c || !out) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
-  if (!c->ad_on) return set_err(MCPT_ERR_NO_ADAPTIVE, "mcpt_adaptive_select: adaptive mode is off (mcpt_adaptive_begin)");
-  if (!(threshold > 0.0f) || !(mu_floor > 0.0f) || !std::isfinite(threshold) || !std::isfinite(mu_floor))
-    return set_err(MCPT_ERR_INVALID_ARG, "mcpt_adaptive_select: threshold and mu_floor must be positive and finite");
-  if (!c->stats_on) return set_err(MCPT_ERR_NO_STATS, "mcpt_adaptive_select: statistics are off (mcpt_stats_begin)");
-  if (c->stats_batches < 2) return set_err(MCPT_ERR_NO_STATS, "mcpt_adaptive_select: needs two batches or more");
-  HIP_OR_RETURN(hipSetDevice(c->device));
-  HIP_OR_RETURN(ensure_timing_events(c->ad_ev, 2));
-  const mcpt::AdaptiveTarget t = adaptive_target(c);
-  int* d_count = c->d_ad_list + c->ad_n_blocks;
-  HIP_OR_RETURN(hipEventRecord(c->ad_ev[0], c->stream));
-  HIP_OR_RETURN(mcpt_launch_adaptive_select(t, c->d_stats, c->d_emap, c->stats_passes, c->stats_batches, mu_floor,
-                                            threshold, c->ad_min_passes, true, c->d_conv, c->stream));
-  HIP_OR_RETURN(mcpt_launch_adaptive_compact(t, c->d_ad_list, d_count, c->stream));
-  HIP_OR_RETURN(hipEventRecord(c->ad_ev[1], c->stream));
-  c->ad_select_timed = true;
-  c->ad_select_split = false;
-  c->emap_valid = true;
-  unsigned long long part[mcpt::kStatsRecWords] = {};
-  int n_list = 0;
-  HIP_OR_RETURN(hipMemcpyAsync(part, c->d_conv, sizeof(part), hipMemcpyDeviceToHost, c->stream));
-  HIP_OR_RETURN(hipMemcpyAsync(&n_list, d_count, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIP_OR_RETURN(hipStreamSynchronize(c->stream));
-  unsigned long long h[5] = {0, 0, 0, 0, 0};
-  reduce_stats_records(part, 5, h);
-  if (n_list < 0 || n_list > c->ad_n_blocks || (unsigned long long)n_list != h[4])
-    return set_err(MCPT_ERR_HIP, "mcpt_adaptive_select: the active list and the block flags disagree");
-  c->ad_n_list = n_list;
-  fill_frame_record(c, h, out);
-  out->n_active_blocks = n_list;
-  out->n_blocks = c->ad_n_blocks;
-  out->samples = (long long)h[3];
+// ---- one select step behind mcpt_adaptive_select,
+// mcpt_adaptive_select_filtered and every select of a queued run: its rule, its checks, its enqueue
+// half and its host half.
+// the filtered rule's own arguments; SelectRule::f null: mcpt_adaptive_select's rule on the raw error
+struct RunFilter { float raw_cap; int iterations; float k_color, sigma_plane; };
+struct SelectRule { float threshold, mu_floor; const RunFilter* f; };
+// where a select's results go on the device: the rule kernel's partial records, the filtered rule's
+// step C's (null without a filter) and a slot that receives a copy of the list's length (null: none)
+struct SelectDest { unsigned long long *rec, *rec_f; int* len; };
+
+// The rule's preconditions, behind the caller's own MCPT_ERR_NO_ADAPTIVE.  single: one select now
+// (mcpt_adaptive_select*), which needs passes and two batches on entry; a queued run's schedule
+// places its selects behind both.
+static int check_select_rule(const mcpt_ctx* c, const SelectRule& r, bool single, const char* who) {
+  const RunFilter* f = r.f;
+  if (!positive_finite({r.threshold, r.mu_floor, f ? f->raw_cap : 1.0f, f ? f->k_color : 1.0f, f ? f->sigma_plane : 1.0f}))
+    return refuse(MCPT_ERR_INVALID_ARG, who,
+                  !single ? "threshold, mu_floor and the filter's widths must be positive and finite"
+                  : f     ? "threshold, raw_cap, mu_floor, k_color and sigma_plane must be positive and finite"
+                          : "threshold and mu_floor must be positive and finite");
+  if (f) {
+    if (f->iterations < 0 || f->iterations > 8) return refuse(MCPT_ERR_INVALID_ARG, who, "iterations not in 0..8");
+    if (!plan::is_full_frame(c->rows, c->H))
+      return refuse(MCPT_ERR_INVALID_ARG, who, "needs a full-frame target (a shard is filtered after its gather)");
+    // (the filter would read a gathered frame's counts and map, the rule this window's)
+    if (c->plane_valid || c->emap_plane_valid)
+      return refuse(MCPT_ERR_INVALID_ARG, who, "the context holds a gathered frame's counts or error map");
+    if (single && c->pass_count <= 0) return refuse(MCPT_ERR_INVALID_ARG, who, "the accumulator holds no passes");
+  }
+  if (!c->stats_on) return refuse(MCPT_ERR_NO_STATS, who, "statistics are off (mcpt_stats_begin)");
+  if (single && c->stats_batches < 2) return refuse(MCPT_ERR_NO_STATS, who, "needs two batches or more");
+  if (f && !c->guides_valid) return refuse(MCPT_ERR_NO_GUIDES, who, "no guides rendered for this target and scene");
   return MCPT_OK;
 }
 
-// The select on the denoised frame's error.  Step A: select_kernel<false>, the map
-// and the raw record, no flag changes.  Step B: denoise_run's resolved variance form on that map.
-// Step C: filtered_select_kernel on the filter's result, then the scan.  Every precondition is
-// checked before step A, so a refusal leaves the flags, the map and the result buffers alone.
+// the events of a select (and of the round before it), with a filter the filter's events and buffers
+static int ensure_select(mcpt_ctx* c, const RunFilter* f) {
+  HIP_OR_RETURN(ensure_timing_events(c->ad_ev, 6));
+  if (f) {
+    HIP_OR_RETURN(ensure_timing_events(c->dn_ev, 10));
+    HIP_OR_RETURN(ensure_denoise_buffers(c));
+  }
+  return MCPT_OK;
+}
+
+// The enqueue half, no host wait.  The raw rule: select_kernel<true> (the map, the record, the flags),
+// then the scan.  The filtered rule: step A select_kernel<false>, the map and the raw
+// record, no flag changes; step B denoise_run's resolved variance form on that map; step C
+// filtered_select_kernel on the filter's result, then the scan.  timed: events [0, 1] around the raw
+// rule and its scan, for the filtered rule [0, 1] around step A and [4, 5] around step C and the scan
+// (mcpt_last_adaptive_ms); every precondition has been checked.
+static int enqueue_select(mcpt_ctx* c, const SelectRule& r, const SelectDest& d, bool timed) {
+  const RunFilter* f = r.f;
+  const mcpt::AdaptiveTarget t = adaptive_target(c);
+  int* d_count = c->d_ad_list + c->ad_n_blocks;
+  if (timed) HIP_OR_RETURN(hipEventRecord(c->ad_ev[0], c->stream));
+  HIP_OR_RETURN(mcpt_launch_adaptive_select(t, c->d_stats, c->d_emap, c->stats_passes, c->stats_batches, r.mu_floor,
+                                            r.threshold, c->ad_min_passes, f == nullptr, d.rec, c->stream));
+  c->emap_valid = true;
+  if (f) {
+    if (timed) HIP_OR_RETURN(hipEventRecord(c->ad_ev[1], c->stream));
+    FilterForm form = kResolvedVariance;
+    form.timed = timed;
+    OK_OR_RETURN(denoise_run(c, f->iterations, f->k_color, f->sigma_plane, form));
+    if (timed) HIP_OR_RETURN(hipEventRecord(c->ad_ev[4], c->stream));
+    HIP_OR_RETURN(mcpt_launch_adaptive_select_filtered(t, c->d_dn[c->dn_result], c->d_emap, r.mu_floor, r.threshold,
+                                                       f->raw_cap, c->ad_min_passes, d.rec_f, c->stream));
+  }
+  HIP_OR_RETURN(mcpt_launch_adaptive_compact(t, c->d_ad_list, d_count, c->stream));
+  if (timed) {
+    HIP_OR_RETURN(hipEventRecord(c->ad_ev[f ? 5 : 1], c->stream));
+    c->ad_select_timed = true;
+    c->ad_select_split = f != nullptr;
+  }
+  if (d.len) HIP_OR_RETURN(hipMemcpyAsync(d.len, d_count, sizeof(int), hipMemcpyDeviceToDevice, c->stream));
+  return MCPT_OK;
+}
+
+// The host half, from one select's reduced records (h; hf: step C's, read when `filtered` is given) and
+// its list length: the length must be the flagged blocks the retiring kernel counted (its word 4);
+// then the context's list length and the caller's record.
+static int finish_select(mcpt_ctx* c, const unsigned long long* h, const unsigned long long* hf, int n_list,
+                         const char* who, mcpt_adaptive_t* raw, mcpt_adaptive_filtered_t* filtered) {
+  if (n_list < 0 || n_list > c->ad_n_blocks || (unsigned long long)n_list != (filtered ? hf : h)[4])
+    return refuse(MCPT_ERR_HIP, who, "the active list and the block flags disagree");
+  c->ad_n_list = n_list;
+  fill_frame_record(c, h, raw);
+  raw->n_active_blocks = n_list;
+  raw->n_blocks = c->ad_n_blocks;
+  raw->samples = (long long)h[3];
+  if (filtered) fill_filtered_record(c, hf, filtered);
+  return MCPT_OK;
+}
+
+// one select now, into d_conv (and d_conv_f), one wait for its records.  Every precondition is checked
+// before the enqueue, so a refusal leaves the flags, the map and the result buffers alone.
+static int select_once(mcpt_ctx* c, const SelectRule& rule, const char* who, mcpt_adaptive_t* raw,
+                       mcpt_adaptive_filtered_t* filtered) {
+  if (!c->ad_on) return refuse(MCPT_ERR_NO_ADAPTIVE, who, "adaptive mode is off (mcpt_adaptive_begin)");
+  OK_OR_RETURN(check_select_rule(c, rule, true, who));
+  HIP_OR_RETURN(hipSetDevice(c->device));
+  OK_OR_RETURN(ensure_select(c, rule.f));
+  if (rule.f && !c->d_conv_f) HIP_OR_RETURN(hipMalloc(&c->d_conv_f, sizeof(unsigned long long) * mcpt::kStatsRecWords));
+  const SelectDest dest = {c->d_conv, rule.f ? c->d_conv_f : nullptr, nullptr};
+  OK_OR_RETURN(enqueue_select(c, rule, dest, true));
+  unsigned long long h[5] = {0, 0, 0, 0, 0}, hf[5] = {0, 0, 0, 0, 0};
+  int n_list = 0;
+  OK_OR_RETURN(read_stats_records(c, 5, 2, dest.rec, h, dest.rec_f, hf, c->d_ad_list + c->ad_n_blocks, &n_list));
+  return finish_select(c, h, hf, n_list, who, raw, filtered);
+}
+
+int mcpt_adaptive_select(mcpt_ctx* c, float threshold, float mu_floor, mcpt_adaptive_t* out) {
+  if (!c || !out) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  return select_once(c, {threshold, mu_floor, nullptr}, "mcpt_adaptive_select", out, nullptr);
+}
+
 int mcpt_adaptive_select_filtered(mcpt_ctx* c, float threshold, float raw_cap, float mu_floor, int iterations,
                                   float k_color, float sigma_plane, mcpt_adaptive_filtered_t* out) {
   if (!c || !out) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
-  if (!c->ad_on)
-    return set_err(MCPT_ERR_NO_ADAPTIVE, "mcpt_adaptive_select_filtered: adaptive mode is off (mcpt_adaptive_begin)");
-  for (float v : {threshold, raw_cap, mu_floor, k_color, sigma_plane})
-    if (!(v > 0.0f) || !std::isfinite(v))
-      return set_err(MCPT_ERR_INVALID_ARG,
-                     "mcpt_adaptive_select_filtered: threshold, raw_cap, mu_floor, k_color and sigma_plane must be "
-                     "positive and finite");
-  if (iterations < 0 || iterations > 8)
-    return set_err(MCPT_ERR_INVALID_ARG, "mcpt_adaptive_select_filtered: iterations not in 0..8");
-  if (!plan::is_full_frame(c->rows, c->H))
-    return set_err(MCPT_ERR_INVALID_ARG, "mcpt_adaptive_select_filtered: needs a full-frame target (a shard is filtered after its gather)");
-  // (the filter would read a gathered frame's counts and map, the rule this window's)
-  if (c->plane_valid || c->emap_plane_valid)
-    return set_err(MCPT_ERR_INVALID_ARG, "mcpt_adaptive_select_filtered: the context holds a gathered frame's counts or error map");
-  if (c->pass_count <= 0)
-    return set_err(MCPT_ERR_INVALID_ARG, "mcpt_adaptive_select_filtered: the accumulator holds no passes");
-  if (!c->stats_on) return set_err(MCPT_ERR_NO_STATS, "mcpt_adaptive_select_filtered: statistics are off (mcpt_stats_begin)");
-  if (c->stats_batches < 2) return set_err(MCPT_ERR_NO_STATS, "mcpt_adaptive_select_filtered: needs two batches or more");
-  if (!c->guides_valid)
-    return set_err(MCPT_ERR_NO_GUIDES, "mcpt_adaptive_select_filtered: no guides rendered for this target and scene");
-  HIP_OR_RETURN(hipSetDevice(c->device));
-  HIP_OR_RETURN(ensure_timing_events(c->ad_ev, 2));
-  HIP_OR_RETURN(ensure_timing_events(c->ad_ev + 4, 2));
-  HIP_OR_RETURN(ensure_timing_events(c->dn_ev, 10));
-  HIP_OR_RETURN(ensure_denoise_buffers(c));
-  if (!c->d_conv_f) HIP_OR_RETURN(hipMalloc(&c->d_conv_f, sizeof(unsigned long long) * mcpt::kStatsRecWords));
-  const mcpt::AdaptiveTarget t = adaptive_target(c);
-  int* d_count = c->d_ad_list + c->ad_n_blocks;
-  HIP_OR_RETURN(hipEventRecord(c->ad_ev[0], c->stream));
-  HIP_OR_RETURN(mcpt_launch_adaptive_select(t, c->d_stats, c->d_emap, c->stats_passes, c->stats_batches, mu_floor,
-                                            threshold, c->ad_min_passes, false, c->d_conv, c->stream));
-  HIP_OR_RETURN(hipEventRecord(c->ad_ev[1], c->stream));
-  c->emap_valid = true;
-  OK_OR_RETURN(denoise_run(c, iterations, k_color, sigma_plane, true, true, true));
-  HIP_OR_RETURN(hipEventRecord(c->ad_ev[4], c->stream));
-  HIP_OR_RETURN(mcpt_launch_adaptive_select_filtered(t, c->d_dn[c->dn_result], c->d_emap, mu_floor, threshold, raw_cap,
-                                                     c->ad_min_passes, c->d_conv_f, c->stream));
-  HIP_OR_RETURN(mcpt_launch_adaptive_compact(t, c->d_ad_list, d_count, c->stream));
-  HIP_OR_RETURN(hipEventRecord(c->ad_ev[5], c->stream));
-  c->ad_select_timed = true;
-  c->ad_select_split = true;
-  unsigned long long part[mcpt::kStatsRecWords] = {}, part_f[mcpt::kStatsRecWords] = {};
-  int n_list = 0;
-  HIP_OR_RETURN(hipMemcpyAsync(part, c->d_conv, sizeof(part), hipMemcpyDeviceToHost, c->stream));
-  HIP_OR_RETURN(hipMemcpyAsync(part_f, c->d_conv_f, sizeof(part_f), hipMemcpyDeviceToHost, c->stream));
-  HIP_OR_RETURN(hipMemcpyAsync(&n_list, d_count, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIP_OR_RETURN(hipStreamSynchronize(c->stream));
-  unsigned long long h[5] = {0, 0, 0, 0, 0}, hf[5] = {0, 0, 0, 0, 0};
-  reduce_stats_records(part, 5, h);
-  reduce_stats_records(part_f, 5, hf);
-  if (n_list < 0 || n_list > c->ad_n_blocks || (unsigned long long)n_list != hf[4])
-    return set_err(MCPT_ERR_HIP, "mcpt_adaptive_select_filtered: the active list and the block flags disagree");
-  c->ad_n_list = n_list;
-  fill_frame_record(c, h, &out->raw);
-  out->raw.n_active_blocks = n_list;
-  out->raw.n_blocks = c->ad_n_blocks;
-  out->raw.samples = (long long)h[3];
-  fill_filtered_record(c, hf, out);
-  return MCPT_OK;
+  const RunFilter f = {raw_cap, iterations, k_color, sigma_plane};
+  return select_once(c, {threshold, mu_floor, &f}, "mcpt_adaptive_select_filtered", &out->raw, out);
 }
 
 int mcpt_read_active_blocks(mcpt_ctx* c, int* ids, int capacity, int* n) {
@@ -491,8 +551,7 @@ int mcpt_read_active_blocks(mcpt_ctx* c, int* ids, int capacity, int* n) {
 static int check_render_adaptive(const mcpt_ctx* c, const float* invPV, const float* invV, int n_passes, int variant,
                                  const char* who) {
   const bool args_ok = invPV && invV && n_passes >= 0 && variant >= 0 && variant <= 2;
-  if (c && args_ok && !c->ad_on)
-    return set_err(MCPT_ERR_NO_ADAPTIVE, "mcpt_render_adaptive: adaptive mode is off (mcpt_adaptive_begin)");
+  if (c && args_ok && !c->ad_on) return refuse(MCPT_ERR_NO_ADAPTIVE, who, "adaptive mode is off (mcpt_adaptive_begin)");
   return check_renderable(c, args_ok, who);
 }
 // the round's launch parameters except its pass range; returns the most segments a sub-launch holds
@@ -512,19 +571,6 @@ static long long adaptive_round_params(const mcpt_ctx* c, const float* invPV, co
   lin.n_local_px = p.n_local_px; lin.n_tiles = p.n_tiles; lin.tile_w = p.tile_w; lin.n_cu = c->n_cu;
   lin.partial_budget = c->partial_budget; lin.mesh = c->n_meshes > 0; lin.steal = false; lin.spare = false;
   return plan::limits(lin).max_seg;
-}
-static hipError_t stats_batch_counted(mcpt_ctx* c, int n, bool timed) {
-  hipError_t e = hipSuccess;
-  if (timed) e = hipEventRecord(c->stats_ev[0], c->stream);
-  if (e == hipSuccess)
-    e = mcpt_launch_stats_update_counted(c->d_accum, c->d_stats, (long long)c->n_local_rows * c->W, n,
-                                         c->d_ad_list + c->ad_n_blocks, c->stream);
-  if (e == hipSuccess && timed) e = hipEventRecord(c->stats_ev[1], c->stream);
-  if (e != hipSuccess) return e;
-  c->stats_passes += n;
-  c->stats_batches += 1;
-  if (timed) c->stats_update_timed = true;
-  return hipSuccess;
 }
 static int adaptive_round(mcpt_ctx* c, const float* invPV, const float* invV, int first_pass, int n_passes, float date,
                           int bounces, float refract_ind, int variant, bool counted, bool timed) {
@@ -563,7 +609,7 @@ static int adaptive_round(mcpt_ctx* c, const float* invPV, const float* invV, in
   else
     HIP_OR_RETURN(mcpt_launch_adaptive_add_passes(adaptive_target(c), c->d_ad_list, c->ad_n_list, n_passes, c->stream));
   c->pass_count += n_passes;   // the active blocks' count: the largest
-  if (c->stats_on) HIP_OR_RETURN(counted ? stats_batch_counted(c, n_passes, timed) : stats_batch(c, n_passes));
+  if (c->stats_on) HIP_OR_RETURN(stats_batch(c, n_passes, counted ? c->d_ad_list + c->ad_n_blocks : nullptr, timed));
   return MCPT_OK;
 }
 
@@ -579,53 +625,35 @@ int mcpt_render_adaptive(mcpt_ctx* c, const float* invPV, const float* invV, int
 // statistics' batch, on the schedule's rounds a select and the scan} on the stream, every list length
 // read on the device, one wait at the end for all the records.  f: the filtered rule's arguments
 // (null: mcpt_adaptive_select's rule); records: mcpt_adaptive_t or, with f, mcpt_adaptive_filtered_t.
-struct RunFilter { float raw_cap; int iterations; float k_color, sigma_plane; };
-
 static int adaptive_run(mcpt_ctx* c, const float* invPV, const float* invV, int first_pass, int n_passes, int rounds,
                         int check_every, float threshold, float mu_floor, float date, int bounces, float refract_ind,
                         int variant, const RunFilter* f, void* records, int records_capacity, mcpt_adaptive_run_t* out) {
   const char* who = f ? "mcpt_adaptive_run_filtered" : "mcpt_adaptive_run";
+  const SelectRule rule = {threshold, mu_floor, f};
   // mcpt_render_adaptive's checks, then the select's, then the run's own: before anything is enqueued
   OK_OR_RETURN(check_render_adaptive(c, invPV, invV, n_passes, variant, who));
   if (!out) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
-  for (float v : {threshold, mu_floor, f ? f->raw_cap : 1.0f, f ? f->k_color : 1.0f, f ? f->sigma_plane : 1.0f})
-    if (!(v > 0.0f) || !std::isfinite(v))
-      return set_err(MCPT_ERR_INVALID_ARG, "mcpt_adaptive_run: threshold, mu_floor and the filter's widths must be positive and finite");
-  if (f) {
-    if (f->iterations < 0 || f->iterations > 8)
-      return set_err(MCPT_ERR_INVALID_ARG, "mcpt_adaptive_run_filtered: iterations not in 0..8");
-    if (!plan::is_full_frame(c->rows, c->H))
-      return set_err(MCPT_ERR_INVALID_ARG, "mcpt_adaptive_run_filtered: needs a full-frame target (a shard is filtered after its gather)");
-    if (c->plane_valid || c->emap_plane_valid)
-      return set_err(MCPT_ERR_INVALID_ARG, "mcpt_adaptive_run_filtered: the context holds a gathered frame's counts or error map");
-  }
-  if (!c->stats_on) return set_err(MCPT_ERR_NO_STATS, "mcpt_adaptive_run: statistics are off (mcpt_stats_begin)");
-  if (f && !c->guides_valid)
-    return set_err(MCPT_ERR_NO_GUIDES, "mcpt_adaptive_run_filtered: no guides rendered for this target and scene");
+  OK_OR_RETURN(check_select_rule(c, rule, false, who));
   if (n_passes <= 0 || rounds < 1 || rounds > plan::kAdaptiveRunMaxRounds || check_every <= 0)
-    return set_err(MCPT_ERR_INVALID_ARG, "mcpt_adaptive_run: n_passes and check_every must be positive, rounds in 1..256");
+    return refuse(MCPT_ERR_INVALID_ARG, who, "n_passes and check_every must be positive, rounds in 1..256");
   const long long last_pass = (long long)first_pass + (long long)rounds * n_passes;
   if (last_pass > 0x7fffffffLL || (long long)c->pass_count + (long long)rounds * n_passes > 0x7fffffffLL)
-    return set_err(MCPT_ERR_INVALID_ARG, "mcpt_adaptive_run: the run's passes do not fit the pass counters");
+    return refuse(MCPT_ERR_INVALID_ARG, who, "the run's passes do not fit the pass counters");
   const int n_sel = plan::run_select_count(rounds, check_every, c->stats_batches);
   if (records_capacity < n_sel || (records_capacity > 0 && !records))
-    return set_err(MCPT_ERR_INVALID_ARG, "mcpt_adaptive_run: records holds fewer selects than the schedule can run");
+    return refuse(MCPT_ERR_INVALID_ARG, who, "records holds fewer selects than the schedule can run");
   std::memset(out, 0, sizeof(*out));
   out->rounds_queued = rounds;
   if (c->ad_n_list == 0) return MCPT_OK;   // every block retired: the host loop stops before its first round
 
   HIP_OR_RETURN(hipSetDevice(c->device));
-  HIP_OR_RETURN(ensure_timing_events(c->ad_ev, 6));
+  OK_OR_RETURN(ensure_select(c, f));
   HIP_OR_RETURN(ensure_timing_events(c->stats_ev, 2));
   HIP_OR_RETURN(ensure_timing_events(c->run_ev, 2));
   const size_t ring_bytes = sizeof(unsigned long long) * mcpt::kStatsRecWords * (size_t)plan::kAdaptiveRunMaxRounds;
   if (!c->d_run_rec) HIP_OR_RETURN(hipMalloc(&c->d_run_rec, ring_bytes));
   if (!c->d_run_len) HIP_OR_RETURN(hipMalloc(&c->d_run_len, sizeof(int) * (size_t)plan::kAdaptiveRunMaxRounds));
-  if (f) {
-    if (!c->d_run_rec_f) HIP_OR_RETURN(hipMalloc(&c->d_run_rec_f, ring_bytes));
-    HIP_OR_RETURN(ensure_timing_events(c->dn_ev, 10));
-    HIP_OR_RETURN(ensure_denoise_buffers(c));
-  }
+  if (f && !c->d_run_rec_f) HIP_OR_RETURN(hipMalloc(&c->d_run_rec_f, ring_bytes));
   {   // the segment-sum buffer of the run's largest sub-launch now: growing it waits for the stream
     mcpt::RenderParams p;
     const long long max_seg = adaptive_round_params(c, invPV, invV, true, p);
@@ -645,8 +673,6 @@ static int adaptive_run(mcpt_ctx* c, const float* invPV, const float* invV, int 
   const int list_in = c->ad_n_list, pass_in = c->pass_count, batches_in = c->stats_batches;
   const long long window_in = c->stats_passes;
   const bool emap_in = c->emap_valid;
-  const mcpt::AdaptiveTarget t = adaptive_target(c);
-  int* d_count = c->d_ad_list + c->ad_n_blocks;
   int sel_round[plan::kAdaptiveRunMaxRounds];
   invalidate_planes(c);
   HIP_OR_RETURN(hipEventRecord(c->run_ev[0], c->stream));
@@ -655,30 +681,12 @@ static int adaptive_run(mcpt_ctx* c, const float* invPV, const float* invV, int 
     OK_OR_RETURN(adaptive_round(c, invPV, invV, first_pass + i * n_passes, n_passes, date, bounces, refract_ind, variant,
                                 true, i == rounds - 1));
     if (!plan::run_round_selects(i, rounds, check_every, batches_in)) continue;
-    const bool timed = k == n_sel - 1;
-    unsigned long long* rec = c->d_run_rec + (size_t)k * mcpt::kStatsRecWords;
-    if (timed) HIP_OR_RETURN(hipEventRecord(c->ad_ev[0], c->stream));
-    HIP_OR_RETURN(mcpt_launch_adaptive_select(t, c->d_stats, c->d_emap, c->stats_passes, c->stats_batches, mu_floor,
-                                              threshold, c->ad_min_passes, f == nullptr, rec, c->stream));
-    c->emap_valid = true;
-    if (f) {
-      if (timed) HIP_OR_RETURN(hipEventRecord(c->ad_ev[1], c->stream));
-      OK_OR_RETURN(denoise_run(c, f->iterations, f->k_color, f->sigma_plane, true, true, true, timed));
-      if (timed) HIP_OR_RETURN(hipEventRecord(c->ad_ev[4], c->stream));
-      HIP_OR_RETURN(mcpt_launch_adaptive_select_filtered(t, c->d_dn[c->dn_result], c->d_emap, mu_floor, threshold,
-                                                         f->raw_cap, c->ad_min_passes,
-                                                         c->d_run_rec_f + (size_t)k * mcpt::kStatsRecWords, c->stream));
-    }
-    HIP_OR_RETURN(mcpt_launch_adaptive_compact(t, c->d_ad_list, d_count, c->stream));
-    if (timed) HIP_OR_RETURN(hipEventRecord(c->ad_ev[f ? 5 : 1], c->stream));
-    HIP_OR_RETURN(hipMemcpyAsync(c->d_run_len + k, d_count, sizeof(int), hipMemcpyDeviceToDevice, c->stream));
+    const size_t slot = (size_t)k * mcpt::kStatsRecWords;   // the select's own slices of the rings
+    const SelectDest dest = {c->d_run_rec + slot, f ? c->d_run_rec_f + slot : nullptr, c->d_run_len + k};
+    OK_OR_RETURN(enqueue_select(c, rule, dest, k == n_sel - 1));   // (events around the run's last select only)
     sel_round[k++] = i;
   }
   HIP_OR_RETURN(hipEventRecord(c->run_ev[1], c->stream));
-  if (n_sel > 0) {
-    c->ad_select_timed = true;
-    c->ad_select_split = f != nullptr;
-  }
   std::vector<unsigned long long> part((size_t)k * mcpt::kStatsRecWords), part_f(f ? part.size() : 0);
   std::vector<int> len((size_t)k);
   if (k > 0) {
@@ -703,22 +711,14 @@ static int adaptive_run(mcpt_ctx* c, const float* invPV, const float* invV, int 
   int status = MCPT_OK;
   for (int s = 0; s < o.selects_run; ++s) {
     unsigned long long h[5] = {0, 0, 0, 0, 0}, hf[5] = {0, 0, 0, 0, 0};
-    reduce_stats_records(part.data() + (size_t)s * mcpt::kStatsRecWords, 5, h);
-    if (f) reduce_stats_records(part_f.data() + (size_t)s * mcpt::kStatsRecWords, 5, hf);
-    const int n_list = len[(size_t)s];
-    if (n_list < 0 || n_list > c->ad_n_blocks || (unsigned long long)n_list != (f ? hf[4] : h[4])) {
-      status = set_err(MCPT_ERR_HIP, "mcpt_adaptive_run: the active list and the block flags disagree");
-      break;
-    }
-    c->ad_n_list = n_list;
-    mcpt_adaptive_t* raw = f ? &static_cast<mcpt_adaptive_filtered_t*>(records)[s].raw : &static_cast<mcpt_adaptive_t*>(records)[s];
-    fill_frame_record(c, h, raw);
-    raw->passes = window_in + (long long)(sel_round[s] + 1) * n_passes;
+    reduce_stats_records(part.data() + (size_t)s * mcpt::kStatsRecWords, 5, 2, h);
+    if (f) reduce_stats_records(part_f.data() + (size_t)s * mcpt::kStatsRecWords, 5, 2, hf);
+    mcpt_adaptive_filtered_t* filtered = f ? &static_cast<mcpt_adaptive_filtered_t*>(records)[s] : nullptr;
+    mcpt_adaptive_t* raw = f ? &filtered->raw : &static_cast<mcpt_adaptive_t*>(records)[s];
+    status = finish_select(c, h, hf, len[(size_t)s], who, raw, filtered);
+    if (status != MCPT_OK) break;
+    raw->passes = window_in + (long long)(sel_round[s] + 1) * n_passes;   // (the window as that select saw it)
     raw->batches = batches_in + sel_round[s] + 1;
-    raw->n_active_blocks = n_list;
-    raw->n_blocks = c->ad_n_blocks;
-    raw->samples = (long long)h[3];
-    if (f) fill_filtered_record(c, hf, &static_cast<mcpt_adaptive_filtered_t*>(records)[s]);
   }
   return status;
 }
@@ -740,39 +740,29 @@ int mcpt_adaptive_run_filtered(mcpt_ctx* c, const float* invPV, const float* inv
                       refract_ind, variant, &f, records, records_capacity, out);
 }
 
-int mcpt_read_sample_counts(mcpt_ctx* c, int* counts) {
-  if (!c || !counts) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
-  if (!has_pixel_counts(c)) return set_err(MCPT_ERR_NO_ADAPTIVE, "mcpt_read_sample_counts: adaptive mode is off (mcpt_adaptive_begin)");
+// every local pixel's sample count (mcpt_read_sample_counts) or, resolved, its accum / (float)count
+// (mcpt_read_resolved), through a device buffer of the call's own, on the host
+static int read_counted(mcpt_ctx* c, void* out, bool resolved, const char* who) {
+  if (!c || !out) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  if (!has_pixel_counts(c)) return refuse(MCPT_ERR_NO_ADAPTIVE, who, "adaptive mode is off (mcpt_adaptive_begin)");
   HIP_OR_RETURN(hipSetDevice(c->device));
-  const size_t n = (size_t)c->n_local_rows * c->W;
+  const size_t n = (size_t)c->n_local_rows * c->W, bytes = n * (resolved ? 3 * sizeof(float) : sizeof(int));
   if (n) {
-    int* d = nullptr;
-    HIP_OR_RETURN(hipMalloc(&d, n * sizeof(int)));
-    hipError_t e = mcpt_launch_counts(count_source(c), d, (long long)n, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(counts, d, n * sizeof(int), hipMemcpyDeviceToHost, c->stream);
+    void* d = nullptr;
+    HIP_OR_RETURN(hipMalloc(&d, bytes));
+    hipError_t e = resolved ? mcpt_launch_resolve(count_source(c), c->d_accum, (float*)d, (long long)n, c->stream)
+                            : mcpt_launch_counts(count_source(c), (int*)d, (long long)n, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d, bytes, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     (void)hipFree(d);
-    if (e != hipSuccess) return set_err(MCPT_ERR_HIP, "mcpt_read_sample_counts", e);
+    if (e != hipSuccess) return set_err(MCPT_ERR_HIP, who, e);
   }
   return MCPT_OK;
 }
 
-int mcpt_read_resolved(mcpt_ctx* c, float* rgb) {
-  if (!c || !rgb) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
-  if (!has_pixel_counts(c)) return set_err(MCPT_ERR_NO_ADAPTIVE, "mcpt_read_resolved: adaptive mode is off (mcpt_adaptive_begin)");
-  HIP_OR_RETURN(hipSetDevice(c->device));
-  const size_t n = (size_t)c->n_local_rows * c->W;
-  if (n) {
-    float* d = nullptr;
-    HIP_OR_RETURN(hipMalloc(&d, n * 3 * sizeof(float)));
-    hipError_t e = mcpt_launch_resolve(count_source(c), c->d_accum, d, (long long)n, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(rgb, d, n * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d);
-    if (e != hipSuccess) return set_err(MCPT_ERR_HIP, "mcpt_read_resolved", e);
-  }
-  return MCPT_OK;
-}
+int mcpt_read_sample_counts(mcpt_ctx* c, int* counts) { return read_counted(c, counts, false, "mcpt_read_sample_counts"); }
+
+int mcpt_read_resolved(mcpt_ctx* c, float* rgb) { return read_counted(c, rgb, true, "mcpt_read_resolved"); }
 
 // ---- checkpoint / resume of an adaptive render (the file layer: mcpt_image.cpp)
 int mcpt_adaptive_checkpoint_save(mcpt_ctx* c, const char* path, int next_pass, const char* tag) {
@@ -882,7 +872,7 @@ int mcpt_error_map_source(mcpt_ctx* c, int* source) {
 
 int mcpt_error_map_record(mcpt_ctx* c, float threshold, mcpt_convergence_t* out) {
   if (!c || !out) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
-  if (!(threshold > 0.0f) || !std::isfinite(threshold))
+  if (!positive_finite({threshold}))
     return set_err(MCPT_ERR_INVALID_ARG, "mcpt_error_map_record: threshold must be positive and finite");
   const int source = error_map_source(c);
   if (source == 0) return set_err(MCPT_ERR_NO_STATS, "mcpt_error_map_record: no error map (gathered or of the current statistics)");
@@ -890,11 +880,8 @@ int mcpt_error_map_record(mcpt_ctx* c, float threshold, mcpt_convergence_t* out)
   if (!c->d_emap_rec) HIP_OR_RETURN(hipMalloc(&c->d_emap_rec, sizeof(unsigned long long) * mcpt::kStatsRecWords));
   const long long n = (long long)c->n_local_rows * c->W;
   HIP_OR_RETURN(mcpt_launch_error_map_record(held_error_map(c), n, threshold, c->d_emap_rec, c->stream));
-  unsigned long long part[mcpt::kStatsRecWords] = {};
-  HIP_OR_RETURN(hipMemcpyAsync(part, c->d_emap_rec, sizeof(part), hipMemcpyDeviceToHost, c->stream));
-  HIP_OR_RETURN(hipStreamSynchronize(c->stream));
   unsigned long long h[3] = {0, 0, 0};
-  reduce_stats_records(part, 3, h);
+  OK_OR_RETURN(read_stats_records(c, 3, 2, c->d_emap_rec, h));
   fill_frame_record(c, h, out);
   if (source == 2) {   // (a gathered map belongs to no window of this context)
     out->passes = c->pass_count;
@@ -955,7 +942,7 @@ int mcpt_temporal_accumulate(mcpt_ctx* c, const float* prevPV16, int max_history
   if (!out) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
   if (max_history < 1 || max_history > MCPT_TEMPORAL_MAX_HISTORY)
     return set_err(MCPT_ERR_INVALID_ARG, "mcpt_temporal_accumulate: max_history not in 1..65535");
-  if (!(plane_tol > 0.0f) || !std::isfinite(plane_tol))
+  if (!positive_finite({plane_tol}))
     return set_err(MCPT_ERR_INVALID_ARG, "mcpt_temporal_accumulate: plane_tol must be positive and finite");
   const bool empty = c->tp_frames == 0;
   if (!empty && !prevPV16)
@@ -1000,15 +987,8 @@ int mcpt_temporal_accumulate(mcpt_ctx* c, const float* prevPV16, int max_history
   c->tp_cur = to;
   c->tp_frames += 1;
   c->tp_timed = true;
-  unsigned long long part[mcpt::kStatsRecWords] = {};
-  HIP_OR_RETURN(hipMemcpyAsync(part, c->d_tp_rec, sizeof(part), hipMemcpyDeviceToHost, c->stream));
-  HIP_OR_RETURN(hipStreamSynchronize(c->stream));
-  unsigned long long h[6] = {0, 0, 0, 0, 0, 0};
-  for (int s = 0; s < mcpt::kStatsRecSlots; ++s) {
-    const unsigned long long* q = part + (size_t)s * mcpt::kStatsRecStride;
-    for (int w = 0; w < 5; ++w) h[w] += q[w];
-    h[5] = std::max(h[5], q[5] & 0xffffffffull);
-  }
+  unsigned long long h[6] = {0, 0, 0, 0, 0, 0};   // (word 5: the longest history, a maximum)
+  OK_OR_RETURN(read_stats_records(c, 6, 5, c->d_tp_rec, h));
   out->n_px = (long long)n;
   out->n_history = (long long)h[0];
   out->n_miss = (long long)h[1];
@@ -1025,7 +1005,7 @@ int mcpt_denoise_temporal(mcpt_ctx* c, int iterations, float k_color, float sigm
   if (!c) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
   if (!c->tp_on) return set_err(MCPT_ERR_NO_TEMPORAL, "mcpt_denoise_temporal: temporal mode is off (mcpt_temporal_begin)");
   if (iterations < 0 || iterations > 8) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_denoise_temporal: iterations not in 0..8");
-  if (!(k_color > 0.0f) || !(sigma_plane > 0.0f) || !std::isfinite(k_color) || !std::isfinite(sigma_plane))
+  if (!positive_finite({k_color, sigma_plane}))
     return set_err(MCPT_ERR_INVALID_ARG, "mcpt_denoise_temporal: k_color and sigma_plane must be positive and finite");
   if (c->tp_frames == 0)
     return set_err(MCPT_ERR_NO_STATS, "mcpt_denoise_temporal: the history is empty (mcpt_temporal_accumulate)");
@@ -1037,7 +1017,8 @@ int mcpt_denoise_temporal(mcpt_ctx* c, int iterations, float k_color, float sigm
   HIP_OR_RETURN(hipEventRecord(c->dn_ev[9], c->stream));
   HIP_OR_RETURN(mcpt_launch_temporal_init(c->d_tp_c[c->tp_cur], c->d_dn[0], c->d_guide, c->W, c->H, c->stream));
   HIP_OR_RETURN(hipEventRecord(c->dn_ev[0], c->stream));
-  return atrous_iterations(c, iterations, k_color, sigma_plane, true, true, nullptr, naive, true);
+  // (the variance form's iterations on the history: guided, the variance filtered along, timed)
+  return atrous_iterations(c, iterations, k_color, sigma_plane, kVariance, nullptr, naive);
 }
 
 int mcpt_read_temporal(mcpt_ctx* c, float* rgbv4, int* history_len) {
@@ -1062,19 +1043,23 @@ int mcpt_last_temporal_ms(mcpt_ctx* c, float* accumulate_ms, float* copy_ms) {
   return pair_ms(c->tp_timed && c->tp_copy, c->tp_ev[1], c->tp_ev[2], copy_ms);   // (ping-pong: no copy, 0)
 }
 
+// channels first .. first + n_ch - 1 of the last filter run's result d_dn[dn_result], packed
+static int read_denoised_channels(mcpt_ctx* c, int first, int n_ch, float* out) {
+  HIP_OR_RETURN(hipSetDevice(c->device));
+  const size_t n = (size_t)c->n_local_rows * c->W;
+  std::vector<float> h(n * 4);
+  if (n) HIP_OR_RETURN(hipMemcpyAsync(h.data(), c->d_dn[c->dn_result], n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+  HIP_OR_RETURN(hipStreamSynchronize(c->stream));
+  for (size_t i = 0; i < n; ++i)
+    for (int k = 0; k < n_ch; ++k) out[(size_t)n_ch * i + k] = h[4 * i + first + k];
+  return MCPT_OK;
+}
+
 int mcpt_read_denoised(mcpt_ctx* c, float* rgb_out) {
   if (!c || !rgb_out) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
   if (!c->has_target) return mcpt_err_bare(MCPT_ERR_NO_TARGET);
   if (c->dn_result < 0) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_read_denoised: no mcpt_denoise on this target yet");
-  HIP_OR_RETURN(hipSetDevice(c->device));
-  const size_t n = (size_t)c->n_local_rows * c->W;
-  std::vector<float4> h(n);
-  if (n) HIP_OR_RETURN(hipMemcpyAsync(h.data(), c->d_dn[c->dn_result], n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
-  HIP_OR_RETURN(hipStreamSynchronize(c->stream));
-  for (size_t i = 0; i < n; ++i) {
-    rgb_out[3 * i] = h[i].x; rgb_out[3 * i + 1] = h[i].y; rgb_out[3 * i + 2] = h[i].z;
-  }
-  return MCPT_OK;
+  return read_denoised_channels(c, 0, 3, rgb_out);
 }
 
 int mcpt_read_denoised_variance(mcpt_ctx* c, float* v_out) {
@@ -1082,13 +1067,7 @@ int mcpt_read_denoised_variance(mcpt_ctx* c, float* v_out) {
   if (!c->has_target) return mcpt_err_bare(MCPT_ERR_NO_TARGET);
   if (c->dn_result < 0 || !c->dn_variance)
     return set_err(MCPT_ERR_NO_STATS, "mcpt_read_denoised_variance: the last filter run was no mcpt_denoise_variance");
-  HIP_OR_RETURN(hipSetDevice(c->device));
-  const size_t n = (size_t)c->n_local_rows * c->W;
-  std::vector<float4> h(n);
-  if (n) HIP_OR_RETURN(hipMemcpyAsync(h.data(), c->d_dn[c->dn_result], n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
-  HIP_OR_RETURN(hipStreamSynchronize(c->stream));
-  for (size_t i = 0; i < n; ++i) v_out[i] = h[i].w;
-  return MCPT_OK;
+  return read_denoised_channels(c, 3, 1, v_out);
 }
 
 int mcpt_last_denoise_ms(mcpt_ctx* c, float* guides_ms, float* filter_ms) {

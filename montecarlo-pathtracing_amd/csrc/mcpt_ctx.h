@@ -333,5 +333,6 @@ void scene_params(const mcpt_ctx* c, const float* invPV, const float* invV, mcpt
 void pass_params(int first_pass, int n_passes, float date, int bounces, float refract_ind, int variant,
                  mcpt::RenderParams& p);
 int checked_sub_launch(mcpt_ctx* c, int k, int n_sub, const mcpt::RenderParams& p);
-// mcpt_capi_post.hip: one batch of the noise statistics behind the last combine
-hipError_t stats_batch(mcpt_ctx* c, int n);
+// mcpt_capi_post.hip: one batch of the noise statistics behind the last combine (d_count: the counted
+// twin of a queued adaptive run, reading the list's length there; timed false: no events)
+hipError_t stats_batch(mcpt_ctx* c, int n, const int* d_count = nullptr, bool timed = true);

@@ -963,9 +963,7 @@ class Renderer:
         _check(lib().mcpt_adaptive_select_filtered(self._h, float(threshold), float(raw_cap), float(mu_floor),
                                                    int(iterations), float(k_color), float(sigma_plane),
                                                    ctypes.byref(rec)), "mcpt_adaptive_select_filtered")
-        out = {k: getattr(rec.raw, k) for k, _ in Adaptive._fields_}
-        out.update({k: getattr(rec, k) for k in ("n_above_f", "sum_qf", "max_rf", "mean_rf")})
-        return out
+        return self._filtered_dict(rec)
 
     def read_denoised(self) -> np.ndarray:
         """mcpt_read_denoised: (local rows, W, 3) f32, the last filter run's image."""
