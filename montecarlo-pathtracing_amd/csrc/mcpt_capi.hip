@@ -1020,6 +1020,12 @@ static int launch(mcpt_ctx* c, const float* invPV, const float* invV, int first_
   lin.n_local_px = p.n_local_px; lin.n_tiles = p.n_tiles; lin.tile_w = p.tile_w; lin.seg_per_item = p.seg_per_item;
   lin.n_cu = c->n_cu; lin.partial_budget = c->partial_budget; lin.mesh = c->n_meshes > 0;
   lin.wave_traversal = p.wave_traversal != 0; lin.steal = steal;
+  // the LDS-scene kernel steals passes inside each wave: timed megakernel launches
+  // only, and none of AUTO's trials (their plan and kernel stay the ones the candidates were
+  // compared with)
+  const bool scene_steal = steal && p.lds_scene_bytes > 0 && c->n_meshes == 0 && !p.wave_traversal && !count &&
+                           !stream && schedule_settled(c);
+  lin.lds_scene = scene_steal;
   const plan::Limits lim = plan::limits(lin);
   if (lim.too_large) return set_err(MCPT_ERR_INVALID_ARG, "render target too large for one launch");
   const bool split = plan::pass_split(lim, p.n_tiles, n_passes, total_seg, c->n_cu, stream, env_int("MCPT_PASS_SPLIT", -1));
@@ -1079,6 +1085,13 @@ static int launch(mcpt_ctx* c, const float* invPV, const float* invV, int first_
     if (lane) HIP_OR_RETURN(hipStreamWaitEvent(L.stream, lane_freed(c, L), 0));
     if (it.order) OK_OR_RETURN(prepare_order(c, li, ws, in, it, p));
     if (it.split_items) OK_OR_RETURN(prepare_split_items(c, L, ws, it.items, steal, p));
+    // (launches of one segment add into the accumulator themselves, pass-split ones run one pass
+    // per item: neither steals)
+    if (scene_steal && lim.may_steal && p.n_segments > 1 && !split) {
+      OK_OR_RETURN(ensure_lane_bytes(c, L.d_steal, L.steal_bytes, sizeof(float) * 3 * (size_t)p.n_tiles * p.n_segments *
+                                                                      mcpt::kPassChunk * p.tile_w * mcpt::kTileH));
+      p.steal_vals = L.d_steal;
+    }
     // The timed interval of a lane launch that follows one on the other lane starts where that
     // launch's render ended (recorded on its stream): the launches overlap, and each is charged
     // its period, not its whole span (which would count the overlapped tails twice)

@@ -68,7 +68,9 @@ constexpr int kMinWavesL2 = 7;
 // 8x8 blocks p.list names, not the blocks of one tile — "tile" is then the workgroup's group of
 // TW / 8 list entries, and only a wave's block origin differs.  One segment per item, no item
 // order, tail pieces, split items, pass stealing or pass split.
-template <bool COUNT, bool WAVE, bool MESH, bool LDSS, bool SUSPEND, int TW, bool LIST = false>
+// STEAL (the LDS-scene kernels of timed launches, RenderParams::steal_vals set):
+// pass stealing inside each wave of the workgroup, over all the segments of the work item.
+template <bool COUNT, bool WAVE, bool MESH, bool LDSS, bool SUSPEND, int TW, bool LIST = false, bool STEAL = false>
 __global__ __launch_bounds__(TW * kTileH, MESH && !WAVE ? kMinWavesMesh
                                            : (!WAVE && !LDSS ? kMinWavesL2 : kMinWaves)) void render_kernel(
     RenderParams p) {
@@ -81,6 +83,7 @@ __global__ __launch_bounds__(TW * kTileH, MESH && !WAVE ? kMinWavesMesh
   // the launch's work-item order (mcpt_order.hip): costliest items of an earlier launch first;
   // in the mesh kernels the costliest of them split in kSplitPieces pass ranges (piece >= 0)
   constexpr bool kSplit = MESH && !WAVE && !COUNT && !LIST;   // (LIST: no split items, no pass stealing)
+  static_assert(!STEAL || (LDSS && !MESH && !WAVE && !COUNT && !LIST), "STEAL: the LDS-scene render kernels");
   int item, piece = -1, sj = -1;
   // (idx_ok: the checked build's bounds tests, mcpt_internal.h; true in the shipped build.  The
   // workgroup-uniform ones return the whole workgroup before the LDS staging barrier.)
@@ -179,6 +182,8 @@ __global__ __launch_bounds__(TW * kTileH, MESH && !WAVE ? kMinWavesMesh
     pass_end = pass_begin + 1;
   }
   const int seg_first = pass_begin;   // the segment's first pass (pass stealing: value slots)
+  // STEAL: the lanes' passes are claimed over all of the work item's segments, pass_end is its end
+  if constexpr (STEAL) pass_end = min(p.first_pass + p.n_passes, (c0 + seg_n) * kPassChunk + 1);
   int b1 = 0;   // a split item's first pass of piece 1 (its later pieces store per-pass values)
   if (kSplit && piece >= 0) {   // (split launches: full 32-pass segments, one per item)
     const int n = pass_end - pass_begin;
@@ -190,6 +195,12 @@ __global__ __launch_bounds__(TW * kTileH, MESH && !WAVE ? kMinWavesMesh
   }
   const int y = live ? p.rows[lr] : 0;   // this shard's local row -> image row (mcpt_set_target*)
 
+  // STEAL: each wave's own claim counter over its units (pass of the item, pixel of the wave) =
+  // (u / 64, u % 64); lane l starts with unit l, its own pixel's first pass.  A wave never takes a
+  // unit of its sibling: every LDS word a stolen pass reads was written by the wave itself, whose
+  // LDS operations are in order, so no barrier enters the render loop.
+  __shared__ int s_wclaim[STEAL ? TT / 64 : 1];
+  __shared__ unsigned s_wstolen[STEAL ? TT / 64 : 1];
   SceneT<MESH, LDSS> s{p.nodes, p.leaves, p.ptype, p.prims, p.depth, p.minfo, p.mpairs, p.mleaftris, p.mtris,
                        p.mverts, p.mnorms, p.flat_face};
   if constexpr (LDSS) {
@@ -201,6 +212,9 @@ __global__ __launch_bounds__(TW * kTileH, MESH && !WAVE ? kMinWavesMesh
     int* s_int = (int*)(s_scene + n4);
     for (int i = tid; i < n_leaves + p.n_prims; i += TT)
       s_int[i] = i < n_leaves ? p.leaves[i] : p.ptype[i - n_leaves];
+    if constexpr (STEAL) {
+      if (lane == 0) { s_wclaim[wave] = 64; s_wstolen[wave] = 0u; }
+    }
     __syncthreads();
     s.nodes = s_scene;
     s.prims = s_scene + 3 * n_nodes;
@@ -264,9 +278,14 @@ __global__ __launch_bounds__(TW * kTileH, MESH && !WAVE ? kMinWavesMesh
   // (u, v) of this pixel for the seed of a new pass (seed_for): the same values as u, v above
   auto pix_seed = [&](int ps) {
     if constexpr (kPixLds) return seed_for(s_pix[18][pj], s_pix[19][pj], ps, p.date);
+    else if constexpr (STEAL) return seed_for(s_pix[12][pj], s_pix[13][pj], ps, p.date);
     else return seed_for(((float)x + 0.5f) / (float)p.W, ((float)y + 0.5f) / (float)p.H, ps, p.date);
   };
-  s_pix[12][tid] = 0.0f; s_pix[13][tid] = 0.0f; s_pix[14][tid] = 0.0f;   // this segment's sum
+  if constexpr (STEAL) {   // (no segment sums: the rows hold the pixel's (u, v) for a stolen pass's seed)
+    s_pix[12][tid] = u; s_pix[13][tid] = v;
+  } else {
+    s_pix[12][tid] = 0.0f; s_pix[13][tid] = 0.0f; s_pix[14][tid] = 0.0f;   // this segment's sum
+  }
   const f3 Ocam = mk(p.ox, p.oy, p.oz);
 
 
@@ -309,6 +328,7 @@ __global__ __launch_bounds__(TW * kTileH, MESH && !WAVE ? kMinWavesMesh
 #endif
   // this segment's sum -> accumulator (one-segment launch) or its segment slot
   auto flush_sum = [&]() {
+    if constexpr (STEAL) return;
     if (kSplit && (piece > 0 || steal)) return;   // passes stored one by one (add_pass)
     // the pixel's address is recomputed at each flush (an empty asm makes the row opaque):
     // hoisted out of the render loop, its 64-bit index and pointer were 4 spilled VGPRs
@@ -336,6 +356,21 @@ __global__ __launch_bounds__(TW * kTileH, MESH && !WAVE ? kMinWavesMesh
   // a finished pass's value: into this segment's sum, or (a split item's later pieces) stored
   // for the combine, which adds it after piece 0's sum in pass order
   auto add_pass = [&](f3 v) {
+    if constexpr (STEAL) {
+      // slot (tile, segment, pass of its chunk, thread of the tile): combine_steal_seg_kernel
+      const int ch = (pass - 1) >> 5, sg = ch - cbase, off = (pass - 1) & (kPassChunk - 1);
+      if constexpr (kChecked) {
+        if (!idx_ok(p.events, CK_STEAL_SLOT, sg, p.n_segments) || !idx_ok(p.events, CK_STEAL_SLOT, pj, TT) ||
+            !idx_ok(p.events, CK_STEAL_SLOT, tile, p.n_tiles))
+          return;
+      }
+      // (the slot's index in 32 bits: plan::limits keeps a launch's store below 2^32 slots; 64-bit
+      // index arithmetic per lane cost the kernel spilled registers)
+      const unsigned slot = (((unsigned)(tile * p.n_segments + sg) * kPassChunk + off) * TT + (unsigned)pj);
+      float* q = p.steal_vals + (size_t)slot * 3;
+      q[0] = v.x; q[1] = v.y; q[2] = v.z;
+      return;
+    }
     if (kSplit && steal) {
       if constexpr (kChecked) {
         if (!idx_ok(p.events, CK_SPLIT_PASS, pass - seg_first, kPassChunk) || !idx_ok(p.events, CK_SPLIT_PASS, pj, kTileThreads))
@@ -375,7 +410,26 @@ __global__ __launch_bounds__(TW * kTileH, MESH && !WAVE ? kMinWavesMesh
       }
     }
   };
+  // STEAL: the same inside one wave of a workgroup of several, over the passes of all the item's
+  // segments (pass_end: the item's end)
+  auto wave_steal_next = [&]() {
+    const int n_units = 64 * (pass_end - pass_begin);
+    for (;;) {
+      const int u = atomicAdd(&s_wclaim[STEAL ? wave : 0], 1);
+      if (u >= n_units) { pass = pass_end; return; }
+      const int t = u & 63;
+      if (bx0 + (t & 7) < p.W && by0 + (t >> 3) < p.n_local_rows) {
+        pj = wave * 64 + t; pass = pass_begin + (u >> 6);
+        if (t != lane) atomicAdd(&s_wstolen[STEAL ? wave : 0], 1u);
+        return;
+      }
+    }
+  };
   auto next_chunk = [&]() {
+    if constexpr (STEAL) {
+      wave_steal_next();
+      return;
+    }
     if (kSplit && steal) {
       steal_next();
       return;
@@ -638,6 +692,10 @@ __global__ __launch_bounds__(TW * kTileH, MESH && !WAVE ? kMinWavesMesh
   }
 #endif
 
+  if constexpr (STEAL) {
+    if (p.events && (int)__lane_id() == __builtin_ffsll((long long)__ballot(1)) - 1 && s_wstolen[wave])
+      atomicAdd(p.events + kDebugStealSlot, (unsigned long long)s_wstolen[wave]);
+  }
   if constexpr (kSplit) {   // (one wave: its LDS operations are in order)
     if (steal && p.events && (int)__lane_id() == __builtin_ffsll((long long)__ballot(1)) - 1 && s_stolen)
       atomicAdd(p.events + kDebugStealSlot, (unsigned long long)s_stolen);
@@ -764,6 +822,39 @@ __global__ __launch_bounds__(256) void combine_steal_kernel(float* __restrict__ 
   accum[i * 3] = a0; accum[i * 3 + 1] = a1; accum[i * 3 + 2] = a2;
 }
 
+// launches of the LDS-scene kernels with pass stealing (render_kernel<.., STEAL>): one thread per
+// thread of a tile, so that a wave reads 64 consecutive values of a slot row.  Per pixel and
+// segment the launch's passes of the chunk are summed from 0 in pass order (a lane's add_pass
+// sequence), and the sums are added to the accumulator in segment order (combine_kernel's).
+__global__ __launch_bounds__(256) void combine_steal_seg_kernel(float* __restrict__ accum, int n_tiles, int n_seg, int W,
+                                                                int n_local_rows, int TW, const float* __restrict__ vals,
+                                                                int first_pass, int n_passes, unsigned long long* ev) {
+  const int TT = TW * kTileH;
+  const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (g >= (long long)n_tiles * TT) return;
+  const int tile = (int)(g / TT), t = (int)(g - (long long)tile * TT);
+  const int tiles_x = (W + TW - 1) / TW, wv = t >> 6, l = t & 63;
+  const int x = (tile % tiles_x) * TW + (wv % (TW / 8)) * 8 + (l & 7);
+  const int lr = (tile / tiles_x) * kTileH + (wv / (TW / 8)) * 8 + (l >> 3);
+  if (x >= W || lr >= n_local_rows) return;
+  const long long i = (long long)lr * W + x;
+  if (!idx_ok(ev, CK_PIXEL, i, (long long)n_local_rows * W)) return;
+  const int cbase = floordiv(first_pass - 1, kPassChunk);
+  float a0 = accum[i * 3], a1 = accum[i * 3 + 1], a2 = accum[i * 3 + 2];
+  for (int s = 0; s < n_seg; ++s) {
+    const int c = cbase + s;
+    const int lo = max(first_pass, c * kPassChunk + 1), hi = min(first_pass + n_passes, (c + 1) * kPassChunk + 1);
+    const float* row = vals + ((((size_t)tile * n_seg + s) * kPassChunk) * TT + t) * 3;
+    float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f;
+    for (int ps = lo; ps < hi; ++ps) {
+      const float* v = row + (size_t)(ps - (c * kPassChunk + 1)) * TT * 3;
+      s0 = s0 + v[0]; s1 = s1 + v[1]; s2 = s2 + v[2];
+    }
+    a0 = a0 + s0; a1 = a1 + s1; a2 = a2 + s2;
+  }
+  accum[i * 3] = a0; accum[i * 3 + 1] = a1; accum[i * 3 + 2] = a2;
+}
+
 // ------------------------------------------------------------------------------------
 // ray queries: the shader library's traverse_all_bvh / just_hit_bvh / intersect_one_prim /
 // hit_one_prim + intersection_info + intersection_color_info / _mat_info
@@ -865,6 +956,18 @@ hipError_t mcpt_launch_render(const mcpt::RenderParams& p, bool count, hipStream
   const size_t shm = lds ? (size_t)p.lds_scene_bytes : 0;
 #define MCPT_RENDER(C, W, M, L, S, T) \
   hipLaunchKernelGGL((mcpt::render_kernel<C, W, M, L, S, T>), grid, block, shm, stream, p)
+  // the LDS-scene kernels with pass stealing (launch() sets steal_vals on timed per-lane launches)
+  if (p.steal_vals && !mesh) {
+    if (!lds || count || wave || p.pass_split || p.n_segments < 2) return hipErrorInvalidValue;
+    if (p.tile_w == 16) {
+      if (susp) hipLaunchKernelGGL((mcpt::render_kernel<false, false, false, true, true, 16, false, true>), grid, block, shm, stream, p);
+      else hipLaunchKernelGGL((mcpt::render_kernel<false, false, false, true, false, 16, false, true>), grid, block, shm, stream, p);
+    } else {
+      if (susp) hipLaunchKernelGGL((mcpt::render_kernel<false, false, false, true, true, 32, false, true>), grid, block, shm, stream, p);
+      else hipLaunchKernelGGL((mcpt::render_kernel<false, false, false, true, false, 32, false, true>), grid, block, shm, stream, p);
+    }
+    return hipGetLastError();
+  }
 #define MCPT_RENDER_CW(C, W, S)                                          \
   if (mesh && lds) MCPT_RENDER(C, W, true, true, S, 8);                  \
   else if (mesh) MCPT_RENDER(C, W, true, false, S, 8);                   \
@@ -915,6 +1018,13 @@ hipError_t mcpt_launch_render_list(const mcpt::RenderParams& p, hipStream_t stre
 hipError_t mcpt_launch_combine(const mcpt::RenderParams& p, hipStream_t stream) {
   if (p.n_local_px <= 0) return hipSuccess;
   dim3 block(256), grid((unsigned)((p.n_local_px + 255) / 256));
+  if (p.steal_vals && p.n_meshes == 0) {   // the LDS-scene kernels' stealing: slots by (tile, segment, pass, thread)
+    const long long n_thr = (long long)p.n_tiles * p.tile_w * mcpt::kTileH;
+    hipLaunchKernelGGL(mcpt::combine_steal_seg_kernel, dim3((unsigned)((n_thr + 255) / 256)), block, 0, stream, p.accum,
+                       p.n_tiles, p.n_segments, p.W, p.n_local_rows, p.tile_w, p.steal_vals, p.first_pass, p.n_passes,
+                       p.events);
+    return hipGetLastError();
+  }
   if (p.steal_vals) {   // (also for one segment: the render stored passes, no sums)
     hipLaunchKernelGGL(mcpt::combine_steal_kernel, grid, block, 0, stream, p.accum, p.n_local_px, p.n_segments, p.W,
                        p.tile_w, p.steal_vals);

@@ -29,6 +29,9 @@ namespace plan {
 constexpr size_t kDefaultPartialBudget = size_t(4) << 30;
 // per-pass value store of pass stealing (mesh launches), per render lane
 constexpr size_t kStealBudget = size_t(8) << 30;
+// ... and of the LDS-scene launches, per render lane: 1080p in 16-wide tiles holds
+// 21 segments (C2's eight are one launch of 6.4 GB), 4K five
+constexpr size_t kSceneStealBudget = size_t(16) << 30;
 // work-item order (mcpt_order.hip): launches with at least this many work items run in the
 // order sorted from an earlier launch of their shape; the order is re-sorted every
 // kOrderRefresh launches of the shape (costs drift little: the same tiles and pass counts)
@@ -54,13 +57,14 @@ struct LimitsIn {
   int tile_w = 16, seg_per_item = 1, n_cu = 256;
   size_t partial_budget = kDefaultPartialBudget;
   bool mesh = false, wave_traversal = false;
+  bool lds_scene = false;   // the LDS-scene kernel (a staged scene, no meshes)
   bool steal = true;    // the MCPT_STEAL switch (adaptive launches: false)
   bool spare = true;    // reserve the grid's spare workgroups (adaptive launches add none: false)
 };
 struct Limits {
   long long max_items = 0;   // grid-size bound on the work items (n_tiles above it: target too large)
   long long max_seg = 1;     // most pass segments of one sub-launch
-  bool may_steal = false;
+  bool may_steal = false;    // mesh launches of one segment per item; LDS-scene launches (lds_scene)
   bool too_large = false;
 };
 // The call's pass range is cut at accumulation-chunk boundaries into sub-launches of at
@@ -84,6 +88,22 @@ inline Limits limits(const LimitsIn& in) {
   r.may_steal = in.mesh && !in.wave_traversal && kseg_max == 1 && in.steal;
   if (r.may_steal && seg_bytes > 0)
     max_seg = std::min(max_seg, std::max(2LL, (long long)(kStealBudget / ((size_t)seg_bytes * kPassChunk))));
+  // the LDS-scene launches steal inside each wave at any number of segments per item (DESIGN.md
+  // §4.8) and store every pass's value by (tile, segment, pass of the chunk, thread of the tile):
+  // at most kSceneStealBudget per render lane, in whole items (kseg_max segments), one at least.
+  // 4K in 16-wide tiles: 3.19 GB per segment, so five segments fit and a launch of four-segment
+  // items holds four of them: C5's 1,024-pass step is eight sub-launches of 128 passes.
+  if (in.lds_scene && !in.mesh && !in.wave_traversal && in.steal) {
+    r.may_steal = true;
+    const long long val_bytes = in.n_tiles * in.tile_w * kTileH * 3 * (long long)sizeof(float) * kPassChunk;
+    // (the kernel indexes the store's 12-byte slots in 32 bits: a frame whose single item would
+    // hold 2^32 of them does not steal)
+    if (val_bytes * kseg_max >= (12LL << 32)) r.may_steal = false;
+    else if (val_bytes > 0) {
+      const long long fit = (long long)(kSceneStealBudget / (size_t)val_bytes);
+      max_seg = std::min(max_seg, std::max(kseg_max, fit / kseg_max * kseg_max));
+    }
+  }
   r.max_seg = std::max(1LL, std::min(max_seg, in.n_tiles > 0 ? r.max_items / in.n_tiles : r.max_items));
   return r;
 }
