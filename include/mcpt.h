@@ -766,6 +766,79 @@ int mcpt_temporal_info(mcpt_ctx* ctx, int* on, int* history_valid, long long* fr
  * form); either NULL */
 int mcpt_last_temporal_ms(mcpt_ctx* ctx, float* accumulate_ms, float* copy_ms);
 
+/* Temporal adaptive sampling (no reference equivalent): render only the blocks
+ * the history cannot carry.  A stopping rule that asks whether the blend this frame's accumulate
+ * would write NOW meets the target, and an accumulate that accepts the per-pixel counts this leaves
+ * behind.  Per camera k a caller runs:
+ *   1. mcpt_clear_accum, mcpt_stats_begin, mcpt_adaptive_begin(min_passes).  mcpt_adaptive_begin on a
+ *      context whose mode is on re-initialises the state: every flag set, every block's passes 0,
+ *      p0 = the accumulator's pass count (0 after the clear), the list full.
+ *   2. mcpt_render_guides(camera k): the rule reads the guides of the camera being rendered.
+ *   3. rounds of mcpt_render_adaptive with mcpt_adaptive_select_temporal from the second batch on, or
+ *      one mcpt_adaptive_run_temporal.
+ *   4. mcpt_temporal_accumulate_resolved(P·V of camera k-1).
+ *   5. mcpt_denoise_temporal, mcpt_read_denoised.
+ *
+ * mcpt_temporal_accumulate_resolved: mcpt_temporal_accumulate with two inputs changed.  The current
+ * colour is c = accum / (float)count per channel, mcpt_read_resolved's bits, the count the adaptive
+ * mode's (p0 plus the block's passes); the variance is v = min(se^2, 2^60) of the held error map,
+ * where retired blocks keep the entries they retired with (as mcpt_denoise_resolved_variance reads
+ * them).  The look-up, the tap tests, the blend, the record and both history forms are unchanged.
+ * Preconditions: mcpt_temporal_accumulate's, in its order, except that the adaptive mode must be on
+ * (else MCPT_ERR_NO_ADAPTIVE, checked right after MCPT_ERR_NO_TEMPORAL) and retired blocks are
+ * allowed; a gathered count plane is still refused.  With no block retired it gives
+ * mcpt_temporal_accumulate's bits.  mcpt_temporal_accumulate itself still refuses a frame with a
+ * retired block.
+ *
+ * mcpt_adaptive_select_temporal: the third rule behind the select step (beside mcpt_adaptive_select
+ * and mcpt_adaptive_select_filtered).  One call, two steps on the context's stream:
+ *   A  as mcpt_adaptive_select_filtered's step A: the {se, r} of the active blocks' pixels into the
+ *      error map and the raw record; no block retires.
+ *   T  for every in-frame pixel of a block that is active on entry, `out` = what
+ *      mcpt_temporal_accumulate_resolved(prevPV16, max_history, plane_tol) would write for it now (the
+ *      same arithmetic on the history's current set and the map step A wrote; nothing is written to
+ *      the history), then in binary32 without contraction in the order written:
+ *        Yt = (0.2126 out.r + 0.7152 out.g) + 0.0722 out.b;
+ *        rt = sqrt(out.v) / (max(0, Yt) + mu_floor);  rt = 64 if Yt is not finite or not rt <= 64.
+ *      The block stays active iff its largest rt > threshold or it holds fewer than min_passes
+ *      passes.  Retired blocks are not computed and never return.  The list is rebuilt as
+ *      mcpt_adaptive_select rebuilds it.
+ * On an empty history every pixel is new, so the rule is a raw-error rule on {c, v}.
+ * The record: `raw` as mcpt_adaptive_select_filtered's raw, n_active_blocks = the blocks THIS rule
+ * keeps; the other fields run over the in-frame pixels of the blocks active on entry.  Integer sums
+ * and a maximum: the bits do not depend on the order.
+ * Preconditions, in this order, a refusal changing nothing: adaptive mode on (else
+ * MCPT_ERR_NO_ADAPTIVE); temporal mode on (else MCPT_ERR_NO_TEMPORAL); threshold, mu_floor and
+ * plane_tol positive and finite, max_history in 1..65535, prevPV16 non-NULL unless the history is
+ * empty, a full-frame target in row order that holds passes, no gathered count plane or gathered
+ * error map (else MCPT_ERR_INVALID_ARG); statistics on with two batches or more (else
+ * MCPT_ERR_NO_STATS); current guides (else MCPT_ERR_NO_GUIDES).
+ * mcpt_last_adaptive_ms's select time covers steps A and T with the list scan.  The three selects
+ * may alternate freely: all only retire.  Device memory: the filtered select's block of partial
+ * records (4 KiB, the statistics buffers' lifetime) serves step T; nothing per pixel.  Synchronizes
+ * once, at the end, for the record.
+ *
+ * mcpt_adaptive_run_temporal: the queued form, mcpt_adaptive_run with this rule (its contract and
+ * preconditions as stated there, the select's as above), records of mcpt_adaptive_temporal_t. */
+typedef struct mcpt_adaptive_temporal_t {
+  mcpt_adaptive_t raw;        /* as mcpt_adaptive_select_filtered's raw: n_active_blocks = what THIS rule keeps */
+  long long n_px_t;           /* in-frame pixels of the blocks active on entry */
+  long long n_above_t;        /* of those, rt > threshold */
+  unsigned long long sum_qt;  /* sum of trunc(rt * 65536) over them */
+  float max_rt;
+  double mean_rt;             /* sum_qt / 65536 / n_px_t (0 when n_px_t = 0) */
+  long long n_history;        /* of those, pixels whose dry-run class is HISTORY */
+} mcpt_adaptive_temporal_t;
+extern int mcpt_temporal_accumulate_resolved(mcpt_ctx* ctx, const float* prevPV16, int max_history, float plane_tol,
+                                             mcpt_temporal_t* out);
+extern int mcpt_adaptive_select_temporal(mcpt_ctx* ctx, const float* prevPV16, int max_history, float plane_tol,
+                                         float threshold, float mu_floor, mcpt_adaptive_temporal_t* out);
+extern int mcpt_adaptive_run_temporal(mcpt_ctx* ctx, const float* invPV, const float* invV, int first_pass, int n_passes,
+                                      int rounds, int check_every, float threshold, float mu_floor,
+                                      const float* prevPV16, int max_history, float plane_tol, float date, int bounces,
+                                      float refract_ind, int variant, mcpt_adaptive_temporal_t* records,
+                                      int records_capacity, mcpt_adaptive_run_t* out);
+
 /* DrawSampling's point cloud (DrawSampling/draw_sampling.cpp:144-150, tp/sampling_base.vert
  * seeding, tp/hsphere.vert random_ray): point k = random_ray(normalize(normal), roughness)
  * with seed floatBitsToUint(fseed) + k * nb_used * (11, 43, 67).  out: n × 3 f32 (host). */

@@ -510,6 +510,44 @@ class Renderer {
     check(mcpt_read_denoised(c_, img.data()), "mcpt_read_denoised");
     return img;
   }
+  // ---- temporal adaptive sampling (mcpt.h): render only the blocks the history
+  // cannot carry.  kTemporalTarget: the sweep's default (tools/temporal_adaptive_bench.py)
+  static constexpr float kTemporalTarget = 0.05f;
+  // temporal_accumulate with every pixel's own sample count (the adaptive mode on; retired blocks allowed)
+  mcpt_temporal_t temporal_accumulate_resolved(const GLMat4* prevPV, int max_history = kTemporalMaxHistory,
+                                               float plane_tol = kTemporalPlaneTol) {
+    mcpt_temporal_t rec;
+    check(mcpt_temporal_accumulate_resolved(c_, prevPV ? prevPV->m : nullptr, max_history, plane_tol, &rec),
+          "mcpt_temporal_accumulate_resolved");
+    return rec;
+  }
+  // the select on the error of the blend temporal_accumulate_resolved would write now
+  mcpt_adaptive_temporal_t adaptive_select_temporal(const GLMat4* prevPV, float threshold = kTemporalTarget,
+                                                    int max_history = kTemporalMaxHistory,
+                                                    float plane_tol = kTemporalPlaneTol,
+                                                    float mu_floor = kErrorMuFloor) {
+    mcpt_adaptive_temporal_t rec;
+    check(mcpt_adaptive_select_temporal(c_, prevPV ? prevPV->m : nullptr, max_history, plane_tol, threshold, mu_floor,
+                                        &rec),
+          "mcpt_adaptive_select_temporal");
+    return rec;
+  }
+  // adaptive_run whose selects are adaptive_select_temporal: one host wait for the whole run
+  mcpt_adaptive_run_t adaptive_run_temporal(const Camera& cam, int first_pass, int n_passes, int rounds,
+                                            int check_every, float threshold, const GLMat4* prevPV, float date,
+                                            int bounces, float refract_ind,
+                                            std::vector<mcpt_adaptive_temporal_t>& records,
+                                            int variant = MCPT_MONTECARLO, int max_history = kTemporalMaxHistory,
+                                            float plane_tol = kTemporalPlaneTol, float mu_floor = kErrorMuFloor) {
+    mcpt_adaptive_run_t run;
+    records.assign((size_t)(rounds > 0 ? rounds : 1), mcpt_adaptive_temporal_t{});
+    check(mcpt_adaptive_run_temporal(c_, cam.invPV.m, cam.invV.m, first_pass, n_passes, rounds, check_every, threshold,
+                                     mu_floor, prevPV ? prevPV->m : nullptr, max_history, plane_tol, date, bounces,
+                                     refract_ind, variant, records.data(), (int)records.size(), &run),
+          "mcpt_adaptive_run_temporal");
+    records.resize((size_t)run.selects_run);
+    return run;
+  }
   // Render passes first_pass, first_pass + 1, ... in calls of `batch` passes until the mean relative
   // error is at most target_error or max_passes are rendered; the convergence is queried after every
   // check_every calls (and at the cap), the calls in between are queued without a wait.  Begins a

@@ -29,8 +29,11 @@
 //       (render until the DENOISED image meets the error: mcpt_adaptive_select_filtered; one device)
 //   mcpt_render --scene 6 --spp 4 --frames 100 --orbit-deg 1 --temporal --denoise-variance --out orbit.png
 //       (an orbit of 100 cameras, 4 spp each, every frame reprojected into the next: orbit_000.png ...)
+//   mcpt_render --scene 6 --spp 16 --chunk 2 --frames 100 --orbit-deg 1 --temporal --temporal-target 0.05
+//       --denoise-variance --out orbit.png   (the same orbit, up to 16 spp where the history cannot carry a block)
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -63,6 +66,8 @@ struct Args {
   int frames = 0;             // --frames N: N cameras, one image each (0: off; with --temporal alone: 1)
   float orbit_deg = 0.0f;     // --orbit-deg D: frame k's world is turned k * D degrees about the up axis
   int temporal = -1;          // --temporal [max_history]: every frame is reprojected into the next (-1: off)
+  double temporal_target = 0.0;   // --temporal-target E: with --temporal, a frame's 8x8 blocks stop once the blend the
+                              // history would give them meets E (--spp: the cap, --chunk: a round's passes; 0: off)
 };
 
 bool parse_list(const char* v, std::vector<int>& out) {
@@ -113,6 +118,9 @@ void usage() {
                "                   [--queue-rounds K]   (with --adaptive, one device: up to K chunks and their selects\n"
                "                                         are queued on the device per host wait, 1..256; the same\n"
                "                                         image; a checkpoint is written after each run)\n"
+               "                   [--temporal-target E]   (with --temporal: per frame rounds of --chunk passes, --spp the\n"
+               "                                   cap, for the 8x8 blocks whose blend with the history does not meet\n"
+               "                                   E yet; queued on the device, --queue-rounds K rounds per wait)\n"
                "                   [--temporal [max_history]] [--frames N] [--orbit-deg D]   (N cameras, frame k with the\n"
                "                                   world turned k * D degrees about the up axis, --spp passes each in\n"
                "                                   two batches or more; every frame's result is reprojected into the\n"
@@ -193,6 +201,10 @@ bool parse(int argc, char** argv, Args& a) {
       a.target_error = std::atof(v);
       if (!(a.target_error > 0.0)) return false;
     }
+    else if (k == "--temporal-target") {
+      a.temporal_target = std::atof(v);
+      if (!(a.temporal_target > 0.0) || !std::isfinite(a.temporal_target)) return false;
+    }
     else if (k == "--queue-rounds") {
       a.queue_rounds = std::atoi(v);
       if (a.queue_rounds < 1 || a.queue_rounds > MCPT_ADAPTIVE_RUN_MAX_ROUNDS) return false;
@@ -223,6 +235,8 @@ bool parse(int argc, char** argv, Args& a) {
   // (first: these refusals carry a message)
   if (a.temporal < 0 && (a.frames > 0 || a.orbit_deg != 0.0f))
     return refuse("--frames and --orbit-deg move the camera of a --temporal render: give --temporal");
+  if (a.temporal < 0 && a.temporal_target > 0.0)
+    return refuse("--temporal-target is the stopping rule of a --temporal render: give --temporal");
   if (a.temporal >= 0) {
     if (a.frames == 0) a.frames = 1;
     if (!a.devices.empty()) return refuse("--temporal keeps its history on one device: not with --devices (not built)");
@@ -235,6 +249,8 @@ bool parse(int argc, char** argv, Args& a) {
     if (!a.aov.empty()) return refuse("--temporal writes its frames only: not with --aov (not built)");
     if (a.denoise_variance < 0) return refuse("--temporal filters with the variance filter: give --denoise-variance [N]");
     if (a.spp < 2) return refuse("--temporal needs two batches per frame for its error map: --spp 2 or more");
+    if (a.temporal_target > 0.0 && (a.chunk <= 0 || a.spp / a.chunk < 2))
+      return refuse("--temporal-target renders rounds of --chunk passes up to --spp: two rounds or more");
   }
   if (!a.devices.empty() && (!a.checkpoint.empty() || !a.resume.empty())) return false;   // one device only
   // (stopping N host threads on a merged record is not built: a uniform --target-error is one device's)
@@ -245,7 +261,7 @@ bool parse(int argc, char** argv, Args& a) {
   if (!a.devices.empty() && a.adaptive && a.noise_filter()) return false;
   if ((a.denoise >= 0) + (a.denoise_guided >= 0) + (a.denoise_variance >= 0) > 1) return false;   // one filter
   if (a.adaptive && !(a.target_error > 0.0)) return false;   // adaptive sampling needs its threshold
-  if (a.queue_rounds > 0) {
+  if (a.queue_rounds > 0 && !(a.temporal_target > 0.0)) {
     if (!a.adaptive) return refuse("--queue-rounds queues the chunks of --adaptive --target-error E: give both");
     if (!a.devices.empty()) return refuse("--queue-rounds runs on one device: not with --devices");
   }
@@ -287,6 +303,8 @@ int run_temporal(const Args& a, mcpt::BVH_GPU_Scene& scene, int W, int H) {
   const std::string png = a.png.empty() && a.pfm.empty() ? "out.png" : a.png;
   double kernel_ms = 0.0, temporal_ms = 0.0, filter_ms = 0.0;
   mcpt_temporal_t rec{};
+  mcpt_adaptive_temporal_t sel{};   // --temporal-target: the frame's last select
+  double samples = 0.0;             // mean samples per pixel, summed over the frames
   mcpt::GLMat4 prev;
   int pass = a.first_pass;
   double mean = 0.0;
@@ -295,15 +313,38 @@ int run_temporal(const Args& a, mcpt::BVH_GPU_Scene& scene, int W, int H) {
     const mcpt::Camera cam = mcpt::Camera::orbit(a.width, a.height, (float)k * a.orbit_deg);
     r.clear_accum();
     r.stats_begin();
-    for (int done = 0; done < a.spp; done += batch) {
-      const int n = std::min(batch, a.spp - done);
-      r.render(cam, pass, n, a.date, a.bounces, a.ior, a.variant);
-      kernel_ms += r.last_render_ms();
-      pass += n;
+    if (a.temporal_target > 0.0) {
+      // the adaptive form of the frame loop (mcpt.h): rounds of --chunk passes for the blocks the
+      // history cannot carry, as queued runs of up to --queue-rounds rounds (none given: one run)
+      r.adaptive_begin(0);
+      r.render_guides(cam);
+      const int rounds = std::min(a.spp / a.chunk, MCPT_ADAPTIVE_RUN_MAX_ROUNDS);
+      std::vector<mcpt_adaptive_temporal_t> recs;
+      for (int done = 0; done < rounds;) {
+        const int q = std::min(a.queue_rounds > 0 ? a.queue_rounds : rounds, rounds - done);
+        const mcpt_adaptive_run_t run =
+            r.adaptive_run_temporal(cam, pass + done * a.chunk, a.chunk, q, 1, (float)a.temporal_target,
+                                    k ? &prev : nullptr, a.date, a.bounces, a.ior, recs, a.variant, a.temporal);
+        kernel_ms += run.device_ms;
+        done += run.rounds_run;
+        if (!recs.empty()) sel = recs.back();
+        if (run.rounds_run < q || (!recs.empty() && sel.raw.n_active_blocks == 0)) break;
+      }
+      samples += (double)sel.raw.samples / (double)(sel.raw.n_px > 0 ? sel.raw.n_px : 1);
+      pass += a.spp;   // (pass ids never repeat, whatever the frame rendered)
+      rec = r.temporal_accumulate_resolved(k ? &prev : nullptr, a.temporal);
+    } else {
+      for (int done = 0; done < a.spp; done += batch) {
+        const int n = std::min(batch, a.spp - done);
+        r.render(cam, pass, n, a.date, a.bounces, a.ior, a.variant);
+        kernel_ms += r.last_render_ms();
+        pass += n;
+      }
+      samples += (double)a.spp;
+      r.convergence(kMapThreshold);
+      r.render_guides(cam);
+      rec = r.temporal_accumulate(k ? &prev : nullptr, a.temporal);
     }
-    r.convergence(kMapThreshold);
-    r.render_guides(cam);
-    rec = r.temporal_accumulate(k ? &prev : nullptr, a.temporal);
     const std::vector<float> img = r.denoise_temporal(a.denoise_variance);
     float am = 0.0f, cm = 0.0f, gm = 0.0f, fm = 0.0f;
     r.last_temporal_ms(am, cm);
@@ -322,10 +363,11 @@ int run_temporal(const Args& a, mcpt::BVH_GPU_Scene& scene, int W, int H) {
               "\"orbit_deg\": %g, \"temporal\": %d, \"denoise_variance\": %d, \"kernel_ms\": %.3f, \"temporal_ms\": %.3f, "
               "\"filter_ms\": %.3f, \"wall_ms\": %.3f, \"mean\": %.6f, \"n_history\": %lld, \"n_new\": %lld, "
               "\"n_miss\": %lld, \"n_offscreen\": %lld, \"n_rejected\": %lld, \"max_len\": %d, \"mean_len\": %.4f, "
-              "\"passes\": %d}\n",
+              "\"passes\": %d, \"temporal_target\": %g, \"mean_spp\": %.4f, \"active_blocks\": %lld}\n",
               a.scene, W, H, a.spp, a.bounces, a.frames, a.orbit_deg, a.temporal, a.denoise_variance, kernel_ms, temporal_ms,
               filter_ms, wall_ms, mean, rec.n_history, rec.n_new, rec.n_miss, rec.n_offscreen, rec.n_rejected, rec.max_len,
-              rec.n_px > 0 ? (double)rec.sum_len / (double)rec.n_px : 0.0, pass - a.first_pass);
+              rec.n_px > 0 ? (double)rec.sum_len / (double)rec.n_px : 0.0, pass - a.first_pass, a.temporal_target,
+              samples / (double)(a.frames > 0 ? a.frames : 1), (long long)sel.raw.n_active_blocks);
   return 0;
 }
 

@@ -412,33 +412,70 @@ int mcpt_adaptive_info(mcpt_ctx* c, int* on, long long* n_active, long long* n_b
 // half and its host half.
 // the filtered rule's own arguments; SelectRule::f null: mcpt_adaptive_select's rule on the raw error
 struct RunFilter { float raw_cap; int iterations; float k_color, sigma_plane; };
-struct SelectRule { float threshold, mu_floor; const RunFilter* f; };
+// the temporal rule's own arguments: mcpt_temporal_accumulate_resolved's
+struct RunTemporal { const float* prevPV16; int max_history; float plane_tol; };
+struct SelectRule { float threshold, mu_floor; const RunFilter* f; const RunTemporal* t = nullptr; };
 // where a select's results go on the device: the rule kernel's partial records, the filtered rule's
-// step C's (null without a filter) and a slot that receives a copy of the list's length (null: none)
+// step C's or the temporal rule's step T's (null for the raw rule) and a slot that receives a copy of
+// the list's length (null: none)
 struct SelectDest { unsigned long long *rec, *rec_f; int* len; };
+// the records a select's caller receives: raw always, one of the others with its rule
+struct SelectOut { mcpt_adaptive_t* raw; mcpt_adaptive_filtered_t* filtered; mcpt_adaptive_temporal_t* temporal; };
+
+// An accumulate's launch parameters from the context (mcpt_temporal_accumulate*, the temporal select's
+// dry run): the current frame, the history's current set as input and the other set as output, the
+// previous camera; its preconditions have been checked
+static mcpt::TemporalParams temporal_params(const mcpt_ctx* c, const float2* emap, const float* prevPV16,
+                                            int max_history, float plane_tol) {
+  const int in = c->tp_cur, to = in ^ 1;
+  const bool empty = c->tp_frames == 0;
+  mcpt::TemporalParams p;
+  std::memset(&p, 0, sizeof(p));
+  p.accum = c->d_accum; p.emap = emap; p.guide = c->d_guide;
+  p.hc_in = c->d_tp_c[in]; p.hl_in = c->d_tp_len[in]; p.hg_in = c->d_tp_g[c->tp_copy ? 0 : in];
+  p.hc_out = c->d_tp_c[to]; p.hl_out = c->d_tp_len[to]; p.hg_out = c->tp_copy ? nullptr : c->d_tp_g[to];
+  p.rec = c->d_tp_rec;
+  p.W = c->W; p.H = c->H; p.nb = (float)c->pass_count;
+  p.counts = count_source(c);
+  p.max_history = max_history; p.plane_tol = plane_tol; p.empty = empty ? 1 : 0;
+  if (!empty) std::memcpy(p.M, prevPV16, sizeof(p.M));
+  return p;
+}
 
 // The rule's preconditions, behind the caller's own MCPT_ERR_NO_ADAPTIVE.  single: one select now
 // (mcpt_adaptive_select*), which needs passes and two batches on entry; a queued run's schedule
 // places its selects behind both.
 static int check_select_rule(const mcpt_ctx* c, const SelectRule& r, bool single, const char* who) {
   const RunFilter* f = r.f;
-  if (!positive_finite({r.threshold, r.mu_floor, f ? f->raw_cap : 1.0f, f ? f->k_color : 1.0f, f ? f->sigma_plane : 1.0f}))
+  const RunTemporal* t = r.t;
+  if (t && !c->tp_on) return refuse(MCPT_ERR_NO_TEMPORAL, who, "temporal mode is off (mcpt_temporal_begin)");
+  if (!positive_finite({r.threshold, r.mu_floor, f ? f->raw_cap : 1.0f, f ? f->k_color : 1.0f, f ? f->sigma_plane : 1.0f,
+                        t ? t->plane_tol : 1.0f}))
     return refuse(MCPT_ERR_INVALID_ARG, who,
-                  !single ? "threshold, mu_floor and the filter's widths must be positive and finite"
-                  : f     ? "threshold, raw_cap, mu_floor, k_color and sigma_plane must be positive and finite"
-                          : "threshold and mu_floor must be positive and finite");
-  if (f) {
-    if (f->iterations < 0 || f->iterations > 8) return refuse(MCPT_ERR_INVALID_ARG, who, "iterations not in 0..8");
+                  t         ? "threshold, mu_floor and plane_tol must be positive and finite"
+                  : !single ? "threshold, mu_floor and the filter's widths must be positive and finite"
+                  : f       ? "threshold, raw_cap, mu_floor, k_color and sigma_plane must be positive and finite"
+                            : "threshold and mu_floor must be positive and finite");
+  if (f && (f->iterations < 0 || f->iterations > 8)) return refuse(MCPT_ERR_INVALID_ARG, who, "iterations not in 0..8");
+  if (t) {
+    if (t->max_history < 1 || t->max_history > MCPT_TEMPORAL_MAX_HISTORY)
+      return refuse(MCPT_ERR_INVALID_ARG, who, "max_history not in 1..65535");
+    if (c->tp_frames > 0 && !t->prevPV16)
+      return refuse(MCPT_ERR_INVALID_ARG, who, "the history needs the previous camera's P*V");
+  }
+  if (f || t) {
     if (!plan::is_full_frame(c->rows, c->H))
-      return refuse(MCPT_ERR_INVALID_ARG, who, "needs a full-frame target (a shard is filtered after its gather)");
-    // (the filter would read a gathered frame's counts and map, the rule this window's)
+      return refuse(MCPT_ERR_INVALID_ARG, who,
+                    f ? "needs a full-frame target (a shard is filtered after its gather)"
+                      : "needs a full-frame target (gather the shards first)");
+    // (the filter or the dry run would read a gathered frame's counts and map, the rule this window's)
     if (c->plane_valid || c->emap_plane_valid)
       return refuse(MCPT_ERR_INVALID_ARG, who, "the context holds a gathered frame's counts or error map");
     if (single && c->pass_count <= 0) return refuse(MCPT_ERR_INVALID_ARG, who, "the accumulator holds no passes");
   }
   if (!c->stats_on) return refuse(MCPT_ERR_NO_STATS, who, "statistics are off (mcpt_stats_begin)");
   if (single && c->stats_batches < 2) return refuse(MCPT_ERR_NO_STATS, who, "needs two batches or more");
-  if (f && !c->guides_valid) return refuse(MCPT_ERR_NO_GUIDES, who, "no guides rendered for this target and scene");
+  if ((f || t) && !c->guides_valid) return refuse(MCPT_ERR_NO_GUIDES, who, "no guides rendered for this target and scene");
   return MCPT_OK;
 }
 
@@ -455,17 +492,23 @@ static int ensure_select(mcpt_ctx* c, const RunFilter* f) {
 // The enqueue half, no host wait.  The raw rule: select_kernel<true> (the map, the record, the flags),
 // then the scan.  The filtered rule: step A select_kernel<false>, the map and the raw
 // record, no flag changes; step B denoise_run's resolved variance form on that map; step C
-// filtered_select_kernel on the filter's result, then the scan.  timed: events [0, 1] around the raw
-// rule and its scan, for the filtered rule [0, 1] around step A and [4, 5] around step C and the scan
-// (mcpt_last_adaptive_ms); every precondition has been checked.
+// filtered_select_kernel on the filter's result, then the scan.  The temporal rule:
+// step A, step T temporal_select_kernel on that map and the history, then the scan.  timed: events
+// [0, 1] around the raw rule (the temporal rule's steps A and T) and its scan, for the filtered rule
+// [0, 1] around step A and [4, 5] around step C and the scan (mcpt_last_adaptive_ms); every
+// precondition has been checked.
 static int enqueue_select(mcpt_ctx* c, const SelectRule& r, const SelectDest& d, bool timed) {
   const RunFilter* f = r.f;
   const mcpt::AdaptiveTarget t = adaptive_target(c);
   int* d_count = c->d_ad_list + c->ad_n_blocks;
   if (timed) HIP_OR_RETURN(hipEventRecord(c->ad_ev[0], c->stream));
   HIP_OR_RETURN(mcpt_launch_adaptive_select(t, c->d_stats, c->d_emap, c->stats_passes, c->stats_batches, r.mu_floor,
-                                            r.threshold, c->ad_min_passes, f == nullptr, d.rec, c->stream));
+                                            r.threshold, c->ad_min_passes, !f && !r.t, d.rec, c->stream));
   c->emap_valid = true;
+  if (r.t)   // step T: the dry run of the resolved accumulate on the map step A wrote (the own window's)
+    HIP_OR_RETURN(mcpt_launch_temporal_select(
+        t, temporal_params(c, c->d_emap, r.t->prevPV16, r.t->max_history, r.t->plane_tol), r.mu_floor, r.threshold,
+        c->ad_min_passes, d.rec_f, c->stream));
   if (f) {
     if (timed) HIP_OR_RETURN(hipEventRecord(c->ad_ev[1], c->stream));
     FilterForm form = kResolvedVariance;
@@ -485,49 +528,67 @@ static int enqueue_select(mcpt_ctx* c, const SelectRule& r, const SelectDest& d,
   return MCPT_OK;
 }
 
-// The host half, from one select's reduced records (h; hf: step C's, read when `filtered` is given) and
-// its list length: the length must be the flagged blocks the retiring kernel counted (its word 4);
-// then the context's list length and the caller's record.
+// The host half, from one select's reduced records (h; hf: the rule's second kernel's, step C's or
+// step T's, read when o.filtered or o.temporal is given) and its list length: the length must be the
+// flagged blocks the retiring kernel counted (its word 4); then the context's list length and the
+// caller's record.
 static int finish_select(mcpt_ctx* c, const unsigned long long* h, const unsigned long long* hf, int n_list,
-                         const char* who, mcpt_adaptive_t* raw, mcpt_adaptive_filtered_t* filtered) {
-  if (n_list < 0 || n_list > c->ad_n_blocks || (unsigned long long)n_list != (filtered ? hf : h)[4])
+                         const char* who, const SelectOut& o) {
+  if (n_list < 0 || n_list > c->ad_n_blocks || (unsigned long long)n_list != (o.filtered || o.temporal ? hf : h)[4])
     return refuse(MCPT_ERR_HIP, who, "the active list and the block flags disagree");
   c->ad_n_list = n_list;
-  fill_frame_record(c, h, raw);
-  raw->n_active_blocks = n_list;
-  raw->n_blocks = c->ad_n_blocks;
-  raw->samples = (long long)h[3];
-  if (filtered) fill_filtered_record(c, hf, filtered);
+  fill_frame_record(c, h, o.raw);
+  o.raw->n_active_blocks = n_list;
+  o.raw->n_blocks = c->ad_n_blocks;
+  o.raw->samples = (long long)h[3];
+  if (o.filtered) fill_filtered_record(c, hf, o.filtered);
+  if (o.temporal) {   // step T's record: over the pixels of the blocks active on entry
+    mcpt_adaptive_temporal_t* t = o.temporal;
+    t->n_px_t = (long long)hf[3];
+    t->n_above_t = (long long)hf[0];
+    t->sum_qt = hf[1];
+    const unsigned mb = (unsigned)(hf[2] & 0xffffffffull);
+    std::memcpy(&t->max_rt, &mb, sizeof(float));
+    t->mean_rt = t->n_px_t > 0 ? (double)hf[1] / 65536.0 / (double)t->n_px_t : 0.0;
+    t->n_history = (long long)hf[5];
+  }
   return MCPT_OK;
 }
 
 // one select now, into d_conv (and d_conv_f), one wait for its records.  Every precondition is checked
 // before the enqueue, so a refusal leaves the flags, the map and the result buffers alone.
-static int select_once(mcpt_ctx* c, const SelectRule& rule, const char* who, mcpt_adaptive_t* raw,
-                       mcpt_adaptive_filtered_t* filtered) {
+static int select_once(mcpt_ctx* c, const SelectRule& rule, const char* who, const SelectOut& o) {
   if (!c->ad_on) return refuse(MCPT_ERR_NO_ADAPTIVE, who, "adaptive mode is off (mcpt_adaptive_begin)");
   OK_OR_RETURN(check_select_rule(c, rule, true, who));
   HIP_OR_RETURN(hipSetDevice(c->device));
   OK_OR_RETURN(ensure_select(c, rule.f));
-  if (rule.f && !c->d_conv_f) HIP_OR_RETURN(hipMalloc(&c->d_conv_f, sizeof(unsigned long long) * mcpt::kStatsRecWords));
-  const SelectDest dest = {c->d_conv, rule.f ? c->d_conv_f : nullptr, nullptr};
+  const bool two = rule.f || rule.t;   // the rule runs a second reducing kernel
+  if (two && !c->d_conv_f) HIP_OR_RETURN(hipMalloc(&c->d_conv_f, sizeof(unsigned long long) * mcpt::kStatsRecWords));
+  const SelectDest dest = {c->d_conv, two ? c->d_conv_f : nullptr, nullptr};
   OK_OR_RETURN(enqueue_select(c, rule, dest, true));
-  unsigned long long h[5] = {0, 0, 0, 0, 0}, hf[5] = {0, 0, 0, 0, 0};
+  unsigned long long h[6] = {0, 0, 0, 0, 0, 0}, hf[6] = {0, 0, 0, 0, 0, 0};
   int n_list = 0;
-  OK_OR_RETURN(read_stats_records(c, 5, 2, dest.rec, h, dest.rec_f, hf, c->d_ad_list + c->ad_n_blocks, &n_list));
-  return finish_select(c, h, hf, n_list, who, raw, filtered);
+  OK_OR_RETURN(read_stats_records(c, 6, 2, dest.rec, h, dest.rec_f, hf, c->d_ad_list + c->ad_n_blocks, &n_list));
+  return finish_select(c, h, hf, n_list, who, o);
 }
 
 int mcpt_adaptive_select(mcpt_ctx* c, float threshold, float mu_floor, mcpt_adaptive_t* out) {
   if (!c || !out) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
-  return select_once(c, {threshold, mu_floor, nullptr}, "mcpt_adaptive_select", out, nullptr);
+  return select_once(c, {threshold, mu_floor, nullptr}, "mcpt_adaptive_select", {out, nullptr, nullptr});
 }
 
 int mcpt_adaptive_select_filtered(mcpt_ctx* c, float threshold, float raw_cap, float mu_floor, int iterations,
                                   float k_color, float sigma_plane, mcpt_adaptive_filtered_t* out) {
   if (!c || !out) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
   const RunFilter f = {raw_cap, iterations, k_color, sigma_plane};
-  return select_once(c, {threshold, mu_floor, &f}, "mcpt_adaptive_select_filtered", &out->raw, out);
+  return select_once(c, {threshold, mu_floor, &f}, "mcpt_adaptive_select_filtered", {&out->raw, out, nullptr});
+}
+
+int mcpt_adaptive_select_temporal(mcpt_ctx* c, const float* prevPV16, int max_history, float plane_tol, float threshold,
+                                  float mu_floor, mcpt_adaptive_temporal_t* out) {
+  if (!c || !out) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  const RunTemporal t = {prevPV16, max_history, plane_tol};
+  return select_once(c, {threshold, mu_floor, nullptr, &t}, "mcpt_adaptive_select_temporal", {&out->raw, nullptr, out});
 }
 
 int mcpt_read_active_blocks(mcpt_ctx* c, int* ids, int capacity, int* n) {
@@ -623,13 +684,16 @@ int mcpt_render_adaptive(mcpt_ctx* c, const float* invPV, const float* invV, int
 
 // ---- queued adaptive runs: `rounds` rounds of {the active blocks' passes, the
 // statistics' batch, on the schedule's rounds a select and the scan} on the stream, every list length
-// read on the device, one wait at the end for all the records.  f: the filtered rule's arguments
-// (null: mcpt_adaptive_select's rule); records: mcpt_adaptive_t or, with f, mcpt_adaptive_filtered_t.
+// read on the device, one wait at the end for all the records.  f: the filtered rule's arguments, t:
+// the temporal rule's (both null: mcpt_adaptive_select's rule); records: mcpt_adaptive_t or, with f,
+// mcpt_adaptive_filtered_t, with t, mcpt_adaptive_temporal_t.
 static int adaptive_run(mcpt_ctx* c, const float* invPV, const float* invV, int first_pass, int n_passes, int rounds,
                         int check_every, float threshold, float mu_floor, float date, int bounces, float refract_ind,
-                        int variant, const RunFilter* f, void* records, int records_capacity, mcpt_adaptive_run_t* out) {
-  const char* who = f ? "mcpt_adaptive_run_filtered" : "mcpt_adaptive_run";
-  const SelectRule rule = {threshold, mu_floor, f};
+                        int variant, const RunFilter* f, const RunTemporal* t, void* records, int records_capacity,
+                        mcpt_adaptive_run_t* out) {
+  const char* who = t ? "mcpt_adaptive_run_temporal" : f ? "mcpt_adaptive_run_filtered" : "mcpt_adaptive_run";
+  const SelectRule rule = {threshold, mu_floor, f, t};
+  const bool two = f || t;   // the rule runs a second reducing kernel (step C, step T): the second ring
   // mcpt_render_adaptive's checks, then the select's, then the run's own: before anything is enqueued
   OK_OR_RETURN(check_render_adaptive(c, invPV, invV, n_passes, variant, who));
   if (!out) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
@@ -653,7 +717,7 @@ static int adaptive_run(mcpt_ctx* c, const float* invPV, const float* invV, int 
   const size_t ring_bytes = sizeof(unsigned long long) * mcpt::kStatsRecWords * (size_t)plan::kAdaptiveRunMaxRounds;
   if (!c->d_run_rec) HIP_OR_RETURN(hipMalloc(&c->d_run_rec, ring_bytes));
   if (!c->d_run_len) HIP_OR_RETURN(hipMalloc(&c->d_run_len, sizeof(int) * (size_t)plan::kAdaptiveRunMaxRounds));
-  if (f && !c->d_run_rec_f) HIP_OR_RETURN(hipMalloc(&c->d_run_rec_f, ring_bytes));
+  if (two && !c->d_run_rec_f) HIP_OR_RETURN(hipMalloc(&c->d_run_rec_f, ring_bytes));
   {   // the segment-sum buffer of the run's largest sub-launch now: growing it waits for the stream
     mcpt::RenderParams p;
     const long long max_seg = adaptive_round_params(c, invPV, invV, true, p);
@@ -682,16 +746,16 @@ static int adaptive_run(mcpt_ctx* c, const float* invPV, const float* invV, int 
                                 true, i == rounds - 1));
     if (!plan::run_round_selects(i, rounds, check_every, batches_in)) continue;
     const size_t slot = (size_t)k * mcpt::kStatsRecWords;   // the select's own slices of the rings
-    const SelectDest dest = {c->d_run_rec + slot, f ? c->d_run_rec_f + slot : nullptr, c->d_run_len + k};
+    const SelectDest dest = {c->d_run_rec + slot, two ? c->d_run_rec_f + slot : nullptr, c->d_run_len + k};
     OK_OR_RETURN(enqueue_select(c, rule, dest, k == n_sel - 1));   // (events around the run's last select only)
     sel_round[k++] = i;
   }
   HIP_OR_RETURN(hipEventRecord(c->run_ev[1], c->stream));
-  std::vector<unsigned long long> part((size_t)k * mcpt::kStatsRecWords), part_f(f ? part.size() : 0);
+  std::vector<unsigned long long> part((size_t)k * mcpt::kStatsRecWords), part_f(two ? part.size() : 0);
   std::vector<int> len((size_t)k);
   if (k > 0) {
     HIP_OR_RETURN(hipMemcpyAsync(part.data(), c->d_run_rec, part.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-    if (f)
+    if (two)
       HIP_OR_RETURN(hipMemcpyAsync(part_f.data(), c->d_run_rec_f, part_f.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     HIP_OR_RETURN(hipMemcpyAsync(len.data(), c->d_run_len, len.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
   }
@@ -710,12 +774,13 @@ static int adaptive_run(mcpt_ctx* c, const float* invPV, const float* invV, int 
   out->passes_run = (long long)o.rounds_run * n_passes;
   int status = MCPT_OK;
   for (int s = 0; s < o.selects_run; ++s) {
-    unsigned long long h[5] = {0, 0, 0, 0, 0}, hf[5] = {0, 0, 0, 0, 0};
-    reduce_stats_records(part.data() + (size_t)s * mcpt::kStatsRecWords, 5, 2, h);
-    if (f) reduce_stats_records(part_f.data() + (size_t)s * mcpt::kStatsRecWords, 5, 2, hf);
+    unsigned long long h[6] = {0, 0, 0, 0, 0, 0}, hf[6] = {0, 0, 0, 0, 0, 0};
+    reduce_stats_records(part.data() + (size_t)s * mcpt::kStatsRecWords, 6, 2, h);
+    if (two) reduce_stats_records(part_f.data() + (size_t)s * mcpt::kStatsRecWords, 6, 2, hf);
     mcpt_adaptive_filtered_t* filtered = f ? &static_cast<mcpt_adaptive_filtered_t*>(records)[s] : nullptr;
-    mcpt_adaptive_t* raw = f ? &filtered->raw : &static_cast<mcpt_adaptive_t*>(records)[s];
-    status = finish_select(c, h, hf, len[(size_t)s], who, raw, filtered);
+    mcpt_adaptive_temporal_t* temporal = t ? &static_cast<mcpt_adaptive_temporal_t*>(records)[s] : nullptr;
+    mcpt_adaptive_t* raw = f ? &filtered->raw : t ? &temporal->raw : &static_cast<mcpt_adaptive_t*>(records)[s];
+    status = finish_select(c, h, hf, len[(size_t)s], who, {raw, filtered, temporal});
     if (status != MCPT_OK) break;
     raw->passes = window_in + (long long)(sel_round[s] + 1) * n_passes;   // (the window as that select saw it)
     raw->batches = batches_in + sel_round[s] + 1;
@@ -727,7 +792,7 @@ int mcpt_adaptive_run(mcpt_ctx* c, const float* invPV, const float* invV, int fi
                       int check_every, float threshold, float mu_floor, float date, int bounces, float refract_ind,
                       int variant, mcpt_adaptive_t* records, int records_capacity, mcpt_adaptive_run_t* out) {
   return adaptive_run(c, invPV, invV, first_pass, n_passes, rounds, check_every, threshold, mu_floor, date, bounces,
-                      refract_ind, variant, nullptr, records, records_capacity, out);
+                      refract_ind, variant, nullptr, nullptr, records, records_capacity, out);
 }
 
 int mcpt_adaptive_run_filtered(mcpt_ctx* c, const float* invPV, const float* invV, int first_pass, int n_passes,
@@ -737,7 +802,16 @@ int mcpt_adaptive_run_filtered(mcpt_ctx* c, const float* invPV, const float* inv
                                mcpt_adaptive_run_t* out) {
   const RunFilter f = {raw_cap, iterations, k_color, sigma_plane};
   return adaptive_run(c, invPV, invV, first_pass, n_passes, rounds, check_every, threshold, mu_floor, date, bounces,
-                      refract_ind, variant, &f, records, records_capacity, out);
+                      refract_ind, variant, &f, nullptr, records, records_capacity, out);
+}
+
+int mcpt_adaptive_run_temporal(mcpt_ctx* c, const float* invPV, const float* invV, int first_pass, int n_passes,
+                               int rounds, int check_every, float threshold, float mu_floor, const float* prevPV16,
+                               int max_history, float plane_tol, float date, int bounces, float refract_ind, int variant,
+                               mcpt_adaptive_temporal_t* records, int records_capacity, mcpt_adaptive_run_t* out) {
+  const RunTemporal t = {prevPV16, max_history, plane_tol};
+  return adaptive_run(c, invPV, invV, first_pass, n_passes, rounds, check_every, threshold, mu_floor, date, bounces,
+                      refract_ind, variant, nullptr, &t, records, records_capacity, out);
 }
 
 // every local pixel's sample count (mcpt_read_sample_counts) or, resolved, its accum / (float)count
@@ -935,56 +1009,46 @@ int mcpt_temporal_info(mcpt_ctx* c, int* on, int* history_valid, long long* fram
   return MCPT_OK;
 }
 
-int mcpt_temporal_accumulate(mcpt_ctx* c, const float* prevPV16, int max_history, float plane_tol,
-                             mcpt_temporal_t* out) {
+// one accumulate behind mcpt_temporal_accumulate and, resolved, mcpt_temporal_accumulate_resolved
+// (DESIGN.md §3.10.1): the current colour accum / (float)count with every pixel's own count, retired
+// blocks allowed
+static int temporal_accumulate(mcpt_ctx* c, const float* prevPV16, int max_history, float plane_tol,
+                               mcpt_temporal_t* out, bool resolved, const char* who) {
   if (!c) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
-  if (!c->tp_on) return set_err(MCPT_ERR_NO_TEMPORAL, "mcpt_temporal_accumulate: temporal mode is off (mcpt_temporal_begin)");
+  if (!c->tp_on) return refuse(MCPT_ERR_NO_TEMPORAL, who, "temporal mode is off (mcpt_temporal_begin)");
+  if (resolved && !c->ad_on) return refuse(MCPT_ERR_NO_ADAPTIVE, who, "adaptive mode is off (mcpt_adaptive_begin)");
   if (!out) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
   if (max_history < 1 || max_history > MCPT_TEMPORAL_MAX_HISTORY)
-    return set_err(MCPT_ERR_INVALID_ARG, "mcpt_temporal_accumulate: max_history not in 1..65535");
-  if (!positive_finite({plane_tol}))
-    return set_err(MCPT_ERR_INVALID_ARG, "mcpt_temporal_accumulate: plane_tol must be positive and finite");
+    return refuse(MCPT_ERR_INVALID_ARG, who, "max_history not in 1..65535");
+  if (!positive_finite({plane_tol})) return refuse(MCPT_ERR_INVALID_ARG, who, "plane_tol must be positive and finite");
   const bool empty = c->tp_frames == 0;
-  if (!empty && !prevPV16)
-    return set_err(MCPT_ERR_INVALID_ARG, "mcpt_temporal_accumulate: the history needs the previous camera's P*V");
+  if (!empty && !prevPV16) return refuse(MCPT_ERR_INVALID_ARG, who, "the history needs the previous camera's P*V");
   if (!plan::is_full_frame(c->rows, c->H))
-    return set_err(MCPT_ERR_INVALID_ARG, "mcpt_temporal_accumulate: needs a full-frame target (gather the shards first)");
-  if (c->pass_count <= 0)
-    return set_err(MCPT_ERR_INVALID_ARG, "mcpt_temporal_accumulate: the accumulator holds no passes");
-  if (c->plane_valid)
-    return set_err(MCPT_ERR_INVALID_ARG, "mcpt_temporal_accumulate: the context holds a gathered frame's counts");
-  if (c->ad_on && c->ad_n_list < c->ad_n_blocks)
-    return set_err(MCPT_ERR_INVALID_ARG, "mcpt_temporal_accumulate: adaptive mode has retired blocks (per-pixel sample counts)");
+    return refuse(MCPT_ERR_INVALID_ARG, who, "needs a full-frame target (gather the shards first)");
+  if (c->pass_count <= 0) return refuse(MCPT_ERR_INVALID_ARG, who, "the accumulator holds no passes");
+  if (c->plane_valid) return refuse(MCPT_ERR_INVALID_ARG, who, "the context holds a gathered frame's counts");
+  if (!resolved && c->ad_on && c->ad_n_list < c->ad_n_blocks)
+    return refuse(MCPT_ERR_INVALID_ARG, who, "adaptive mode has retired blocks (per-pixel sample counts)");
   const float2* emap = held_error_map(c);
   if (error_map_source(c) == 0)
-    return set_err(MCPT_ERR_NO_STATS, "mcpt_temporal_accumulate: no error map (mcpt_convergence) of the current statistics");
-  if (!c->guides_valid)
-    return set_err(MCPT_ERR_NO_GUIDES, "mcpt_temporal_accumulate: no guides rendered for this target and scene");
+    return refuse(MCPT_ERR_NO_STATS, who, "no error map (mcpt_convergence) of the current statistics");
+  if (!c->guides_valid) return refuse(MCPT_ERR_NO_GUIDES, who, "no guides rendered for this target and scene");
   HIP_OR_RETURN(hipSetDevice(c->device));
   HIP_OR_RETURN(ensure_timing_events(c->tp_ev, 3));
-  const int in = c->tp_cur, to = in ^ 1;
-  mcpt::TemporalParams p;
-  std::memset(&p, 0, sizeof(p));
-  p.accum = c->d_accum; p.emap = emap; p.guide = c->d_guide;
-  p.hc_in = c->d_tp_c[in]; p.hl_in = c->d_tp_len[in]; p.hg_in = c->d_tp_g[c->tp_copy ? 0 : in];
-  p.hc_out = c->d_tp_c[to]; p.hl_out = c->d_tp_len[to]; p.hg_out = c->tp_copy ? nullptr : c->d_tp_g[to];
-  p.rec = c->d_tp_rec;
-  p.W = c->W; p.H = c->H; p.nb = (float)c->pass_count;
-  p.max_history = max_history; p.plane_tol = plane_tol; p.empty = empty ? 1 : 0;
-  if (!empty) std::memcpy(p.M, prevPV16, sizeof(p.M));
+  const mcpt::TemporalParams p = temporal_params(c, emap, prevPV16, max_history, plane_tol);
   const size_t n = (size_t)c->H * c->W;
   // (the context's stream is ordered after all queued renders: their combines run on it)
   // (the record is zeroed before the timed interval: the events enclose the kernel alone)
   HIP_OR_RETURN(hipMemsetAsync(c->d_tp_rec, 0, sizeof(unsigned long long) * mcpt::kStatsRecWords, c->stream));
   HIP_OR_RETURN(hipEventRecord(c->tp_ev[0], c->stream));
-  HIP_OR_RETURN(mcpt_launch_temporal(p, c->stream));
+  HIP_OR_RETURN(mcpt_launch_temporal(p, resolved, c->stream));
   HIP_OR_RETURN(hipEventRecord(c->tp_ev[1], c->stream));
   if (c->tp_copy) {
     if (n)
       HIP_OR_RETURN(hipMemcpyAsync(c->d_tp_g[0], c->d_guide, n * 2 * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
     HIP_OR_RETURN(hipEventRecord(c->tp_ev[2], c->stream));
   }
-  c->tp_cur = to;
+  c->tp_cur ^= 1;
   c->tp_frames += 1;
   c->tp_timed = true;
   unsigned long long h[6] = {0, 0, 0, 0, 0, 0};   // (word 5: the longest history, a maximum)
@@ -999,6 +1063,16 @@ int mcpt_temporal_accumulate(mcpt_ctx* c, const float* prevPV16, int max_history
   out->max_len = (int)h[5];
   out->frames = c->tp_frames;
   return MCPT_OK;
+}
+
+int mcpt_temporal_accumulate(mcpt_ctx* c, const float* prevPV16, int max_history, float plane_tol,
+                             mcpt_temporal_t* out) {
+  return temporal_accumulate(c, prevPV16, max_history, plane_tol, out, false, "mcpt_temporal_accumulate");
+}
+
+int mcpt_temporal_accumulate_resolved(mcpt_ctx* c, const float* prevPV16, int max_history, float plane_tol,
+                                      mcpt_temporal_t* out) {
+  return temporal_accumulate(c, prevPV16, max_history, plane_tol, out, true, "mcpt_temporal_accumulate_resolved");
 }
 
 int mcpt_denoise_temporal(mcpt_ctx* c, int iterations, float k_color, float sigma_plane) {

@@ -353,14 +353,23 @@ struct TemporalParams {
                                 // [4] sum_len [5] max_len per slot
   int W, H;
   float nb;                     // (float)pass_count
+  CountSource counts;           // the resolved form and the temporal select: every pixel's own count
   int max_history;
   float plane_tol;
   int empty;                    // the history holds nothing: every pixel is new
   float M[16];                  // P·V of the camera the history was made with, column-major
 };
 }  // namespace mcpt
-// one accumulate; adds into p.rec, which the caller has zeroed
-hipError_t mcpt_launch_temporal(const mcpt::TemporalParams& p, hipStream_t stream);
+// one accumulate; adds into p.rec, which the caller has zeroed.  counted: the current colour is
+// accum / (float)count_at(p.counts) (mcpt_temporal_accumulate_resolved), else accum / p.nb
+hipError_t mcpt_launch_temporal(const mcpt::TemporalParams& p, bool counted, hipStream_t stream);
+// mcpt_adaptive_select_temporal's step T: zeroes rec, then for every block of t
+// that is active the dry run of the counted accumulate p describes (p's *_out and rec are not used:
+// the history is only read), every pixel's rt into the record ([0] n_above_t, [1] sum_qt, [2] max_rt's
+// bits, [3] n_px_t, [4] active blocks, [5] n_history) and the block's new flag: it stays iff its
+// largest rt > threshold or it holds fewer than min_passes passes
+hipError_t mcpt_launch_temporal_select(const mcpt::AdaptiveTarget& t, const mcpt::TemporalParams& p, float mu_floor,
+                                       float threshold, int min_passes, unsigned long long* rec, hipStream_t stream);
 // the variance filter's first input from the temporal image: out = {hc.rgb, 3x3 prefilter of hc.w
 // among the centre's key} (mcpt_launch_variance_init's taps and weights)
 hipError_t mcpt_launch_temporal_init(const float4* hc, float4* out, const float4* guide, int W, int H,

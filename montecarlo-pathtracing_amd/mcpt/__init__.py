@@ -30,6 +30,7 @@ __all__ = [
     "Transfo", "average", "write_pfm", "write_png", "material", "light", "Hit", "HIT_DTYPE",
     "Convergence", "DENOISE_K_COLOR", "ERROR_MU_FLOOR", "DENOISE_K_VARIANCE",
     "TemporalRecord", "TEMPORAL_MAX_HISTORY", "TEMPORAL_PLANE_TOL", "mat4_inverse",
+    "AdaptiveTemporal", "TEMPORAL_TARGET",
 ]
 
 MONTECARLO, MAT, MAT_TR = 0, 1, 2
@@ -67,6 +68,9 @@ NO_TEMPORAL = -10  # MCPT_ERR_NO_TEMPORAL
 # camera, within which a history tap shows the same surface point
 TEMPORAL_MAX_HISTORY = 8
 TEMPORAL_PLANE_TOL = 0.01
+# temporal adaptive sampling's default target (tools/temporal_adaptive_bench.py): a
+# block stops once the relative error of the blend its accumulate would write now is at most this
+TEMPORAL_TARGET = 0.05
 
 
 class MCPTError(RuntimeError):
@@ -107,6 +111,14 @@ class TemporalRecord(ctypes.Structure):
     _fields_ = [("n_px", ctypes.c_longlong), ("n_history", ctypes.c_longlong), ("n_new", ctypes.c_longlong),
                 ("n_miss", ctypes.c_longlong), ("n_offscreen", ctypes.c_longlong), ("n_rejected", ctypes.c_longlong),
                 ("sum_len", ctypes.c_longlong), ("max_len", ctypes.c_int), ("frames", ctypes.c_longlong)]
+
+
+class AdaptiveTemporal(ctypes.Structure):
+    """mcpt_adaptive_temporal_t (include/mcpt.h): the raw frame record and the dry-run record of a select
+    on the temporal blend's error."""
+    _fields_ = [("raw", Adaptive), ("n_px_t", ctypes.c_longlong), ("n_above_t", ctypes.c_longlong),
+                ("sum_qt", ctypes.c_ulonglong), ("max_rt", ctypes.c_float), ("mean_rt", ctypes.c_double),
+                ("n_history", ctypes.c_longlong)]
 
 
 class AdaptiveCheckpoint(ctypes.Structure):
@@ -255,6 +267,10 @@ def _declare(L: ctypes.CDLL) -> None:
         "mcpt_temporal_begin": (i, [_vp]),
         "mcpt_temporal_end": (i, [_vp]),
         "mcpt_temporal_accumulate": (i, [_vp, fp, i, f, ctypes.POINTER(TemporalRecord)]),
+        "mcpt_temporal_accumulate_resolved": (i, [_vp, fp, i, f, ctypes.POINTER(TemporalRecord)]),
+        "mcpt_adaptive_select_temporal": (i, [_vp, fp, i, f, f, f, ctypes.POINTER(AdaptiveTemporal)]),
+        "mcpt_adaptive_run_temporal": (i, [_vp, fp, fp, i, i, i, i, f, f, fp, i, f, f, i, f, i,
+                                           ctypes.POINTER(AdaptiveTemporal), i, ctypes.POINTER(AdaptiveRun)]),
         "mcpt_denoise_temporal": (i, [_vp, i, f, f]),
         "mcpt_read_temporal": (i, [_vp, fp, ip]),
         "mcpt_temporal_info": (i, [_vp, ip, ip, ctypes.POINTER(ctypes.c_longlong)]),
@@ -1194,6 +1210,107 @@ class Renderer:
         self.render_guides(invPV, invV)
         rec = self.temporal_accumulate(prevPV, max_history, plane_tol)
         return self.denoise_temporal(iterations, k_color, sigma_plane), rec
+
+    # ---- temporal adaptive sampling: render only the blocks the history cannot carry (mcpt.h;
+    # DESIGN.md §3.10.1)
+    def temporal_accumulate_resolved(self, prevPV=None, max_history: int = TEMPORAL_MAX_HISTORY,
+                                     plane_tol: float = TEMPORAL_PLANE_TOL) -> dict:
+        """mcpt_temporal_accumulate_resolved: temporal_accumulate() whose current colour is accum /
+        (float)count with every pixel's own sample count (the adaptive mode must be on; retired blocks
+        are allowed and keep the error map entries they retired with).  The same record."""
+        rec = TemporalRecord()
+        m = None if prevPV is None else _f32(prevPV, 16)
+        _check(lib().mcpt_temporal_accumulate_resolved(self._h, None if m is None else _fp(m), int(max_history),
+                                                       float(plane_tol), ctypes.byref(rec)),
+               "mcpt_temporal_accumulate_resolved")
+        return {k: getattr(rec, k) for k, _ in TemporalRecord._fields_}
+
+    @staticmethod
+    def _temporal_dict(rec: AdaptiveTemporal) -> dict:
+        out = {k: getattr(rec.raw, k) for k, _ in Adaptive._fields_}
+        out.update({k: getattr(rec, k) for k, _ in AdaptiveTemporal._fields_[1:]})
+        return out
+
+    def adaptive_select_temporal(self, prevPV=None, threshold: float = TEMPORAL_TARGET,
+                                 max_history: int = TEMPORAL_MAX_HISTORY, plane_tol: float = TEMPORAL_PLANE_TOL,
+                                 mu_floor: float = ERROR_MU_FLOOR) -> dict:
+        """mcpt_adaptive_select_temporal: the select on the error of the blend that
+        temporal_accumulate_resolved(prevPV, max_history, plane_tol) would write now.  Writes the error
+        map as adaptive_select() does, reads the history and leaves it alone, and retires the active
+        blocks whose largest rt <= threshold (and that hold min_passes).  adaptive_select()'s keys
+        (n_active_blocks: what this rule keeps) plus n_px_t, n_above_t, sum_qt, max_rt, mean_rt and
+        n_history over the pixels of the blocks active on entry.  Needs render_guides() of the camera
+        being rendered."""
+        rec = AdaptiveTemporal()
+        m = None if prevPV is None else _f32(prevPV, 16)
+        _check(lib().mcpt_adaptive_select_temporal(self._h, None if m is None else _fp(m), int(max_history),
+                                                   float(plane_tol), float(threshold), float(mu_floor),
+                                                   ctypes.byref(rec)), "mcpt_adaptive_select_temporal")
+        return self._temporal_dict(rec)
+
+    def adaptive_run_temporal(self, invPV, invV, first_pass: int, n_passes: int, rounds: int, prevPV=None,
+                              threshold: float = TEMPORAL_TARGET, check_every: int = 1,
+                              max_history: int = TEMPORAL_MAX_HISTORY, plane_tol: float = TEMPORAL_PLANE_TOL,
+                              mu_floor: float = ERROR_MU_FLOOR, date: float = 0.0, bounces: int = 3,
+                              refract_ind: float = 1.0, variant: int = MONTECARLO) -> dict:
+        """mcpt_adaptive_run_temporal: adaptive_run() whose selects are adaptive_select_temporal(prevPV,
+        threshold, max_history, plane_tol, mu_floor); the records are that call's dicts."""
+        a, b = _f32(invPV, 16), _f32(invV, 16)
+        m = None if prevPV is None else _f32(prevPV, 16)
+        cap = max(int(rounds), 1)
+        recs, run = (AdaptiveTemporal * cap)(), AdaptiveRun()
+        _check(lib().mcpt_adaptive_run_temporal(self._h, _fp(a), _fp(b), int(first_pass), int(n_passes), int(rounds),
+                                                int(check_every), float(threshold), float(mu_floor),
+                                                None if m is None else _fp(m), int(max_history), float(plane_tol),
+                                                float(date), int(bounces), float(refract_ind), int(variant), recs, cap,
+                                                ctypes.byref(run)), "mcpt_adaptive_run_temporal")
+        out = {k: getattr(run, k) for k, _ in AdaptiveRun._fields_}
+        out["records"] = [self._temporal_dict(recs[j]) for j in range(run.selects_run)]
+        return out
+
+    def render_frame_temporal_adaptive(self, invPV, invV, prevPV, first_pass: int, cap_spp: int = 16,
+                                       n_passes: int = 2, threshold: float = TEMPORAL_TARGET, date: float = 0.0,
+                                       bounces: int = 3, refract_ind: float = 1.0, variant: int = MONTECARLO,
+                                       max_history: int = TEMPORAL_MAX_HISTORY, plane_tol: float = TEMPORAL_PLANE_TOL,
+                                       iterations: int = 5, k_color: float = DENOISE_K_VARIANCE,
+                                       sigma_plane: float = DENOISE_SIGMA_PLANE, mu_floor: float = ERROR_MU_FLOOR,
+                                       min_passes: int = 0, queued: bool = True) -> Tuple[np.ndarray, dict, dict]:
+        """One frame of a moving-camera render that spends samples only where the history cannot carry
+        the pixel: clear the accumulator, a fresh statistics window and adaptive state, the guides of
+        this camera, then rounds of `n_passes` passes for the active blocks, up to cap_spp // n_passes
+        rounds, with adaptive_select_temporal(prevPV, threshold) after every round from the second on
+        (queued: as one adaptive_run_temporal, one host wait; else the host loop, the same bits), then
+        temporal_accumulate_resolved(prevPV) and denoise_temporal.  Begins the temporal mode unless it
+        is on.  Returns (the filtered H x W x 3 image, the accumulate's record, the last select's record
+        with "rendered": the passes the longest-lived blocks received).  The next frame's first_pass is
+        first_pass + cap_spp (pass ids never repeat whatever a frame rendered) and its prevPV is
+        mat4_inverse(invPV) of this one."""
+        if n_passes <= 0 or cap_spp < 2 * n_passes or not threshold > 0:
+            raise MCPTError("render_frame_temporal_adaptive: positive n_passes and threshold, cap_spp of two "
+                            "rounds or more")
+        rounds = min(cap_spp // n_passes, ADAPTIVE_RUN_MAX_ROUNDS)
+        if not self.temporal_info()["on"]:
+            self.temporal_begin()
+        self.clear_accum()
+        self.stats_begin()
+        self.adaptive_begin(min_passes)
+        self.render_guides(invPV, invV)
+        if queued:
+            got = self.adaptive_run_temporal(invPV, invV, first_pass, n_passes, rounds, prevPV, threshold, 1,
+                                             max_history, plane_tol, mu_floor, date, bounces, refract_ind, variant)
+            sel, done = got["records"][-1], got["rounds_run"] * n_passes
+        else:
+            sel, done = None, 0
+            for i in range(rounds):
+                self.render_adaptive(invPV, invV, first_pass + done, n_passes, date, bounces, refract_ind, variant)
+                done += n_passes
+                if i >= 1:
+                    sel = self.adaptive_select_temporal(prevPV, threshold, max_history, plane_tol, mu_floor)
+                    if sel["n_active_blocks"] == 0:
+                        break
+        sel["rendered"] = done
+        rec = self.temporal_accumulate_resolved(prevPV, max_history, plane_tol)
+        return self.denoise_temporal(iterations, k_color, sigma_plane), rec, sel
 
     # ---- frames with per-pixel sample counts: filter, checkpoint, gather (mcpt.h; DESIGN.md §3.9)
     def denoise_resolved(self, iterations: int = 5, sigma_color: float = DENOISE_SIGMA_COLOR,
