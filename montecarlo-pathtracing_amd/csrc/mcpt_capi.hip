@@ -945,10 +945,8 @@ static int prepare_order(mcpt_ctx* c, int li, hipStream_t ws, const plan::ItemsI
   return MCPT_OK;
 }
 
-// ... its split items' buffers and, with pass stealing (kernel: steal_next; MCPT_STEAL=0: off,
-// tests and A/B; the same bits either way), the store of every pass's value
-static int prepare_split_items(mcpt_ctx* c, mcpt_ctx::Lane& L, hipStream_t ws, long long items, bool steal,
-                               mcpt::RenderParams& p) {
+// ... its split items' buffers
+static int prepare_split_items(mcpt_ctx::Lane& L, hipStream_t ws, long long items, mcpt::RenderParams& p) {
   if (!L.d_split_pass) {
     HIP_OR_RETURN(hipMalloc(&L.d_split_pass, sizeof(float) * 3 * (size_t)plan::kSplitMax * mcpt::kPassChunk *
                                                  mcpt::kTileThreads));
@@ -958,11 +956,6 @@ static int prepare_split_items(mcpt_ctx* c, mcpt_ctx::Lane& L, hipStream_t ws, l
   p.split_pass = L.d_split_pass;
   p.split_max = plan::kSplitMax;
   if (p.item_perm) p.split_n = L.d_split_n;
-  if (steal) {
-    OK_OR_RETURN(ensure_lane_bytes(c, L.d_steal, L.steal_bytes,
-                                   sizeof(float) * 3 * (size_t)items * mcpt::kPassChunk * mcpt::kTileThreads));
-    p.steal_vals = L.d_steal;
-  }
   return MCPT_OK;
 }
 
@@ -1084,12 +1077,14 @@ static int launch(mcpt_ctx* c, const float* invPV, const float* invV, int first_
     if (it.order) HIP_OR_RETURN(ensure_item_order(c, L, it.items));
     if (lane) HIP_OR_RETURN(hipStreamWaitEvent(L.stream, lane_freed(c, L), 0));
     if (it.order) OK_OR_RETURN(prepare_order(c, li, ws, in, it, p));
-    if (it.split_items) OK_OR_RETURN(prepare_split_items(c, L, ws, it.items, steal, p));
-    // (launches of one segment add into the accumulator themselves, pass-split ones run one pass
-    // per item: neither steals)
-    if (scene_steal && lim.may_steal && p.n_segments > 1 && !split) {
-      OK_OR_RETURN(ensure_lane_bytes(c, L.d_steal, L.steal_bytes, sizeof(float) * 3 * (size_t)p.n_tiles * p.n_segments *
-                                                                      mcpt::kPassChunk * p.tile_w * mcpt::kTileH));
+    if (it.split_items) OK_OR_RETURN(prepare_split_items(L, ws, it.items, p));
+    // pass stealing (MCPT_STEAL=0: off, tests and A/B; the same bits either way): the mesh kernels
+    // in split-item launches, the LDS-scene kernels in launches of several segments (launches of
+    // one segment add into the accumulator themselves, pass-split ones run one pass per item:
+    // neither steals); the store of every pass's value
+    if (lim.may_steal && (it.split_items || (scene_steal && p.n_segments > 1 && !split))) {
+      OK_OR_RETURN(ensure_lane_bytes(c, L.d_steal, L.steal_bytes,
+                                     (size_t)plan::steal_store_bytes(p.n_tiles, p.tile_w, p.n_segments)));
       p.steal_vals = L.d_steal;
     }
     // The timed interval of a lane launch that follows one on the other lane starts where that

@@ -116,16 +116,15 @@ struct RenderParams {
   const int* split_n;
   int* split_of;
   float* split_pass;
-  // pass stealing (mesh kernels with split items; null: off): every pass's value of the launch goes
-  // to steal_vals (n_items x kPassChunk x kTileThreads x 3 floats, by the pass's offset in its
-  // segment and its pixel's thread), a lane done with its own pixel takes the next unstarted pass
-  // of any pixel of its workgroup, and combine_steal_kernel sums each segment's passes from 0 in
-  // pass order: the bits of the per-lane sums.
-  // LDS-scene kernels (no meshes; render_kernel<.., STEAL>): n_tiles x n_segments x
-  // kPassChunk x (tile_w x kTileH) x 3 floats, the slot of a pass at ((tile x n_segments + segment)
-  // x kPassChunk + pass offset in its chunk) x tile threads + its pixel's thread; each wave of the
-  // workgroup steals among its own 64 pixels over all the segments of the work item, and
-  // combine_steal_seg_kernel sums the launch's passes of each chunk from 0 in pass order
+  // pass stealing (null: off; set by launch() on the mesh kernels' split-item launches and on the
+  // LDS-scene kernels' timed launches of several segments, render_kernel<.., STEAL>; DESIGN.md
+  // §4.6, §4.8): every pass's value of the launch goes to steal_vals, n_tiles x n_segments x
+  // kPassChunk x (tile_w x kTileH) x 3 floats (plan::steal_store_bytes), the slot of a pass at
+  // ((tile x n_segments + segment) x kPassChunk + pass offset in its chunk) x tile threads + its
+  // pixel's thread.  A lane done with its pixel takes the next unstarted pass of any pixel of its
+  // wave (over the item's segments; mesh kernels: its one segment or split piece), and
+  // combine_steal_kernel sums the launch's passes of each chunk from 0 in pass order: the bits of
+  // the per-lane sums.
   float* steal_vals;
   int n_items;                  // work items of the launch (its grid may hold spare workgroups)
   int tail_m;                   // seg_per_item > 1: the last tail_m items of item_perm run one segment per workgroup
@@ -408,12 +407,12 @@ enum CheckSite {
   CK_PERM_HEAD,       // item_perm[b] / item b, a whole item's workgroup (b < n_items)
   CK_ITEM,            // the item a workgroup runs (< n_items)
   CK_SPLIT_OF,        // split_of[item] (< n_items)
-  CK_SPLIT_PASS,      // split_pass slot: split index < split_max, pass within the chunk
+  CK_SPLIT_PASS,      // split_pass slot: split index < split_max, pass within the chunk, thread < kTileThreads
   CK_SEGMENT,         // segment slot of partial (< n_segments)
   CK_PIXEL,           // local pixel of accum / partial (< n_local_px)
   CK_COMBINE_SPLIT,   // combine_items_kernel: split index read from split_of (< split_max)
   CK_LIST,            // adaptive launches: the list index and the block id read from it (< n_blocks)
-  CK_STEAL_SLOT,      // the LDS-scene kernels' steal_vals slot: tile < n_tiles, segment < n_segments, thread < TT
+  CK_STEAL_SLOT,      // steal_vals slot: tile < n_tiles, segment < n_segments, thread < TT (mesh kernels: pass offset < kPassChunk, thread < TT)
   CK_COUNT
 };
 #ifdef MCPT_CHECKED

@@ -357,7 +357,7 @@ __global__ __launch_bounds__(TW * kTileH, MESH && !WAVE ? kMinWavesMesh
   // for the combine, which adds it after piece 0's sum in pass order
   auto add_pass = [&](f3 v) {
     if constexpr (STEAL) {
-      // slot (tile, segment, pass of its chunk, thread of the tile): combine_steal_seg_kernel
+      // slot (tile, segment, pass of its chunk, thread of the tile): combine_steal_kernel
       const int ch = (pass - 1) >> 5, sg = ch - cbase, off = (pass - 1) & (kPassChunk - 1);
       if constexpr (kChecked) {
         if (!idx_ok(p.events, CK_STEAL_SLOT, sg, p.n_segments) || !idx_ok(p.events, CK_STEAL_SLOT, pj, TT) ||
@@ -373,10 +373,13 @@ __global__ __launch_bounds__(TW * kTileH, MESH && !WAVE ? kMinWavesMesh
     }
     if (kSplit && steal) {
       if constexpr (kChecked) {
-        if (!idx_ok(p.events, CK_SPLIT_PASS, pass - seg_first, kPassChunk) || !idx_ok(p.events, CK_SPLIT_PASS, pj, kTileThreads))
+        if (!idx_ok(p.events, CK_STEAL_SLOT, pass - seg_first, kPassChunk) || !idx_ok(p.events, CK_STEAL_SLOT, pj, TT))
           return;
       }
-      float* q = p.steal_vals + (((size_t)item * kPassChunk + (pass - seg_first)) * kTileThreads + pj) * 3;
+      // the STEAL slot above at TT = 64: split-item launches run one whole segment per item, so
+      // item = tile x n_segments + segment and pass - seg_first is the pass's offset in its chunk
+      // (64-bit arithmetic: this store has no 2^32-slot guard)
+      float* q = p.steal_vals + (((size_t)item * kPassChunk + (pass - seg_first)) * TT + pj) * 3;
       q[0] = v.x; q[1] = v.y; q[2] = v.z;
       return;
     }
@@ -797,38 +800,14 @@ __global__ __launch_bounds__(256) void combine_items_kernel(float* __restrict__ 
   accum[i * 3] = a0; accum[i * 3 + 1] = a1; accum[i * 3 + 2] = a2;
 }
 
-// launches with pass stealing (RenderParams::steal_vals): every pass's value is stored; per pixel
-// and segment the passes are summed from 0 in pass order (as the lane's segment sum was), and the
-// segment sums are added to the accumulator in segment order — the bits of combine_items_kernel's
-// launches (one segment per item, full 32-pass segments)
-__global__ __launch_bounds__(256) void combine_steal_kernel(float* __restrict__ accum, long long n_px, int n_seg,
-                                                            int W, int TW, const float* __restrict__ vals) {
-  long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n_px) return;
-  const int lr = (int)(i / W), x = (int)(i - (long long)lr * W);
-  const int tiles_x = (W + TW - 1) / TW;
-  const int tile = (lr / kTileH) * tiles_x + x / TW;
-  const int t = (((lr % kTileH) / 8) * (TW / 8) + (x % TW) / 8) * 64 + (lr % 8) * 8 + (x % 8);   // its thread
-  float a0 = accum[i * 3], a1 = accum[i * 3 + 1], a2 = accum[i * 3 + 2];
-  for (int s = 0; s < n_seg; ++s) {
-    const size_t item = (size_t)tile * n_seg + s;
-    float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f;
-    for (int k = 0; k < kPassChunk; ++k) {
-      const float* v = vals + ((item * kPassChunk + k) * kTileThreads + t) * 3;
-      s0 = s0 + v[0]; s1 = s1 + v[1]; s2 = s2 + v[2];
-    }
-    a0 = a0 + s0; a1 = a1 + s1; a2 = a2 + s2;
-  }
-  accum[i * 3] = a0; accum[i * 3 + 1] = a1; accum[i * 3 + 2] = a2;
-}
-
-// launches of the LDS-scene kernels with pass stealing (render_kernel<.., STEAL>): one thread per
+// launches with pass stealing (RenderParams::steal_vals; the STEAL kernels and the mesh kernels of
+// split-item launches, TW = 8): every pass's value is stored, no segment sums.  One thread per
 // thread of a tile, so that a wave reads 64 consecutive values of a slot row.  Per pixel and
 // segment the launch's passes of the chunk are summed from 0 in pass order (a lane's add_pass
 // sequence), and the sums are added to the accumulator in segment order (combine_kernel's).
-__global__ __launch_bounds__(256) void combine_steal_seg_kernel(float* __restrict__ accum, int n_tiles, int n_seg, int W,
-                                                                int n_local_rows, int TW, const float* __restrict__ vals,
-                                                                int first_pass, int n_passes, unsigned long long* ev) {
+__global__ __launch_bounds__(256) void combine_steal_kernel(float* __restrict__ accum, int n_tiles, int n_seg, int W,
+                                                            int n_local_rows, int TW, const float* __restrict__ vals,
+                                                            int first_pass, int n_passes, unsigned long long* ev) {
   const int TT = TW * kTileH;
   const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
   if (g >= (long long)n_tiles * TT) return;
@@ -1018,16 +997,11 @@ hipError_t mcpt_launch_render_list(const mcpt::RenderParams& p, hipStream_t stre
 hipError_t mcpt_launch_combine(const mcpt::RenderParams& p, hipStream_t stream) {
   if (p.n_local_px <= 0) return hipSuccess;
   dim3 block(256), grid((unsigned)((p.n_local_px + 255) / 256));
-  if (p.steal_vals && p.n_meshes == 0) {   // the LDS-scene kernels' stealing: slots by (tile, segment, pass, thread)
+  if (p.steal_vals) {   // slots by (tile, segment, pass, thread); (the render stored passes, no sums)
     const long long n_thr = (long long)p.n_tiles * p.tile_w * mcpt::kTileH;
-    hipLaunchKernelGGL(mcpt::combine_steal_seg_kernel, dim3((unsigned)((n_thr + 255) / 256)), block, 0, stream, p.accum,
+    hipLaunchKernelGGL(mcpt::combine_steal_kernel, dim3((unsigned)((n_thr + 255) / 256)), block, 0, stream, p.accum,
                        p.n_tiles, p.n_segments, p.W, p.n_local_rows, p.tile_w, p.steal_vals, p.first_pass, p.n_passes,
                        p.events);
-    return hipGetLastError();
-  }
-  if (p.steal_vals) {   // (also for one segment: the render stored passes, no sums)
-    hipLaunchKernelGGL(mcpt::combine_steal_kernel, grid, block, 0, stream, p.accum, p.n_local_px, p.n_segments, p.W,
-                       p.tile_w, p.steal_vals);
     return hipGetLastError();
   }
   if (p.n_segments <= 1) return hipSuccess;

@@ -27,7 +27,7 @@ namespace plan {
 // is one launch: +0.7 % against four launches under a 1 GiB bound, whose grid tails add up,
 // profiles/r03_ab_partial_budget_c5.jsonl; mcpt_set_partial_budget / MCPT_PARTIAL_BYTES)
 constexpr size_t kDefaultPartialBudget = size_t(4) << 30;
-// per-pass value store of pass stealing (mesh launches), per render lane
+// per-pass value store of pass stealing (steal_store_bytes), per render lane: of mesh launches
 constexpr size_t kStealBudget = size_t(8) << 30;
 // ... and of the LDS-scene launches, per render lane: 1080p in 16-wide tiles holds
 // 21 segments (C2's eight are one launch of 6.4 GB), 4K five
@@ -67,6 +67,11 @@ struct Limits {
   bool may_steal = false;    // mesh launches of one segment per item; LDS-scene launches (lds_scene)
   bool too_large = false;
 };
+// bytes of the pass-stealing value store (RenderParams::steal_vals) of a launch of n_segments
+// segments: three floats per (tile, segment, pass of the chunk, thread of the tile)
+constexpr long long steal_store_bytes(long long n_tiles, int tile_w, long long n_segments) {
+  return n_tiles * n_segments * kPassChunk * tile_w * kTileH * 3 * (long long)sizeof(float);
+}
 // The call's pass range is cut at accumulation-chunk boundaries into sub-launches of at
 // most max_seg segments, so that the segment-sum buffer stays within partial_budget and
 // the grid within 2^32 work-items (an 84,000-pass 4K call is ~2,600 segments: 261 GB of
@@ -82,20 +87,19 @@ inline Limits limits(const LimitsIn& in) {
   r.max_items = (1LL << 32) / (in.tile_w * kTileH) - 1 - spare;
   r.too_large = in.n_tiles > r.max_items;
   long long max_seg = seg_bytes > 0 ? (long long)(in.partial_budget / (size_t)seg_bytes) : (1LL << 30);
-  // mesh launches that may steal passes also store every pass's value (kPassChunk per segment and
-  // pixel): at most kStealBudget of them per render lane, but two segments at least, so that
-  // split items and stealing still apply (1080p: 10 segments per sub-launch; 4K: 2, 6.4 GB)
+  // launches that steal passes store every pass's value (steal_store_bytes); one segment's:
+  const long long val_bytes = steal_store_bytes(in.n_tiles, in.tile_w, 1);
+  // mesh launches (one segment per item): at most kStealBudget per render lane, but two segments
+  // at least, so that split items and stealing still apply (1080p: 10 segments per sub-launch,
+  // 7.96 GB; 4K: 2, 6.4 GB)
   r.may_steal = in.mesh && !in.wave_traversal && kseg_max == 1 && in.steal;
-  if (r.may_steal && seg_bytes > 0)
-    max_seg = std::min(max_seg, std::max(2LL, (long long)(kStealBudget / ((size_t)seg_bytes * kPassChunk))));
-  // the LDS-scene launches steal inside each wave at any number of segments per item (DESIGN.md
-  // §4.8) and store every pass's value by (tile, segment, pass of the chunk, thread of the tile):
-  // at most kSceneStealBudget per render lane, in whole items (kseg_max segments), one at least.
+  if (r.may_steal && val_bytes > 0) max_seg = std::min(max_seg, std::max(2LL, (long long)(kStealBudget / (size_t)val_bytes)));
+  // the LDS-scene launches steal at any number of segments per item: at most
+  // kSceneStealBudget per render lane, in whole items (kseg_max segments), one at least.
   // 4K in 16-wide tiles: 3.19 GB per segment, so five segments fit and a launch of four-segment
   // items holds four of them: C5's 1,024-pass step is eight sub-launches of 128 passes.
   if (in.lds_scene && !in.mesh && !in.wave_traversal && in.steal) {
     r.may_steal = true;
-    const long long val_bytes = in.n_tiles * in.tile_w * kTileH * 3 * (long long)sizeof(float) * kPassChunk;
     // (the kernel indexes the store's 12-byte slots in 32 bits: a frame whose single item would
     // hold 2^32 of them does not steal)
     if (val_bytes * kseg_max >= (12LL << 32)) r.may_steal = false;

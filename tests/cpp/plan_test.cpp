@@ -69,6 +69,45 @@ static void test_max_seg() {
   done("max_seg");
 }
 
+// the pass-stealing value store: 12 B x 32 passes x tile threads per tile and segment, and the
+// sub-launch bounds it gives (the values of before the store had one size function)
+static void test_steal_store() {
+  plan::LimitsIn in = frame(1920, 1080, 8, true);   // 240 x 135 = 32,400 tiles of 64 threads
+  CHECK(in.n_tiles == 32400);
+  CHECK(plan::steal_store_bytes(in.n_tiles, 8, 10) == 7962624000LL);   // 32,400 x 10 x 32 x 64 x 12
+  CHECK(plan::steal_store_bytes(in.n_tiles, 8, 10) <= (long long)plan::kStealBudget);
+  CHECK(plan::steal_store_bytes(in.n_tiles, 8, 11) > (long long)plan::kStealBudget);
+  CHECK(plan::limits(in).max_seg == 10);
+  in = frame(3840, 2160, 8, true);   // 480 x 270 = 129,600 tiles
+  CHECK(plan::steal_store_bytes(in.n_tiles, 8, 2) == 6370099200LL);   // 129,600 x 2 x 32 x 64 x 12
+  CHECK(plan::limits(in).max_seg == 2);
+  // 253 x 131: 32 x 17 = 544 tiles, the partial ones whole in the store (not 33,143 px / 64 = 517.9)
+  in = frame(253, 131, 8, true);
+  CHECK(in.n_tiles == 544);
+  CHECK(plan::steal_store_bytes(in.n_tiles, 8, 1) == 544LL * 32 * 64 * 12);   // 13,369,344
+  // 8 GiB / 13,369,344 = 642.5 (the segment-sum budget allows 10,799).  Sized by pixels, 8 GiB /
+  // (33,143 x 32 x 12) gave 674, whose store of 544 tiles is 9,010,937,856 B > 8 GiB: the one
+  // shape here whose bound moves, and only above the 24 segments the suite renders at this size
+  CHECK(plan::limits(in).max_seg == 642);
+  CHECK(plan::steal_store_bytes(in.n_tiles, 8, 674) > (long long)plan::kStealBudget);
+  in.partial_budget = (size_t)(253 * 131 * 12 * 8);   // (tests/test_gpu_work_items.py: eight segments)
+  CHECK(plan::limits(in).max_seg == 8);
+  // the LDS-scene kernels' store at 1080p in 16-wide tiles: 120 x 135 tiles of 128 threads
+  in = frame(1920, 1080, 16, false);
+  in.lds_scene = true;
+  in.seg_per_item = 4;
+  CHECK(plan::steal_store_bytes(in.n_tiles, 16, 8) == in.n_tiles * 16 * mcpt::kTileH * 12 * mcpt::kPassChunk * 8);
+  CHECK(plan::steal_store_bytes(in.n_tiles, 16, 8) == 6370099200LL);
+  CHECK(plan::limits(in).max_seg == 20);
+  in.seg_per_item = 1;
+  CHECK(plan::limits(in).max_seg == 21);
+  in = frame(3840, 2160, 16, false);
+  in.lds_scene = true;
+  in.seg_per_item = 4;
+  CHECK(plan::limits(in).max_seg == 4);
+  done("steal_store");
+}
+
 static void test_may_steal() {
   plan::LimitsIn in = frame(1920, 1080, 8, true);
   CHECK(plan::limits(in).may_steal);
@@ -356,6 +395,7 @@ int main() {
   test_pass_segments();
   test_max_seg();
   test_may_steal();
+  test_steal_store();
   test_grid_bound();
   test_cutting();
   test_pass_split();

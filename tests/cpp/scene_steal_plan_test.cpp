@@ -52,6 +52,8 @@ int main() {
     check_budgets(in, l);
     CHECK(plan::count_sub_launches(1, 256, l.max_seg, false) == 1);   // C2's step: one launch, 6.4 GB
     CHECK(value_bytes(in, 8) == 6370099200LL);
+    CHECK(plan::steal_store_bytes(in.n_tiles, in.tile_w, 8) == value_bytes(in, 8));   // the plan's own size function
+    CHECK(plan::steal_store_bytes(in.n_tiles, in.tile_w, l.max_seg) == value_bytes(in, l.max_seg));
     in.seg_per_item = 2;
     CHECK(plan::limits(in).may_steal && plan::limits(in).max_seg == 20);
     in.seg_per_item = 1;

@@ -226,6 +226,38 @@ def test_render_lanes_partial_tiles_same_bits(mcpt_mod, mesh, mesh_baseline, mon
         assert np.array_equal(bits(out["1"][k]), bits(mesh_baseline[768])), k
 
 
+# a frame one tile wide: 17 tiles of 8x8, every one with the partial column, the last 3 px tall
+E_W, E_H = 5, 131
+E_ROWS = np.arange(3, 131, 12)   # 11 image rows: two tiles, of 8 and of 3 local rows
+
+
+@pytest.mark.parametrize("rows,segs", [(None, 256), (E_ROWS, 2048)], ids=["frame", "row_shard"])
+def test_mesh_one_tile_column_same_bits(mcpt_mod, mesh, monkeypatch, rows, segs):
+    """Case E: 5 x 131, the mesh kernels' value store where the tile index is the tile row alone
+    (tiles_x = 1) and no tile is whole.  One call of 2 x `segs` segments, cut by the segment-sum
+    budget into two sub-launches of `segs` segments: 17 x 256 = 4,352 items on the frame, 2 x 2,048 =
+    4,096 on an 11-row shard (kOrderMinItems: split-item launches, which steal; the second sub-launch
+    starts at chunk `segs` and runs the order the first one measured).  The frame equals launch
+    order's (MCPT_ITEM_ORDER=0: no stealing, combine_kernel) bit for bit."""
+    n_rows = E_H if rows is None else len(rows)
+    assert -(-n_rows // 8) * segs >= 4096
+    r = mcpt_mod.Renderer(0)
+    try:
+        r.set_partial_budget(E_W * n_rows * 12 * segs)
+        set_env(monkeypatch)
+        on, _, launches, (stolen, n_split) = run_calls(mcpt_mod, r, mesh, E_W, E_H, [2 * segs * 32], MB, MIOR, 1, rows=rows)
+        set_env(monkeypatch, MCPT_ITEM_ORDER=0)
+        off, _, launches_off, (stolen_off, _) = run_calls(mcpt_mod, r, mesh, E_W, E_H, [2 * segs * 32], MB, MIOR, 1, rows=rows)
+    finally:
+        r.close()
+    print(f"case E, {n_rows} rows: slot 62 (stolen passes) {stolen}, slot 63 (items split) {n_split}, launches {launches}")
+    assert launches == [2] and launches_off == [2]
+    assert stolen > 0 and stolen_off == 0
+    assert on.shape == (n_rows, E_W, 3) and off.any()
+    same = bits(on) == bits(off)
+    assert same.all(), f"{int((~same).any(axis=2).sum())} pixels differ, rows {np.unique(np.nonzero(~same)[0])[:12]}"
+
+
 D_W, D_H, D_B = 517, 253, 4   # 32 tile rows, the last 5 px tall; the last tile column 5 px wide at 16 and at 32
 D_ROWS = [0, 100, 247, 248, 252]
 # (scene, walk, tile width (mcpt_internal.h tile_w_for), passes per call of the tail-piece runs).
