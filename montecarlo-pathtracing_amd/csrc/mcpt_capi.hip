@@ -56,10 +56,10 @@ static hipEvent_t ev_at(const mcpt_ctx* c, int slot, int k, int i) { return c->e
 static hipError_t ensure_events(mcpt_ctx* c, int slot, int n_sub) {
   if ((int)c->ring_lane[slot].size() < n_sub) c->ring_lane[slot].resize(n_sub, 0);
   while ((int)c->evs[slot].size() < kEvPerSub * n_sub) {
-    hipEvent_t e = nullptr;
-    hipError_t r = hipEventCreate(&e);
+    Event e;
+    hipError_t r = e.ensure();
     if (r != hipSuccess) return r;
-    c->evs[slot].push_back(e);
+    c->evs[slot].push_back(std::move(e));
   }
   return hipSuccess;
 }
@@ -67,7 +67,7 @@ static hipError_t ensure_events(mcpt_ctx* c, int slot, int n_sub) {
 // slot `slot` (waits for it)
 static hipError_t slot_launch_ms(const mcpt_ctx* c, int slot, float* trace_ms, float* combine_ms) {
   *trace_ms = 0.0f; *combine_ms = 0.0f;
-  const std::vector<hipEvent_t>& v = c->evs[slot];
+  const std::vector<Event>& v = c->evs[slot];
   for (int k = 0; k < c->ring_n_sub[slot]; ++k) {
     float a = 0.0f, b = 0.0f;
     hipError_t e = hipEventSynchronize(v[kEvPerSub * k + 2]);
@@ -95,7 +95,7 @@ static int resolve_candidate(const mcpt_ctx* c, long long segs) {
 static bool schedule_settled(const mcpt_ctx* c) { return c->traversal != MCPT_TRAVERSAL_AUTO || c->tuner.tune_choice != 0; }
 
 static void reset_tuning(mcpt_ctx* c) {
-  for (auto& L : c->lanes) L.order_valid = false;   // a new scene / target: item costs start over
+  for (auto& L : c->lanes) L.order.valid = false;   // a new scene / target: item costs start over
   c->tuner.reset();
 }
 
@@ -187,11 +187,11 @@ int mcpt_create(int device_ordinal, mcpt_ctx** out) {
   // lanes its short kernels are dispatched ahead of the next render's waiting workgroups
   int prio_least = 0, prio_greatest = 0;
   if (hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest) != hipSuccess) prio_greatest = 0;
-  hipError_t e = hipStreamCreateWithPriority(&c->own_stream, hipStreamNonBlocking, prio_greatest);
+  hipError_t e = c->own_stream.ensure_with_priority(hipStreamNonBlocking, prio_greatest);
   for (auto& L : c->lanes) {
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&L.stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&L.freed, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&L.tail, hipEventDisableTiming);
+    if (e == hipSuccess) e = L.stream.ensure(hipStreamNonBlocking);
+    if (e == hipSuccess) e = L.freed.ensure(hipEventDisableTiming);
+    if (e == hipSuccess) e = L.tail.ensure(hipEventDisableTiming);
   }
   // (recorded once, so that the first waits on them are satisfied)
   for (auto& L : c->lanes) {
@@ -208,7 +208,7 @@ int mcpt_create(int device_ordinal, mcpt_ctx** out) {
 #else
   constexpr size_t kEventSlots = MCPT_DEBUG_SLOTS;
 #endif
-  if (e == hipSuccess) e = hipMalloc(&c->d_events, sizeof(unsigned long long) * kEventSlots);
+  if (e == hipSuccess) e = c->d_events.alloc(kEventSlots);
   if (e == hipSuccess) e = hipMemset(c->d_events, 0, sizeof(unsigned long long) * kEventSlots);
   if (e != hipSuccess) { mcpt_destroy(c); return set_err(MCPT_ERR_HIP, "mcpt_create", e); }
   c->stream = c->own_stream;
@@ -216,67 +216,12 @@ int mcpt_create(int device_ordinal, mcpt_ctx** out) {
   return MCPT_OK;
 }
 
-static void free_meshes(mcpt_ctx* c) {
-  (void)hipFree(c->d_minfo); (void)hipFree(c->d_mpairs);   // (d_mleaftris points into d_mpairs)
-  (void)hipFree(c->d_mtris); (void)hipFree(c->d_mverts); (void)hipFree(c->d_mnorms);
-  c->d_minfo = nullptr; c->d_mpairs = nullptr; c->d_mleaftris = nullptr;
-  c->d_mtris = nullptr; c->d_mverts = nullptr; c->d_mnorms = nullptr;
-  c->n_meshes = 0;
-}
-
-static void free_scene(mcpt_ctx* c) {
-  (void)hipFree(c->d_nodes); (void)hipFree(c->d_leaves); (void)hipFree(c->d_ptype); (void)hipFree(c->d_prims);
-  c->d_nodes = nullptr; c->d_leaves = nullptr; c->d_ptype = nullptr; c->d_prims = nullptr;
-  c->has_scene = false;
-}
-
 int mcpt_destroy(mcpt_ctx* c) {
   if (!c) return MCPT_OK;
   (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
-  free_scene(c);
-  free_meshes(c);
-  free_denoise(c);
-  for (hipEvent_t e : c->guide_ev) if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : c->dn_ev) if (e) (void)hipEventDestroy(e);
-  free_stats(c);
-  for (hipEvent_t e : c->stats_ev) if (e) (void)hipEventDestroy(e);
-  free_adaptive(c);
-  for (hipEvent_t e : c->ad_ev) if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : c->run_ev) if (e) (void)hipEventDestroy(e);
-  free_count_plane(c);
-  free_temporal(c);
-  for (hipEvent_t e : c->tp_ev) if (e) (void)hipEventDestroy(e);
-  (void)hipFree(c->d_accum);
-  (void)hipFree(c->d_rows);
-  (void)hipFree(c->d_events);
-  for (auto& L : c->lanes) {
-    if (L.stream) (void)hipStreamSynchronize(L.stream);
-    (void)hipFree(L.d_partial);
-    (void)hipFree(L.d_item_cost);
-    (void)hipFree(L.d_cost_sorted);
-    (void)hipFree(L.d_item_iota);
-    (void)hipFree(L.d_item_perm);
-    (void)hipFree(L.d_split_of);
-    (void)hipFree(L.d_split_pass);
-    (void)hipFree(L.d_steal);
-    (void)hipFree(L.d_split_n);
-    (void)hipFree(L.d_sort_tmp);
-    if (L.freed) (void)hipEventDestroy(L.freed);
-    if (L.tail) (void)hipEventDestroy(L.tail);
-    if (L.stream) (void)hipStreamDestroy(L.stream);
-  }
-  (void)hipFree(c->d_slots);
-  (void)hipFree(c->d_queue);
-  (void)hipFree(c->d_sctr);
-  if (c->h_sctr) (void)hipHostFree(c->h_sctr);
-  for (hipEvent_t e : c->batch_ev) if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : c->pool_ev) if (e) (void)hipEventDestroy(e);
-  for (hipStream_t st : c->pool_stream) if (st) (void)hipStreamDestroy(st);
-  for (const std::vector<hipEvent_t>& v : c->evs)
-    for (hipEvent_t e : v) (void)hipEventDestroy(e);
-  if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-  delete c;
+  for (auto& L : c->lanes) if (L.stream) (void)hipStreamSynchronize(L.stream);
+  delete c;   // (every member frees what it owns: mcpt_owned.h)
   return MCPT_OK;
 }
 
@@ -336,21 +281,22 @@ int mcpt_upload_scene(mcpt_ctx* c, const float* prims, int n_prims, const float*
   }
   HIP_OR_RETURN(hipSetDevice(c->device));
   HIP_OR_RETURN(hipStreamSynchronize(c->stream));
-  free_scene(c);
-  HIP_OR_RETURN(hipMalloc(&c->d_nodes, hn.size() * sizeof(float4)));
-  HIP_OR_RETURN(hipMalloc(&c->d_leaves, (size_t)n_leaf * sizeof(int)));
-  HIP_OR_RETURN(hipMalloc(&c->d_ptype, (size_t)n_prims * sizeof(int)));
-  HIP_OR_RETURN(hipMalloc(&c->d_prims, hp.size() * sizeof(float4)));
-  HIP_OR_RETURN(hipMemcpy(c->d_nodes, hn.data(), hn.size() * sizeof(float4), hipMemcpyHostToDevice));
-  HIP_OR_RETURN(hipMemcpy(c->d_leaves, leaves, (size_t)n_leaf * sizeof(int), hipMemcpyHostToDevice));
-  HIP_OR_RETURN(hipMemcpy(c->d_ptype, ht.data(), (size_t)n_prims * sizeof(int), hipMemcpyHostToDevice));
-  HIP_OR_RETURN(hipMemcpy(c->d_prims, hp.data(), hp.size() * sizeof(float4), hipMemcpyHostToDevice));
+  c->scene = {};   // (the previous scene goes first: the two need not fit side by side)
+  mcpt_ctx::Scene sc;
+  HIP_OR_RETURN(sc.d_nodes.alloc(hn.size()));
+  HIP_OR_RETURN(sc.d_leaves.alloc((size_t)n_leaf));
+  HIP_OR_RETURN(sc.d_ptype.alloc((size_t)n_prims));
+  HIP_OR_RETURN(sc.d_prims.alloc(hp.size()));
+  HIP_OR_RETURN(hipMemcpy(sc.d_nodes, hn.data(), sc.d_nodes.bytes(), hipMemcpyHostToDevice));
+  HIP_OR_RETURN(hipMemcpy(sc.d_leaves, leaves, sc.d_leaves.bytes(), hipMemcpyHostToDevice));
+  HIP_OR_RETURN(hipMemcpy(sc.d_ptype, ht.data(), sc.d_ptype.bytes(), hipMemcpyHostToDevice));
+  HIP_OR_RETURN(hipMemcpy(sc.d_prims, hp.data(), sc.d_prims.bytes(), hipMemcpyHostToDevice));
+  sc.has_scene = true; c->scene = std::move(sc);
   c->n_prims = n_prims; c->depth = c->tuner.depth = depth; c->nb_emissive = nb_emissives;
   c->mesh_ids = mesh_ids;
-  c->guides_valid = false;
-  c->tp_frames = 0;               // (temporal mode: the history shows another scene)
-  free_meshes(c);                 // a new scene drops the previous meshes (upload them again)
-  c->has_scene = true;
+  c->denoise.guides_valid = false;
+  c->temporal.tp_frames = 0;      // (temporal mode: the history shows another scene)
+  c->meshes = {};                 // a new scene drops the previous meshes (upload them again)
   reset_tuning(c);
   return MCPT_OK;
 }
@@ -407,12 +353,12 @@ int mcpt_upload_meshes(mcpt_ctx* c, int n_meshes, const int* info, int n_nodes, 
                        const int* leaves, int n_tris, const int* tris, int n_verts, const float* verts,
                        const float* normals) {
   if (!c || n_meshes < 0) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_upload_meshes: bad arguments");
-  if (!c->has_scene) return set_err(MCPT_ERR_NO_SCENE, "upload the scene before its meshes");
+  if (!c->scene.has_scene) return set_err(MCPT_ERR_NO_SCENE, "upload the scene before its meshes");
   HIP_OR_RETURN(hipSetDevice(c->device));
   HIP_OR_RETURN(hipStreamSynchronize(c->stream));
-  free_meshes(c);
-  c->guides_valid = false;
-  c->tp_frames = 0;
+  c->meshes = {};
+  c->denoise.guides_valid = false;
+  c->temporal.tp_frames = 0;
   if (n_meshes == 0) {
     for (int id : c->mesh_ids)
       if (id >= 0) return set_err(MCPT_ERR_BAD_SCENE, "the scene has mesh instances but no meshes were uploaded");
@@ -482,31 +428,32 @@ int mcpt_upload_meshes(mcpt_ctx* c, int n_meshes, const int* info, int n_nodes, 
       r[2] = make_float4(C.x - A.x, C.y - A.y, C.z - A.z, 0.0f);
     }
   }
-  HIP_OR_RETURN(hipMalloc(&c->d_minfo, hi.size() * sizeof(int4)));
   // one allocation: the pair slots, then the leaf records (walk_run_mesh addresses both by 32-bit
   // byte offsets from d_mpairs)
   if ((hn.size() + hl.size()) * sizeof(float4) > (size_t(1) << 32))
     return set_err(MCPT_ERR_BAD_SCENE, "mesh BVH records exceed 4 GiB");
-  HIP_OR_RETURN(hipMalloc(&c->d_mpairs, (hn.size() + hl.size()) * sizeof(float4)));
-  c->d_mleaftris = c->d_mpairs + hn.size();
-  HIP_OR_RETURN(hipMalloc(&c->d_mtris, ht.size() * sizeof(int4)));
-  HIP_OR_RETURN(hipMalloc(&c->d_mverts, hv.size() * sizeof(float4)));
-  HIP_OR_RETURN(hipMalloc(&c->d_mnorms, hm.size() * sizeof(float4)));
-  HIP_OR_RETURN(hipMemcpy(c->d_minfo, hi.data(), hi.size() * sizeof(int4), hipMemcpyHostToDevice));
-  HIP_OR_RETURN(hipMemcpy(c->d_mpairs, hn.data(), hn.size() * sizeof(float4), hipMemcpyHostToDevice));
-  HIP_OR_RETURN(hipMemcpy(c->d_mleaftris, hl.data(), hl.size() * sizeof(float4), hipMemcpyHostToDevice));
-  HIP_OR_RETURN(hipMemcpy(c->d_mtris, ht.data(), ht.size() * sizeof(int4), hipMemcpyHostToDevice));
-  HIP_OR_RETURN(hipMemcpy(c->d_mverts, hv.data(), hv.size() * sizeof(float4), hipMemcpyHostToDevice));
-  HIP_OR_RETURN(hipMemcpy(c->d_mnorms, hm.data(), hm.size() * sizeof(float4), hipMemcpyHostToDevice));
-  c->n_meshes = n_meshes;
+  mcpt_ctx::Meshes ms;
+  HIP_OR_RETURN(ms.d_minfo.alloc(hi.size()));
+  HIP_OR_RETURN(ms.d_mpairs.alloc(hn.size() + hl.size()));
+  ms.d_mleaftris = ms.d_mpairs + hn.size();
+  HIP_OR_RETURN(ms.d_mtris.alloc(ht.size()));
+  HIP_OR_RETURN(ms.d_mverts.alloc(hv.size()));
+  HIP_OR_RETURN(ms.d_mnorms.alloc(hm.size()));
+  HIP_OR_RETURN(hipMemcpy(ms.d_minfo, hi.data(), hi.size() * sizeof(int4), hipMemcpyHostToDevice));
+  HIP_OR_RETURN(hipMemcpy(ms.d_mpairs, hn.data(), hn.size() * sizeof(float4), hipMemcpyHostToDevice));
+  HIP_OR_RETURN(hipMemcpy(ms.d_mleaftris, hl.data(), hl.size() * sizeof(float4), hipMemcpyHostToDevice));
+  HIP_OR_RETURN(hipMemcpy(ms.d_mtris, ht.data(), ht.size() * sizeof(int4), hipMemcpyHostToDevice));
+  HIP_OR_RETURN(hipMemcpy(ms.d_mverts, hv.data(), hv.size() * sizeof(float4), hipMemcpyHostToDevice));
+  HIP_OR_RETURN(hipMemcpy(ms.d_mnorms, hm.data(), hm.size() * sizeof(float4), hipMemcpyHostToDevice));
+  ms.n_meshes = n_meshes; c->meshes = std::move(ms);
   return MCPT_OK;
 }
 
 int mcpt_set_flat_face(mcpt_ctx* c, int flat_face) {
   if (!c) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
   c->flat_face = flat_face ? 1 : 0;
-  c->guides_valid = false;
-  c->tp_frames = 0;
+  c->denoise.guides_valid = false;
+  c->temporal.tp_frames = 0;
   return MCPT_OK;
 }
 
@@ -519,29 +466,22 @@ static int set_target_rows(mcpt_ctx* c, int W, int H, const int* rows, int n_row
     return set_err(MCPT_ERR_INVALID_ARG, "mcpt_set_target: a shard of 2^31 pixels or more");
   HIP_OR_RETURN(hipSetDevice(c->device));
   HIP_OR_RETURN(hipStreamSynchronize(c->stream));
-  free_denoise(c);   // (sized by the target; allocated again by the next guides / denoise call)
-  free_stats(c);     // (statistics off: a new target begins again)
-  free_adaptive(c);  // (adaptive mode off: its blocks are the old target's)
-  free_count_plane(c);   // (a gathered frame's counts are the old target's)
-  free_temporal(c);  // (temporal mode off: its history is the old target's)
-  size_t bytes = (size_t)n_rows * W * 3 * sizeof(float);
-  if (bytes != c->accum_bytes) {
-    (void)hipFree(c->d_accum);
-    c->d_accum = nullptr;
-    c->accum_bytes = 0;
-    if (bytes) HIP_OR_RETURN(hipMalloc(&c->d_accum, bytes));
-    c->accum_bytes = bytes;
+  c->denoise = {};    // (sized by the target; allocated again by the next guides / denoise call)
+  c->stats = {};      // (statistics off: a new target begins again)
+  c->adaptive = {};   // (adaptive mode off: its blocks are the old target's)
+  c->planes = {};     // (a gathered frame's counts are the old target's)
+  c->temporal = {};   // (temporal mode off: its history is the old target's)
+  for (auto& L : c->lanes) L.drop_target_sized();   // (segment sums, steal store, item order: other pixels)
+  const size_t n_accum = (size_t)n_rows * W * 3;
+  if (n_accum != c->target.d_accum.size()) {
+    c->target.d_accum.reset();
+    if (n_accum) HIP_OR_RETURN(c->target.d_accum.alloc(n_accum));
   }
-  if ((size_t)n_rows != c->rows.size() || !c->d_rows) {
-    (void)hipFree(c->d_rows);
-    c->d_rows = nullptr;
-    HIP_OR_RETURN(hipMalloc(&c->d_rows, sizeof(int) * (size_t)std::max(n_rows, 1)));
-  }
+  if ((size_t)std::max(n_rows, 1) != c->target.d_rows.size()) HIP_OR_RETURN(c->target.d_rows.alloc((size_t)std::max(n_rows, 1)));
   c->rows.assign(rows, rows + n_rows);
-  if (n_rows) HIP_OR_RETURN(hipMemcpy(c->d_rows, rows, sizeof(int) * (size_t)n_rows, hipMemcpyHostToDevice));
+  if (n_rows) HIP_OR_RETURN(hipMemcpy(c->target.d_rows, rows, sizeof(int) * (size_t)n_rows, hipMemcpyHostToDevice));
   c->W = W; c->H = H; c->band_rows = band_rows; c->world = world; c->rank = rank; c->n_local_rows = n_rows;
   c->has_target = true;
-  for (auto& L : c->lanes) L.order_valid = false;   // other pixels: the item costs start over
   return mcpt_clear_accum(c);
 }
 
@@ -610,7 +550,7 @@ int mcpt_clear_accum(mcpt_ctx* c) {
   if (!c) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
   if (!c->has_target) return mcpt_err_bare(MCPT_ERR_NO_TARGET);
   HIP_OR_RETURN(hipSetDevice(c->device));
-  if (c->accum_bytes) HIP_OR_RETURN(hipMemsetAsync(c->d_accum, 0, c->accum_bytes, c->stream));
+  if (c->target.d_accum.bytes()) HIP_OR_RETURN(hipMemsetAsync(c->target.d_accum, 0, c->target.d_accum.bytes(), c->stream));
   c->pass_count = 0;
   invalidate_planes(c);
   return MCPT_OK;
@@ -679,29 +619,24 @@ static int stream_run(mcpt_ctx* c, const mcpt::RenderParams& p) {
     pool_n[k] = (int)(n_slots / n_pools + (k < n_slots % n_pools ? 1 : 0));
     if (pool_n[k] > 0) np = k + 1;
   }
-  if (n_slots > c->slot_cap) {
+  const size_t slot_floats = (size_t)mcpt::SF_COUNT * n_slots, queue_floats = (size_t)2 * mcpt::QF_COUNT * n_slots;
+  if (slot_floats > c->pools.d_slots.size() || queue_floats > c->pools.d_queue.size()) {
     HIP_OR_RETURN(hipStreamSynchronize(c->stream));
-    (void)hipFree(c->d_slots); (void)hipFree(c->d_queue);
-    c->d_slots = nullptr; c->d_queue = nullptr; c->slot_cap = 0;
-    HIP_OR_RETURN(hipMalloc(&c->d_slots, (size_t)mcpt::SF_COUNT * n_slots * sizeof(float)));
-    HIP_OR_RETURN(hipMalloc(&c->d_queue, (size_t)2 * mcpt::QF_COUNT * n_slots * sizeof(float)));
-    c->slot_cap = n_slots;
+    c->pools.d_slots.reset(); c->pools.d_queue.reset();   // (both go before either grows)
   }
-  if (!c->d_sctr) HIP_OR_RETURN(hipMalloc(&c->d_sctr, kStreamPools * mcpt::SC_COUNT * sizeof(unsigned)));
-  if (!c->h_sctr)
-    HIP_OR_RETURN(hipHostMalloc(&c->h_sctr, 2 * kStreamPools * mcpt::SC_COUNT * sizeof(unsigned), hipHostMallocDefault));
-  for (hipEvent_t& e : c->batch_ev)
-    if (!e) HIP_OR_RETURN(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  for (hipEvent_t& e : c->pool_ev)
-    if (!e) HIP_OR_RETURN(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  for (hipStream_t& st : c->pool_stream)
-    if (!st) HIP_OR_RETURN(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+  HIP_OR_RETURN(c->pools.d_slots.ensure(slot_floats));
+  HIP_OR_RETURN(c->pools.d_queue.ensure(queue_floats));
+  HIP_OR_RETURN(c->pools.d_sctr.ensure(kStreamPools * mcpt::SC_COUNT));
+  HIP_OR_RETURN(c->pools.h_sctr.ensure(2 * kStreamPools * mcpt::SC_COUNT));
+  for (Event& e : c->pools.batch_ev) HIP_OR_RETURN(e.ensure(hipEventDisableTiming));
+  for (Event& e : c->pools.pool_ev) HIP_OR_RETURN(e.ensure(hipEventDisableTiming));
+  for (Stream& st : c->pools.pool_stream) HIP_OR_RETURN(st.ensure(hipStreamNonBlocking));
   // BVH nodes in the trace kernel's LDS where they fit (MCPT_STREAM_LDS_NODES=1): off by default,
   // no faster on scenes 3/7/8 (random lanes' node reads conflict in the LDS banks, 11 conflict
   // cycles per LDS instruction; gpurun_out r03e/r03f)
   const bool lds_nodes = env_int("MCPT_STREAM_LDS_NODES", 0) != 0 && p.n_meshes == 0 && mcpt_stream_lds_nodes_fit(p.depth);
   mcpt::StreamParams q[kStreamPools];
-  unsigned* unit_ctr = c->d_sctr + mcpt::SC_UNIT;   // pool 0's slot: shared
+  unsigned* unit_ctr = c->pools.d_sctr + mcpt::SC_UNIT;   // pool 0's slot: shared
   {
     const unsigned first_free = (unsigned)n_slots;   // units 0 .. n_slots-1 start in the pools' slots
     HIP_OR_RETURN(hipMemcpyAsync(unit_ctr, &first_free, sizeof(unsigned), hipMemcpyHostToDevice, c->stream));
@@ -715,10 +650,10 @@ static int stream_run(mcpt_ctx* c, const mcpt::RenderParams& p) {
     // +4 % over 8 and 32, 4 is -8 %)
     if (c->leaf_batch < 0) s.r.leaf_batch = 16;
     // field f of pool entry i at queue[par][f * n + i], slot data likewise: laid out per pool
-    s.slots = c->d_slots + slot_off;
-    s.queue[0] = c->d_queue + queue_off;
+    s.slots = c->pools.d_slots + slot_off;
+    s.queue[0] = c->pools.d_queue + queue_off;
     s.queue[1] = s.queue[0] + (size_t)mcpt::QF_COUNT * pool_n[k];
-    s.ctr = c->d_sctr + k * mcpt::SC_COUNT;
+    s.ctr = c->pools.d_sctr + k * mcpt::SC_COUNT;
     s.unit_ctr = unit_ctr;
     s.n_slots = pool_n[k];
     s.unit_base = unit_base;
@@ -732,8 +667,8 @@ static int stream_run(mcpt_ctx* c, const mcpt::RenderParams& p) {
     HIP_OR_RETURN(mcpt_launch_stream_init(s, c->stream));
   }
   // fork: the pool streams start after the set-up (and everything before it) on the context's stream
-  HIP_OR_RETURN(hipEventRecord(c->pool_ev[2], c->stream));
-  for (int k = 0; k < np; ++k) HIP_OR_RETURN(hipStreamWaitEvent(c->pool_stream[k], c->pool_ev[2], 0));
+  HIP_OR_RETURN(hipEventRecord(c->pools.pool_ev[2], c->stream));
+  for (int k = 0; k < np; ++k) HIP_OR_RETURN(hipStreamWaitEvent(c->pools.pool_stream[k], c->pools.pool_ev[2], 0));
   // every iteration advances each live slot by one traversal; a unit needs at most
   // (passes) x (2 B + 1) + 1 of them, and a slot runs ceil(units / slots) units
   const long long per_unit = (long long)mcpt::kPassChunk * (2LL * p.bounces + 1) + 1;
@@ -748,22 +683,22 @@ static int stream_run(mcpt_ctx* c, const mcpt::RenderParams& p) {
         if (done[j]) continue;
         q[j].parity = (int)(it & 1);
         q[j].compact = (k == 0 && compact[j]) ? 1 : 0;
-        HIP_OR_RETURN(mcpt_launch_stream_iter(q[j], c->n_cu, lds_nodes, c->pool_stream[j]));
+        HIP_OR_RETURN(mcpt_launch_stream_iter(q[j], c->n_cu, lds_nodes, c->pools.pool_stream[j]));
       }
     // every pool's counters after the batch, read on pool 0's stream once all pools are there
     for (int j = 1; j < np; ++j) {
-      HIP_OR_RETURN(hipEventRecord(c->pool_ev[j], c->pool_stream[j]));
-      HIP_OR_RETURN(hipStreamWaitEvent(c->pool_stream[0], c->pool_ev[j], 0));
+      HIP_OR_RETURN(hipEventRecord(c->pools.pool_ev[j], c->pools.pool_stream[j]));
+      HIP_OR_RETURN(hipStreamWaitEvent(c->pools.pool_stream[0], c->pools.pool_ev[j], 0));
     }
-    unsigned* h = c->h_sctr + (b & 1) * kStreamPools * mcpt::SC_COUNT;
-    HIP_OR_RETURN(hipMemcpyAsync(h, c->d_sctr, (size_t)np * mcpt::SC_COUNT * sizeof(unsigned), hipMemcpyDeviceToHost,
-                                 c->pool_stream[0]));
-    HIP_OR_RETURN(hipEventRecord(c->batch_ev[b & 1], c->pool_stream[0]));
+    unsigned* h = c->pools.h_sctr + (b & 1) * kStreamPools * mcpt::SC_COUNT;
+    HIP_OR_RETURN(hipMemcpyAsync(h, c->pools.d_sctr, (size_t)np * mcpt::SC_COUNT * sizeof(unsigned), hipMemcpyDeviceToHost,
+                                 c->pools.pool_stream[0]));
+    HIP_OR_RETURN(hipEventRecord(c->pools.batch_ev[b & 1], c->pools.pool_stream[0]));
     if (b >= 1) {
-      HIP_OR_RETURN(hipEventSynchronize(c->batch_ev[(b - 1) & 1]));
+      HIP_OR_RETURN(hipEventSynchronize(c->pools.batch_ev[(b - 1) & 1]));
       bool all = true;
       for (int j = 0; j < np; ++j) {
-        const unsigned* hp = c->h_sctr + ((b - 1) & 1) * kStreamPools * mcpt::SC_COUNT + j * mcpt::SC_COUNT;
+        const unsigned* hp = c->pools.h_sctr + ((b - 1) & 1) * kStreamPools * mcpt::SC_COUNT + j * mcpt::SC_COUNT;
         const unsigned dead = hp[mcpt::SC_DEAD];
         done[j] = dead >= (unsigned)pool_n[j];   // every slot of the pool was done by the end of batch b-1
         all = all && done[j];
@@ -783,10 +718,10 @@ static int stream_run(mcpt_ctx* c, const mcpt::RenderParams& p) {
   // synchronizing its own stream, so that stream must not run ahead of them.
   bool joined = true;
   for (int j = 0; j < np; ++j)
-    joined = joined && hipEventRecord(c->pool_ev[j], c->pool_stream[j]) == hipSuccess &&
-             hipStreamWaitEvent(c->stream, c->pool_ev[j], 0) == hipSuccess;
+    joined = joined && hipEventRecord(c->pools.pool_ev[j], c->pools.pool_stream[j]) == hipSuccess &&
+             hipStreamWaitEvent(c->stream, c->pools.pool_ev[j], 0) == hipSuccess;
   if (!joined)   // cannot order them: wait for them here
-    for (int j = 0; j < np; ++j) (void)hipStreamSynchronize(c->pool_stream[j]);
+    for (int j = 0; j < np; ++j) (void)hipStreamSynchronize(c->pools.pool_stream[j]);
   if (st != MCPT_OK) return st;
   if (!joined) return set_err(MCPT_ERR_HIP, "stream schedule: joining the pool streams failed");
   c->stream_iters += it;
@@ -795,42 +730,36 @@ static int stream_run(mcpt_ctx* c, const mcpt::RenderParams& p) {
 
 // the stream schedule's pools (4 GB at the default 16 Mi slots), once no longer selected
 static int free_stream_pools(mcpt_ctx* c) {
-  if (!c->d_slots && !c->d_queue) return MCPT_OK;
+  if (!c->pools.d_slots && !c->pools.d_queue) return MCPT_OK;
   HIP_OR_RETURN(hipSetDevice(c->device));
   HIP_OR_RETURN(hipStreamSynchronize(c->stream));
-  (void)hipFree(c->d_slots); (void)hipFree(c->d_queue);
-  c->d_slots = nullptr; c->d_queue = nullptr; c->slot_cap = 0;
+  c->pools.d_slots.reset(); c->pools.d_queue.reset();
   return MCPT_OK;
 }
 
 // Buffers of the work-item order for `items` items (grown on demand, with the identity values
 // the sort permutes and its temporary storage)
 static hipError_t ensure_item_order(mcpt_ctx* c, mcpt_ctx::Lane& L, long long items) {
-  if (items <= L.item_cap) return hipSuccess;
+  if (items <= L.order.cap()) return hipSuccess;
   hipError_t e = hipStreamSynchronize(c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(L.stream);
   if (e != hipSuccess) return e;
-  (void)hipFree(L.d_item_cost); (void)hipFree(L.d_cost_sorted); (void)hipFree(L.d_item_iota);
-  (void)hipFree(L.d_item_perm); (void)hipFree(L.d_sort_tmp); (void)hipFree(L.d_split_of);
-  L.d_item_cost = L.d_cost_sorted = nullptr; L.d_item_iota = L.d_item_perm = nullptr; L.d_sort_tmp = nullptr;
-  L.d_split_of = nullptr;
-  L.item_cap = 0; L.sort_tmp_bytes = 0; L.order_valid = false;
-  const size_t n = (size_t)items;
-  size_t tmp = 0;
-  if ((e = hipMalloc(&L.d_item_cost, sizeof(unsigned) * n)) != hipSuccess) return e;
-  if ((e = hipMalloc(&L.d_cost_sorted, sizeof(unsigned) * n)) != hipSuccess) return e;
-  if ((e = hipMalloc(&L.d_item_iota, sizeof(int) * n)) != hipSuccess) return e;
-  if ((e = hipMalloc(&L.d_item_perm, sizeof(int) * n)) != hipSuccess) return e;
-  if ((e = hipMalloc(&L.d_split_of, sizeof(int) * n)) != hipSuccess) return e;
-  if (!L.d_split_n && (e = hipMalloc(&L.d_split_n, sizeof(int))) != hipSuccess) return e;
-  if ((e = hipMemset(L.d_split_n, 0, sizeof(int))) != hipSuccess) return e;
+  L.order = {};
+  mcpt_ctx::Lane::Order o;
+  size_t n = (size_t)items, tmp = 0;
+  if ((e = o.d_item_cost.alloc(n)) != hipSuccess) return e;
+  if ((e = o.d_cost_sorted.alloc(n)) != hipSuccess) return e;
+  if ((e = o.d_item_iota.alloc(n)) != hipSuccess) return e;
+  if ((e = o.d_item_perm.alloc(n)) != hipSuccess) return e;
+  if ((e = o.d_split_of.alloc(n)) != hipSuccess) return e;
+  if ((e = o.d_split_n.alloc(1)) != hipSuccess) return e;
+  if ((e = hipMemset(o.d_split_n, 0, sizeof(int))) != hipSuccess) return e;
   if ((e = mcpt_order_items(nullptr, nullptr, nullptr, nullptr, (int)items, nullptr, &tmp, c->stream)) != hipSuccess)
     return e;
-  if ((e = hipMalloc(&L.d_sort_tmp, std::max<size_t>(tmp, 1))) != hipSuccess) return e;
-  if ((e = mcpt_iota(L.d_item_iota, (int)items, c->stream)) != hipSuccess) return e;
+  if ((e = o.d_sort_tmp.alloc(std::max<size_t>(tmp, 1))) != hipSuccess) return e;
+  if ((e = mcpt_iota(o.d_item_iota, (int)items, c->stream)) != hipSuccess) return e;
   if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return e;
-  L.sort_tmp_bytes = tmp;
-  L.item_cap = items;
+  L.order = std::move(o);
   return hipSuccess;
 }
 
@@ -861,19 +790,19 @@ extern "C++" int checked_sub_launch(mcpt_ctx* c, int k, int n_sub, const mcpt::R
 // a render launch's scene, target and camera fields (launch(), mcpt_render_adaptive, mcpt_render_guides)
 extern "C++" void scene_params(const mcpt_ctx* c, const float* invPV, const float* invV, mcpt::RenderParams& p) {
   std::memset(&p, 0, sizeof(p));
-  p.nodes = c->d_nodes; p.leaves = c->d_leaves; p.ptype = c->d_ptype; p.prims = c->d_prims;
-  p.accum = c->d_accum; p.events = c->d_events;
+  p.nodes = c->scene.d_nodes; p.leaves = c->scene.d_leaves; p.ptype = c->scene.d_ptype; p.prims = c->scene.d_prims;
+  p.accum = c->target.d_accum; p.events = c->d_events;
   corner_rays(invPV, invV, p);
-  p.W = c->W; p.H = c->H; p.rows = c->d_rows;
+  p.W = c->W; p.H = c->H; p.rows = c->target.d_rows;
   p.n_local_rows = c->n_local_rows; p.depth = c->depth; p.n_prims = c->n_prims;
   {
     const long long lds = ((3LL * ((2LL << c->depth) - 1) + (long long)mcpt::kPrimF4 * c->n_prims) * 16) +
                           (((1LL << c->depth) + c->n_prims) * 4);
     p.lds_scene_bytes = lds <= mcpt::kLdsSceneBytes ? (int)lds : 0;
   }
-  p.minfo = c->d_minfo; p.mpairs = c->d_mpairs; p.mleaftris = c->d_mleaftris; p.mtris = c->d_mtris;
-  p.mverts = c->d_mverts; p.mnorms = c->d_mnorms; p.n_meshes = c->n_meshes; p.flat_face = c->flat_face;
-  p.tile_w = mcpt::tile_w_for(c->n_meshes > 0, p.lds_scene_bytes);
+  p.minfo = c->meshes.d_minfo; p.mpairs = c->meshes.d_mpairs; p.mleaftris = c->meshes.d_mleaftris; p.mtris = c->meshes.d_mtris;
+  p.mverts = c->meshes.d_mverts; p.mnorms = c->meshes.d_mnorms; p.n_meshes = c->meshes.n_meshes; p.flat_face = c->flat_face;
+  p.tile_w = mcpt::tile_w_for(c->meshes.n_meshes > 0, p.lds_scene_bytes);
   p.n_local_px = (long long)c->n_local_rows * c->W;
 }
 
@@ -899,9 +828,9 @@ extern "C++" int check_renderable(const mcpt_ctx* c, bool args_ok, const char* w
     std::snprintf(what, sizeof(what), "%s: bad arguments", who);
     return set_err(MCPT_ERR_INVALID_ARG, what);
   }
-  if (!c->has_scene) return set_err(MCPT_ERR_NO_SCENE, "no scene uploaded");
+  if (!c->scene.has_scene) return set_err(MCPT_ERR_NO_SCENE, "no scene uploaded");
   if (!c->has_target) return set_err(MCPT_ERR_NO_TARGET, "no render target");
-  if (c->n_meshes == 0)
+  if (c->meshes.n_meshes == 0)
     for (int id : c->mesh_ids)
       if (id >= 0) return set_err(MCPT_ERR_BAD_SCENE, "mesh instances present: call mcpt_upload_meshes");
   return MCPT_OK;
@@ -913,7 +842,7 @@ static hipEvent_t lane_freed(mcpt_ctx* c, mcpt_ctx::Lane& X) {
   return X.freed;
 }
 static bool holds_order(const mcpt_ctx::Lane& L, const plan::Items& it) {
-  return L.order_valid && std::equal(it.key, it.key + 8, L.order_key);
+  return L.order.valid && std::equal(it.key, it.key + 8, L.order.key);
 }
 
 // An ordered sub-launch on lane li (its render and set-up on `ws`): the order it runs, its tail
@@ -924,55 +853,52 @@ static int prepare_order(mcpt_ctx* c, int li, hipStream_t ws, const plan::ItemsI
   // the other lane holds this shape's order (AUTO's trials alternate candidates between the
   // lanes; a new shape's first launches): copied once its last sort is done, so that a trial
   // runs the order a settled launch of its candidate would
-  if (!holds_order(L, it) && holds_order(O, it) && O.item_cap >= it.items) {
+  if (!holds_order(L, it) && holds_order(O, it) && O.order.cap() >= it.items) {
     HIP_OR_RETURN(hipStreamWaitEvent(ws, O.tail, 0));
     HIP_OR_RETURN(hipStreamWaitEvent(ws, lane_freed(c, O), 0));
-    HIP_OR_RETURN(hipMemcpyAsync(L.d_item_perm, O.d_item_perm, sizeof(int) * (size_t)it.items, hipMemcpyDeviceToDevice, ws));
-    HIP_OR_RETURN(hipMemcpyAsync(L.d_split_n, O.d_split_n, sizeof(int), hipMemcpyDeviceToDevice, ws));
+    HIP_OR_RETURN(hipMemcpyAsync(L.order.d_item_perm, O.order.d_item_perm, sizeof(int) * (size_t)it.items, hipMemcpyDeviceToDevice, ws));
+    HIP_OR_RETURN(hipMemcpyAsync(L.order.d_split_n, O.order.d_split_n, sizeof(int), hipMemcpyDeviceToDevice, ws));
     // (the other lane's next sort, which rewrites its order, waits for the copy)
     HIP_OR_RETURN(hipEventRecord(L.tail, ws));
     HIP_OR_RETURN(hipStreamWaitEvent(O.stream, L.tail, 0));
-    std::copy(it.key, it.key + 8, L.order_key);
-    L.order_valid = true;
-    L.order_age = O.order_age;
+    std::copy(it.key, it.key + 8, L.order.key);
+    L.order.valid = true;
+    L.order.age = O.order.age;
   }
   if (holds_order(L, it)) {
-    p.item_perm = L.d_item_perm;
+    p.item_perm = L.order.d_item_perm;
     p.tail_m = plan::tail_m(in, it, true);
   }
-  HIP_OR_RETURN(hipMemsetAsync(L.d_item_cost, 0, sizeof(unsigned) * (size_t)it.items, ws));
-  p.item_cost = L.d_item_cost;
+  HIP_OR_RETURN(hipMemsetAsync(L.order.d_item_cost, 0, sizeof(unsigned) * (size_t)it.items, ws));
+  p.item_cost = L.order.d_item_cost;
   return MCPT_OK;
 }
 
 // ... its split items' buffers
 static int prepare_split_items(mcpt_ctx::Lane& L, hipStream_t ws, long long items, mcpt::RenderParams& p) {
-  if (!L.d_split_pass) {
-    HIP_OR_RETURN(hipMalloc(&L.d_split_pass, sizeof(float) * 3 * (size_t)plan::kSplitMax * mcpt::kPassChunk *
-                                                 mcpt::kTileThreads));
-  }
-  HIP_OR_RETURN(hipMemsetAsync(L.d_split_of, 0xff, sizeof(int) * (size_t)items, ws));
-  p.split_of = L.d_split_of;
+  HIP_OR_RETURN(L.d_split_pass.ensure(3 * (size_t)plan::kSplitMax * mcpt::kPassChunk * mcpt::kTileThreads));
+  HIP_OR_RETURN(hipMemsetAsync(L.order.d_split_of, 0xff, sizeof(int) * (size_t)items, ws));
+  p.split_of = L.order.d_split_of;
   p.split_pass = L.d_split_pass;
   p.split_max = plan::kSplitMax;
-  if (p.item_perm) p.split_n = L.d_split_n;
+  if (p.item_perm) p.split_n = L.order.d_split_n;
   return MCPT_OK;
 }
 
 // ... and the sort of the costs it measured: after its render (outside its timed events); the
 // lane's next launch of this shape reads the order in stream order, so no host wait
 static int sort_order(mcpt_ctx* c, mcpt_ctx::Lane& L, hipStream_t ws, const plan::Items& it, const mcpt::RenderParams& p) {
-  size_t tmp = L.sort_tmp_bytes;
-  HIP_OR_RETURN(mcpt_order_items(L.d_item_cost, L.d_cost_sorted, L.d_item_iota, L.d_item_perm, (int)it.items,
-                                 L.d_sort_tmp, &tmp, ws));
+  size_t tmp = L.order.d_sort_tmp.size();
+  HIP_OR_RETURN(mcpt_order_items(L.order.d_item_cost, L.order.d_cost_sorted, L.order.d_item_iota, L.order.d_item_perm, (int)it.items,
+                                 L.order.d_sort_tmp, &tmp, ws));
   // mesh scenes: how many of the costliest to split next time (the mesh kernels run 5
   // waves per SIMD: 20 per CU, in workgroups of tile_w / 8 waves)
-  if (c->n_meshes > 0)
-    HIP_OR_RETURN(mcpt_split_count(L.d_cost_sorted, (int)it.items, 20 / (p.tile_w / 8) * c->n_cu, plan::kSplitMax,
-                                   L.d_split_n, c->d_events + kDebugSplitSlot, ws));
-  std::copy(it.key, it.key + 8, L.order_key);
-  L.order_valid = true;
-  L.order_age = 0;
+  if (c->meshes.n_meshes > 0)
+    HIP_OR_RETURN(mcpt_split_count(L.order.d_cost_sorted, (int)it.items, 20 / (p.tile_w / 8) * c->n_cu, plan::kSplitMax,
+                                   L.order.d_split_n, c->d_events + kDebugSplitSlot, ws));
+  std::copy(it.key, it.key + 8, L.order.key);
+  L.order.valid = true;
+  L.order.age = 0;
   return MCPT_OK;
 }
 
@@ -1001,7 +927,7 @@ static int launch(mcpt_ctx* c, const float* invPV, const float* invV, int first_
   const bool stream = cand == plan::kCandStream && stream_applies(c, variant, bounces, count);
   c->stream_iters = 0;
   p.wave_traversal = (cand == MCPT_TRAVERSAL_WAVE) ? 1 : 0;
-  p.walk_exit = plan::cand_walk_exit(cand, c->walk_exit, c->n_meshes, c->depth);
+  p.walk_exit = plan::cand_walk_exit(cand, c->walk_exit, c->meshes.n_meshes, c->depth);
   p.leaf_batch = plan::cand_leaf_batch(cand, c->leaf_batch, c->depth);
   p.walk_min_done = plan::cand_deep_knobs(cand) ? plan::kDeepMinDone : 1;
   // MCPT_WALK_MIN_DONE overrides (tuning hook; same bits for any value)
@@ -1011,12 +937,12 @@ static int launch(mcpt_ctx* c, const float* invPV, const float* invV, int first_
   const bool steal = env_int("MCPT_STEAL", 1) != 0;
   plan::LimitsIn lin;
   lin.n_local_px = p.n_local_px; lin.n_tiles = p.n_tiles; lin.tile_w = p.tile_w; lin.seg_per_item = p.seg_per_item;
-  lin.n_cu = c->n_cu; lin.partial_budget = c->partial_budget; lin.mesh = c->n_meshes > 0;
+  lin.n_cu = c->n_cu; lin.partial_budget = c->partial_budget; lin.mesh = c->meshes.n_meshes > 0;
   lin.wave_traversal = p.wave_traversal != 0; lin.steal = steal;
   // the LDS-scene kernel steals passes inside each wave: timed megakernel launches
   // only, and none of AUTO's trials (their plan and kernel stay the ones the candidates were
   // compared with)
-  const bool scene_steal = steal && p.lds_scene_bytes > 0 && c->n_meshes == 0 && !p.wave_traversal && !count &&
+  const bool scene_steal = steal && p.lds_scene_bytes > 0 && c->meshes.n_meshes == 0 && !p.wave_traversal && !count &&
                            !stream && schedule_settled(c);
   lin.lds_scene = scene_steal;
   const plan::Limits lim = plan::limits(lin);
@@ -1044,7 +970,7 @@ static int launch(mcpt_ctx* c, const float* invPV, const float* invV, int first_
   plan::ItemsIn in;
   in.n_tiles = p.n_tiles; in.seg_per_item = p.seg_per_item; in.walk_exit = p.walk_exit; in.bounces = bounces;
   in.variant = variant; in.tile_w = p.tile_w; in.n_cu = c->n_cu; in.wave_traversal = p.wave_traversal != 0;
-  in.pass_split = split; in.mesh = c->n_meshes > 0;
+  in.pass_split = split; in.mesh = c->meshes.n_meshes > 0;
   // (MCPT_ITEM_ORDER=0: dispatch order b = item, tests and A/B; the same bits either way)
   in.orderable = !count && !stream && env_int("MCPT_ITEM_ORDER", 1) != 0;
   in.split_items_on = env_int("MCPT_SPLIT_ITEMS", 1) != 0;
@@ -1072,7 +998,7 @@ static int launch(mcpt_ctx* c, const float* invPV, const float* invV, int first_
     mcpt_ctx::Lane& L = c->lanes[li];
     const bool lane = lanes_ok && p.n_segments > 1;
     hipStream_t ws = lane ? L.stream : c->stream;   // the stream of the render and its set-up
-    if (p.n_segments > 1) OK_OR_RETURN(ensure_lane_bytes(c, L.d_partial, L.partial_bytes, (size_t)p.n_segments * seg_bytes));
+    if (p.n_segments > 1) OK_OR_RETURN(ensure_lane_bytes(c, L.d_partial, (size_t)p.n_segments * seg_bytes));
     p.partial = L.d_partial;
     if (it.order) HIP_OR_RETURN(ensure_item_order(c, L, it.items));
     if (lane) HIP_OR_RETURN(hipStreamWaitEvent(L.stream, lane_freed(c, L), 0));
@@ -1083,7 +1009,7 @@ static int launch(mcpt_ctx* c, const float* invPV, const float* invV, int first_
     // one segment add into the accumulator themselves, pass-split ones run one pass per item:
     // neither steals); the store of every pass's value
     if (lim.may_steal && (it.split_items || (scene_steal && p.n_segments > 1 && !split))) {
-      OK_OR_RETURN(ensure_lane_bytes(c, L.d_steal, L.steal_bytes,
+      OK_OR_RETURN(ensure_lane_bytes(c, L.d_steal,
                                      (size_t)plan::steal_store_bytes(p.n_tiles, p.tile_w, p.n_segments)));
       p.steal_vals = L.d_steal;
     }
@@ -1107,7 +1033,7 @@ static int launch(mcpt_ctx* c, const float* invPV, const float* invV, int first_
     }
     HIP_OR_RETURN(mcpt_launch_combine(p, c->stream));
     HIP_OR_RETURN(hipEventRecord(ev_at(c, slot, k, 2), c->stream));
-    if (it.order && (!p.item_perm || ++L.order_age >= plan::kOrderRefresh)) OK_OR_RETURN(sort_order(c, L, ws, it, p));
+    if (it.order && (!p.item_perm || ++L.order.age >= plan::kOrderRefresh)) OK_OR_RETURN(sort_order(c, L, ws, it, p));
     if (lane) {   // `stream` stays ordered after all of the lane's work; the lane is free after it
       HIP_OR_RETURN(hipEventRecord(L.tail, L.stream));
       HIP_OR_RETURN(hipStreamWaitEvent(c->stream, L.tail, 0));
@@ -1131,10 +1057,10 @@ static int launch(mcpt_ctx* c, const float* invPV, const float* invV, int first_
   c->timed = true;
   c->pass_count += n_passes;
   // adaptive mode on: a plain render reaches every pixel, retired blocks included
-  if (c->ad_on && n_passes > 0)
+  if (c->adaptive.ad_on && n_passes > 0)
     HIP_OR_RETURN(mcpt_launch_adaptive_add_passes(adaptive_target(c), nullptr, 0, n_passes, c->stream));
   // noise statistics on: the call is one batch, behind its last combine
-  if (c->stats_on && n_passes > 0) HIP_OR_RETURN(stats_batch(c, n_passes));
+  if (c->stats.stats_on && n_passes > 0) HIP_OR_RETURN(stats_batch(c, n_passes));
   if (count) {
     unsigned long long h[mcpt::EV_COUNT];
     HIP_OR_RETURN(hipMemcpyAsync(h, c->d_events, sizeof(h), hipMemcpyDeviceToHost, c->stream));
@@ -1189,8 +1115,8 @@ int mcpt_read_accum(mcpt_ctx* c, float* rgb_out, int* pass_count) {
   if (!c) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
   if (!c->has_target) return mcpt_err_bare(MCPT_ERR_NO_TARGET);
   HIP_OR_RETURN(hipSetDevice(c->device));
-  if (rgb_out && c->accum_bytes)
-    HIP_OR_RETURN(hipMemcpyAsync(rgb_out, c->d_accum, c->accum_bytes, hipMemcpyDeviceToHost, c->stream));
+  if (rgb_out && c->target.d_accum.bytes())
+    HIP_OR_RETURN(hipMemcpyAsync(rgb_out, c->target.d_accum, c->target.d_accum.bytes(), hipMemcpyDeviceToHost, c->stream));
   HIP_OR_RETURN(hipStreamSynchronize(c->stream));
   if (pass_count) *pass_count = c->pass_count;
   return MCPT_OK;
@@ -1200,8 +1126,8 @@ int mcpt_write_accum(mcpt_ctx* c, const float* rgb, int pass_count) {
   if (!c || !rgb || pass_count < 0) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
   if (!c->has_target) return mcpt_err_bare(MCPT_ERR_NO_TARGET);
   HIP_OR_RETURN(hipSetDevice(c->device));
-  if (c->accum_bytes)
-    HIP_OR_RETURN(hipMemcpyAsync(c->d_accum, rgb, c->accum_bytes, hipMemcpyHostToDevice, c->stream));
+  if (c->target.d_accum.bytes())
+    HIP_OR_RETURN(hipMemcpyAsync(c->target.d_accum, rgb, c->target.d_accum.bytes(), hipMemcpyHostToDevice, c->stream));
   HIP_OR_RETURN(hipStreamSynchronize(c->stream));
   c->pass_count = pass_count;
   invalidate_planes(c);
@@ -1257,29 +1183,30 @@ int mcpt_checkpoint_load(mcpt_ctx* c, const char* path, const char* tag, int* ne
 int mcpt_accum_device_ptr(mcpt_ctx* c, void** dev_ptr, size_t* bytes) {
   if (!c || !dev_ptr) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
   if (!c->has_target) return mcpt_err_bare(MCPT_ERR_NO_TARGET);
-  *dev_ptr = c->d_accum;
-  if (bytes) *bytes = c->accum_bytes;
+  *dev_ptr = c->target.d_accum;
+  if (bytes) *bytes = c->target.d_accum.bytes();
   return MCPT_OK;
 }
 
 int mcpt_trace(mcpt_ctx* c, const float* origins, const float* dirs, int n, int any_hit, int prim, mcpt_hit* out) {
   if (!c || n < 0 || (n > 0 && (!origins || !dirs || !out))) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_trace: bad arguments");
-  if (!c->has_scene) return set_err(MCPT_ERR_NO_SCENE, "no scene uploaded");
+  if (!c->scene.has_scene) return set_err(MCPT_ERR_NO_SCENE, "no scene uploaded");
   if (prim >= c->n_prims) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_trace: primitive index out of range");
-  if (c->n_meshes == 0)
+  if (c->meshes.n_meshes == 0)
     for (int id : c->mesh_ids)
       if (id >= 0) return set_err(MCPT_ERR_BAD_SCENE, "mesh instances present: call mcpt_upload_meshes");
   if (n == 0) return MCPT_OK;
   HIP_OR_RETURN(hipSetDevice(c->device));
   const size_t n3 = (size_t)n * 3 * sizeof(float), ni = (size_t)n * 3 * sizeof(int);
   const size_t nf = (size_t)n * mcpt::kTraceFloats * sizeof(float);
-  char* buf = nullptr;
-  HIP_OR_RETURN(hipMalloc(&buf, 2 * n3 + ni + nf));
+  DevBuf<char> scratch;
+  HIP_OR_RETURN(scratch.alloc(2 * n3 + ni + nf));
+  char* buf = scratch;
   mcpt::TraceParams q;
-  q.nodes = c->d_nodes; q.leaves = c->d_leaves; q.ptype = c->d_ptype; q.prims = c->d_prims; q.depth = c->depth;
+  q.nodes = c->scene.d_nodes; q.leaves = c->scene.d_leaves; q.ptype = c->scene.d_ptype; q.prims = c->scene.d_prims; q.depth = c->depth;
   q.prim = prim < 0 ? -1 : prim;
-  q.minfo = c->d_minfo; q.mpairs = c->d_mpairs; q.mleaftris = c->d_mleaftris; q.mtris = c->d_mtris;
-  q.mverts = c->d_mverts; q.mnorms = c->d_mnorms; q.n_meshes = c->n_meshes; q.flat_face = c->flat_face;
+  q.minfo = c->meshes.d_minfo; q.mpairs = c->meshes.d_mpairs; q.mleaftris = c->meshes.d_mleaftris; q.mtris = c->meshes.d_mtris;
+  q.mverts = c->meshes.d_mverts; q.mnorms = c->meshes.d_mnorms; q.n_meshes = c->meshes.n_meshes; q.flat_face = c->flat_face;
   q.orig = (const float*)buf; q.dir = (const float*)(buf + n3);
   q.out_i = (int*)(buf + 2 * n3); q.out = (float*)(buf + 2 * n3 + ni); q.n = n;
   std::vector<int> hi((size_t)n * 3);
@@ -1290,7 +1217,6 @@ int mcpt_trace(mcpt_ctx* c, const float* origins, const float* dirs, int n, int 
   if (e == hipSuccess) e = hipMemcpyAsync(hi.data(), q.out_i, ni, hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(hf.data(), q.out, nf, hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  (void)hipFree(buf);
   if (e != hipSuccess) return set_err(MCPT_ERR_HIP, "mcpt_trace", e);
   for (int i = 0; i < n; ++i) {
     mcpt_hit& h = out[i];
@@ -1314,11 +1240,12 @@ int mcpt_sample_hemisphere(mcpt_ctx* c, const float* normal3, const float* fseed
   mcpt::SampleParams q;
   for (int k = 0; k < 3; ++k) { q.normal[k] = normal3[k]; q.fseed[k] = fseed3[k]; }
   q.roughness = roughness; q.nb_used = (uint32_t)nb_used; q.n = n;
-  HIP_OR_RETURN(hipMalloc(&q.out, (size_t)n * 3 * sizeof(float)));
+  DevBuf<float> out;
+  HIP_OR_RETURN(out.alloc((size_t)n * 3));
+  q.out = out;
   hipError_t e = mcpt_launch_sample(q, c->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(out_xyz, q.out, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  (void)hipFree(q.out);
   if (e != hipSuccess) return set_err(MCPT_ERR_HIP, "mcpt_sample_hemisphere", e);
   return MCPT_OK;
 }
@@ -1393,7 +1320,7 @@ int mcpt_get_leaf_batch(mcpt_ctx* c, int* resolved) {
 
 int mcpt_get_walk_exit(mcpt_ctx* c, int* resolved) {
   if (!c || !resolved) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
-  *resolved = plan::cand_walk_exit(resolve_candidate(c, c->tuner.meas_segs), c->walk_exit, c->n_meshes, c->depth);
+  *resolved = plan::cand_walk_exit(resolve_candidate(c, c->tuner.meas_segs), c->walk_exit, c->meshes.n_meshes, c->depth);
   return MCPT_OK;
 }
 
@@ -1416,7 +1343,7 @@ int mcpt_set_stream(mcpt_ctx* c, void* s) {
   if (!c) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
   HIP_OR_RETURN(hipSetDevice(c->device));
   HIP_OR_RETURN(hipStreamSynchronize(c->stream));
-  c->stream = s ? (hipStream_t)s : c->own_stream;
+  c->stream = s ? (hipStream_t)s : (hipStream_t)c->own_stream;
   return MCPT_OK;
 }
 
@@ -1450,7 +1377,7 @@ int mcpt_kernel_span_ms_back(mcpt_ctx* c, int back, float* span_ms) {
   const int slot = ring_slot_back(c, back);
   if (slot < 0) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_kernel_span_ms_back: no such call in the timing ring");
   HIP_OR_RETURN(hipSetDevice(c->device));
-  const std::vector<hipEvent_t>& v = c->evs[slot];
+  const std::vector<Event>& v = c->evs[slot];
   float tot = 0.0f;
   for (int k = 0; k < c->ring_n_sub[slot]; ++k) {
     float a = 0.0f;

@@ -19,12 +19,6 @@ struct DeviceGuard {
   DeviceGuard() { if (hipGetDevice(&prev) != hipSuccess) prev = -1; }
   ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
 };
-// an event created in a gather is destroyed on every return path (it is released by HIP once the
-// waits recorded against it have been satisfied)
-struct EventGuard {
-  hipEvent_t e = nullptr;
-  ~EventGuard() { if (e) (void)hipEventDestroy(e); }
-};
 // direct xGMI reads/writes between a frame's device and a shard's (once per process)
 int enable_peer_access(const mcpt_ctx* frame, const mcpt_ctx* s) {
   int ok = 0;
@@ -66,11 +60,12 @@ struct Plane { void* dst; const void* src; size_t row_bytes; };
 int copy_shard_planes(const char* who, mcpt_ctx* frame, mcpt_ctx* s, const Plane* planes, int n_planes) {
   OK_OR_RETURN(enable_peer_access(frame, s));
   HIP_OR_RETURN(hipSetDevice(s->device));
-  EventGuard done;
-  HIP_OR_RETURN(hipEventCreateWithFlags(&done.e, hipEventDisableTiming));
-  HIP_OR_RETURN(hipEventRecord(done.e, s->stream));
+  // (destroyed on every return path: HIP releases an event once the waits on it are satisfied)
+  Event done;
+  HIP_OR_RETURN(done.ensure(hipEventDisableTiming));
+  HIP_OR_RETURN(hipEventRecord(done, s->stream));
   HIP_OR_RETURN(hipSetDevice(frame->device));
-  HIP_OR_RETURN(hipStreamWaitEvent(frame->stream, done.e, 0));
+  HIP_OR_RETURN(hipStreamWaitEvent(frame->stream, done, 0));
   for (const plan::RowRun& run : plan::row_runs(s->rows))
     for (int p = 0; p < n_planes; ++p) {
       const Plane& pl = planes[p];
@@ -79,11 +74,11 @@ int copy_shard_planes(const char* who, mcpt_ctx* frame, mcpt_ctx* s, const Plane
                                               (size_t)run.n * pl.row_bytes, frame->stream);
       if (e != hipSuccess) return refuse(MCPT_ERR_HIP, who, "peer copy", e);
     }
-  EventGuard copied;
-  HIP_OR_RETURN(hipEventCreateWithFlags(&copied.e, hipEventDisableTiming));
-  HIP_OR_RETURN(hipEventRecord(copied.e, frame->stream));
+  Event copied;
+  HIP_OR_RETURN(copied.ensure(hipEventDisableTiming));
+  HIP_OR_RETURN(hipEventRecord(copied, frame->stream));
   HIP_OR_RETURN(hipSetDevice(s->device));
-  HIP_OR_RETURN(hipStreamWaitEvent(s->stream, copied.e, 0));
+  HIP_OR_RETURN(hipStreamWaitEvent(s->stream, copied, 0));
   return MCPT_OK;
 }
 
@@ -111,9 +106,9 @@ int gather_rows(mcpt_ctx* frame, mcpt_ctx* const* shards, int n_shards, bool cou
   DeviceGuard device_guard;
   const size_t row_bytes = (size_t)frame->W * 3 * sizeof(float);
   const size_t row_counts = (size_t)frame->W * sizeof(int);
-  if (counted && !frame->d_count_plane) {
+  if (counted && !frame->planes.d_count_plane) {
     HIP_OR_RETURN(hipSetDevice(frame->device));
-    HIP_OR_RETURN(hipMalloc(&frame->d_count_plane, (size_t)frame->H * row_counts));
+    HIP_OR_RETURN(frame->planes.d_count_plane.alloc((size_t)frame->H * frame->W));
   }
   int most = 0;
   for (int k = 0; k < n_shards; ++k) {
@@ -122,15 +117,15 @@ int gather_rows(mcpt_ctx* frame, mcpt_ctx* const* shards, int n_shards, bool cou
       // the shard's counts on its stream (which waited for the previous gather's copies of this buffer)
       const size_t n_px = (size_t)s->n_local_rows * s->W;
       HIP_OR_RETURN(hipSetDevice(s->device));
-      if (!s->d_gather_counts) HIP_OR_RETURN(hipMalloc(&s->d_gather_counts, n_px * sizeof(int)));
-      HIP_OR_RETURN(mcpt_launch_counts(count_source(s), s->d_gather_counts, (long long)n_px, s->stream));
+      HIP_OR_RETURN(s->planes.d_gather_counts.ensure(n_px));
+      HIP_OR_RETURN(mcpt_launch_counts(count_source(s), s->planes.d_gather_counts, (long long)n_px, s->stream));
     }
-    const Plane planes[2] = {{frame->d_accum, s->d_accum, row_bytes}, {frame->d_count_plane, s->d_gather_counts, row_counts}};
+    const Plane planes[2] = {{frame->target.d_accum, s->target.d_accum, row_bytes}, {frame->planes.d_count_plane, s->planes.d_gather_counts, row_counts}};
     OK_OR_RETURN(copy_shard_planes(who, frame, s, planes, counted ? 2 : 1));
     most = std::max(most, s->pass_count);
   }
   if (n_shards > 0) frame->pass_count = most;   // (a plain gather's shards hold one pass count)
-  frame->plane_valid = counted;
+  frame->planes.plane_valid = counted;
   return MCPT_OK;
 }
 
@@ -141,18 +136,18 @@ constexpr size_t kMapBytes = sizeof(float2);   // {se, r} per pixel
 // previous load's, so mcpt_load_rows_counted and mcpt_load_rows_error_map with one index upload it once
 int upload_load_index(mcpt_ctx* c, const int* src_row) {
   const size_t index_bytes = (size_t)c->H * sizeof(int);
-  if (!c->d_load_index) {
-    HIP_OR_RETURN(hipMalloc(&c->d_load_index, index_bytes));
-    c->load_index.clear();
+  if (!c->planes.d_load_index) {
+    HIP_OR_RETURN(c->planes.d_load_index.alloc((size_t)c->H));
+    c->planes.load_index.clear();
   }
-  if (c->load_index.size() != (size_t)c->H || std::memcmp(c->load_index.data(), src_row, index_bytes) != 0) {
+  if (c->planes.load_index.size() != (size_t)c->H || std::memcmp(c->planes.load_index.data(), src_row, index_bytes) != 0) {
     // on the stream after the loads that read the previous index; a queued upload of the previous
     // index may still read the host copy, so replacing one waits for it (a first upload does not)
-    if (!c->load_index.empty()) HIP_OR_RETURN(hipStreamSynchronize(c->stream));
-    c->load_index.assign(src_row, src_row + c->H);
-    const hipError_t e = hipMemcpyAsync(c->d_load_index, c->load_index.data(), index_bytes, hipMemcpyHostToDevice, c->stream);
+    if (!c->planes.load_index.empty()) HIP_OR_RETURN(hipStreamSynchronize(c->stream));
+    c->planes.load_index.assign(src_row, src_row + c->H);
+    const hipError_t e = hipMemcpyAsync(c->planes.d_load_index, c->planes.load_index.data(), index_bytes, hipMemcpyHostToDevice, c->stream);
     if (e != hipSuccess) {
-      c->load_index.clear();
+      c->planes.load_index.clear();
       return set_err(MCPT_ERR_HIP, "mcpt_load_rows: index upload", e);
     }
   }
@@ -175,10 +170,10 @@ extern "C" {
 int mcpt_copy_accum_device(mcpt_ctx* c, void* dst, size_t bytes) {
   if (!c || (!dst && bytes)) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
   if (!c->has_target) return mcpt_err_bare(MCPT_ERR_NO_TARGET);
-  if (bytes < c->accum_bytes) return set_err(MCPT_ERR_INVALID_ARG, "destination smaller than the accumulator");
+  if (bytes < c->target.d_accum.bytes()) return set_err(MCPT_ERR_INVALID_ARG, "destination smaller than the accumulator");
   HIP_OR_RETURN(hipSetDevice(c->device));
-  if (c->accum_bytes)
-    HIP_OR_RETURN(hipMemcpyAsync(dst, c->d_accum, c->accum_bytes, hipMemcpyDeviceToDevice, c->stream));
+  if (c->target.d_accum.bytes())
+    HIP_OR_RETURN(hipMemcpyAsync(dst, c->target.d_accum, c->target.d_accum.bytes(), hipMemcpyDeviceToDevice, c->stream));
   return MCPT_OK;
 }
 
@@ -195,7 +190,7 @@ int mcpt_gather_rows_counted(mcpt_ctx* frame, mcpt_ctx* const* shards, int n_sha
 int mcpt_gather_error_map(mcpt_ctx* frame, mcpt_ctx* const* shards, int n_shards) {
   const char* who = "mcpt_gather_error_map";
   if (!frame || n_shards < 0 || (n_shards > 0 && !shards)) return refuse(MCPT_ERR_INVALID_ARG, who, "bad arguments");
-  frame->emap_plane_valid = false;
+  frame->planes.emap_plane_valid = false;
   if (!frame->has_target) return refuse(MCPT_ERR_NO_TARGET, who, "frame has no target");
   if (frame->n_local_rows != frame->H) return refuse(MCPT_ERR_INVALID_ARG, who, "frame target is a shard");
   if (!plan::is_full_frame(frame->rows, frame->H)) return refuse(MCPT_ERR_INVALID_ARG, who, "frame target is not in row order");
@@ -207,15 +202,15 @@ int mcpt_gather_error_map(mcpt_ctx* frame, mcpt_ctx* const* shards, int n_shards
       return refuse(MCPT_ERR_NO_STATS, who, "a shard holds no error map of its current statistics window");
   DeviceGuard device_guard;
   const size_t row_bytes = (size_t)frame->W * kMapBytes;
-  if (!frame->d_emap_plane && frame->H > 0 && frame->W > 0) {
+  if (!frame->planes.d_emap_plane && frame->H > 0 && frame->W > 0) {
     HIP_OR_RETURN(hipSetDevice(frame->device));
-    HIP_OR_RETURN(hipMalloc(&frame->d_emap_plane, (size_t)frame->H * row_bytes));
+    HIP_OR_RETURN(frame->planes.d_emap_plane.alloc((size_t)frame->H * frame->W));
   }
   for (int k = 0; k < n_shards; ++k) {
-    const Plane map = {frame->d_emap_plane, shards[k]->d_emap, row_bytes};
+    const Plane map = {frame->planes.d_emap_plane, shards[k]->stats.d_emap, row_bytes};
     OK_OR_RETURN(copy_shard_planes(who, frame, shards[k], &map, 1));
   }
-  frame->emap_plane_valid = true;
+  frame->planes.emap_plane_valid = true;
   return MCPT_OK;
 }
 
@@ -236,7 +231,7 @@ int mcpt_pack_counted_device(mcpt_ctx* c, void* dst, size_t bytes) {
   if (!dst || ((uintptr_t)dst & (kPackedBytes - 1)))
     return set_err(MCPT_ERR_INVALID_ARG, "mcpt_pack_counted_device: destination must be a 16-byte aligned device pointer");
   HIP_OR_RETURN(hipSetDevice(c->device));
-  HIP_OR_RETURN(mcpt_launch_pack_counted(count_source(c), c->n_local_rows, c->d_accum, dst, c->stream));
+  HIP_OR_RETURN(mcpt_launch_pack_counted(count_source(c), c->n_local_rows, c->target.d_accum, dst, c->stream));
   return MCPT_OK;
 }
 
@@ -248,11 +243,11 @@ int mcpt_load_rows_counted(mcpt_ctx* c, const void* src, long long src_rows, con
   if (c->H == 0 || c->W == 0) return MCPT_OK;
   HIP_OR_RETURN(hipSetDevice(c->device));
   const size_t n_px = (size_t)c->H * c->W;
-  if (!c->d_count_plane) HIP_OR_RETURN(hipMalloc(&c->d_count_plane, n_px * sizeof(int)));
+  HIP_OR_RETURN(c->planes.d_count_plane.ensure(n_px));
   OK_OR_RETURN(upload_load_index(c, src_row));
-  HIP_OR_RETURN(mcpt_launch_load_rows_counted(src, c->d_load_index, c->W, c->H, c->d_accum, c->d_count_plane, c->stream));
+  HIP_OR_RETURN(mcpt_launch_load_rows_counted(src, c->planes.d_load_index, c->W, c->H, c->target.d_accum, c->planes.d_count_plane, c->stream));
   c->pass_count = pass_count;
-  c->plane_valid = true;
+  c->planes.plane_valid = true;
   return MCPT_OK;
 }
 
@@ -269,22 +264,22 @@ int mcpt_pack_error_map_device(mcpt_ctx* c, void* dst, size_t bytes) {
     return set_err(MCPT_ERR_INVALID_ARG, "mcpt_pack_error_map_device: destination must be an 8-byte aligned device pointer");
   HIP_OR_RETURN(hipSetDevice(c->device));
   // (the map is contiguous in local row order already: a copy on the stream, behind the select)
-  HIP_OR_RETURN(hipMemcpyAsync(dst, c->d_emap, need, hipMemcpyDeviceToDevice, c->stream));
+  HIP_OR_RETURN(hipMemcpyAsync(dst, c->stats.d_emap, need, hipMemcpyDeviceToDevice, c->stream));
   return MCPT_OK;
 }
 
 int mcpt_load_rows_error_map(mcpt_ctx* c, const void* src, long long src_rows, const int* src_row) {
   if (!c) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
-  c->emap_plane_valid = false;   // (on any error the frame holds no gathered map)
+  c->planes.emap_plane_valid = false;   // (on any error the frame holds no gathered map)
   if (!src || !src_row || ((uintptr_t)src & (kMapBytes - 1)))
     return set_err(MCPT_ERR_INVALID_ARG, "mcpt_load_rows_error_map: bad arguments (8-byte aligned source)");
   OK_OR_RETURN(check_load("mcpt_load_rows_error_map", c, src_rows, src_row));
   if (c->H == 0 || c->W == 0) return MCPT_OK;
   HIP_OR_RETURN(hipSetDevice(c->device));
-  if (!c->d_emap_plane) HIP_OR_RETURN(hipMalloc(&c->d_emap_plane, (size_t)c->H * c->W * kMapBytes));
+  HIP_OR_RETURN(c->planes.d_emap_plane.ensure((size_t)c->H * c->W));
   OK_OR_RETURN(upload_load_index(c, src_row));
-  HIP_OR_RETURN(mcpt_launch_load_rows_error_map(src, c->d_load_index, c->W, c->H, c->d_emap_plane, c->stream));
-  c->emap_plane_valid = true;
+  HIP_OR_RETURN(mcpt_launch_load_rows_error_map(src, c->planes.d_load_index, c->W, c->H, c->planes.d_emap_plane, c->stream));
+  c->planes.emap_plane_valid = true;
   return MCPT_OK;
 }
 
