@@ -704,6 +704,25 @@ extern int mcpt_adaptive_run_filtered(mcpt_ctx* ctx, const float* invPV, const f
                                float refract_ind, int variant, mcpt_adaptive_filtered_t* records, int records_capacity,
                                mcpt_adaptive_run_t* out);
 
+/* The host side of that schedule: the next step of a loop that renders batches of `batch` passes for
+ * the active blocks, selects after every check_every calls (from the second on, and at the cap) and
+ * ends at max_passes, after `done` passes in `calls` render calls (a queued run of r rounds counts as
+ * r; a resumed render enters with the window's batches).  Every such loop of the library, the C++ and
+ * Python faces and mcpt_render asks this one function, so they issue the same calls:
+ *   *rounds == 0 and *n_passes == 0: finished (done >= max_passes);
+ *   *rounds > 0: a queued run of that many rounds of `batch` passes from pass first + done on
+ *     (mcpt_adaptive_run* with this check_every).  Only with queued_rounds > 0 and calls a multiple of
+ *     check_every: min(queued_rounds, the whole batches left, MCPT_ADAPTIVE_RUN_MAX_ROUNDS) rounds,
+ *     trimmed to a multiple of check_every unless the run ends exactly at the cap;
+ *   else *n_passes = min(batch, max_passes - done) passes in one mcpt_render_adaptive, followed by a
+ *     select iff *select != 0.
+ * The caller stops early when a select's record has no active block or a run reports rounds_run
+ * below its rounds.  No context and no device: plain host arithmetic.  MCPT_ERR_INVALID_ARG for a
+ * non-positive batch, max_passes or check_every, a negative done, calls or queued_rounds, or a NULL
+ * out pointer. */
+extern int mcpt_adaptive_until_next(int done, int calls, int batch, int max_passes, int check_every, int queued_rounds,
+                                    int* rounds, int* n_passes, int* select);
+
 /* Temporal reprojection: carry the integrated frame across camera moves of a
  * static scene.  A context in temporal mode keeps, per pixel of a full frame, the integrated colour,
  * the variance of its mean, the history length and the guides of the frame the history was made with

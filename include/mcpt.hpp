@@ -21,6 +21,7 @@
 #define MCPT_HPP_
 
 #include <cstring>
+#include <functional>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -292,6 +293,41 @@ struct Camera {
   // the forward matrix P·V (what temporal_accumulate takes for the previous frame's camera)
   GLMat4 PV() const { return invPV.inverse(); }
 };
+
+// The loop behind Renderer::render_adaptive_until and mcpt_render's adaptive renders: every step is
+// what mcpt_adaptive_until_next (mcpt.h) says follows `done` passes in `calls` render calls, issued as
+// render(first, n), select() -> its record's n_active_blocks, or run(first, rounds) -> what the queued
+// run did (null: never queued; render and select may be null where every step is a run); then
+// after_step(done, calls) if given.  Ends at the cap, on a record with no active block or on a run
+// that stopped short.  Unlike Python's driver it never selects on its own: when selects == 0 (fewer
+// than two batches) the caller that needs a record owes the select.
+struct AdaptiveRan { int rounds_run, selects_run; long long n_active; };   // n_active: the last record's, if any
+struct AdaptiveUntil { int done, calls, selects; };
+inline AdaptiveUntil adaptive_until(int first_pass, int batch, int max_passes, int check_every, int queued_rounds,
+                                    const std::function<void(int, int)>& render, const std::function<long long()>& select,
+                                    const std::function<AdaptiveRan(int, int)>& run = nullptr,
+                                    const std::function<void(int, int)>& after_step = nullptr, int done = 0,
+                                    int calls = 0) {
+  AdaptiveUntil u{done, calls, 0};
+  for (long long n_active = 1; n_active > 0;) {
+    int rounds = 0, n = 0, sel = 0;
+    check(mcpt_adaptive_until_next(u.done, u.calls, batch, max_passes, check_every, run ? queued_rounds : 0, &rounds, &n,
+                                   &sel), "mcpt_adaptive_until_next");
+    if (rounds == 0 && n == 0) break;
+    AdaptiveRan got{1, sel, 0};   // (a single call is one round)
+    if (rounds > 0) {
+      got = run(first_pass + u.done, rounds);
+    } else {
+      render(first_pass + u.done, n);
+      if (sel) got.n_active = select();
+    }
+    if (got.selects_run > 0) n_active = got.n_active;
+    u = {u.done + (rounds > 0 ? got.rounds_run * batch : n), u.calls + got.rounds_run, u.selects + got.selects_run};
+    if (after_step) after_step(u.done, u.calls);
+    if (got.rounds_run < rounds) break;
+  }
+  return u;
+}
 
 // prg_ray + the RGB32F accumulation FBO (montecarlo.cpp:384-386, 408-477), one GPU
 class Renderer {
@@ -669,30 +705,29 @@ class Renderer {
   // Begin a statistics window and the adaptive mode, render calls of `batch` passes for the active
   // blocks only, select after every check_every calls (from the second on, and at the cap) until no
   // block is active or max_passes are rendered.  The mode stays on (read_resolved, read_sample_counts).
+  // queued_rounds K > 0: as queued runs of up to K rounds (adaptive_run), the same record and *rendered.
   mcpt_adaptive_t render_adaptive_until(const Camera& cam, float threshold, int batch = 32, int max_passes = 4096,
                                         int min_passes = 0, int check_every = 1, int first_pass = 1,
                                         float date = 0.0f, int bounces = 3, float refract_ind = 1.0f,
                                         int variant = MCPT_MONTECARLO, int* rendered = nullptr,
-                                        float mu_floor = kErrorMuFloor) {
-    if (batch <= 0 || check_every <= 0 || max_passes <= 0 || !(threshold > 0.0f))
+                                        float mu_floor = kErrorMuFloor, int queued_rounds = 0) {
+    if (batch <= 0 || check_every <= 0 || max_passes <= 0 || !(threshold > 0.0f) || queued_rounds < 0)
       throw std::runtime_error("render_adaptive_until: batch, check_every, max_passes and threshold must be positive");
     stats_begin();
     adaptive_begin(min_passes);
     mcpt_adaptive_t rec;
-    bool have = false;
-    int done = 0;
-    for (int calls = 1; done < max_passes; ++calls) {
-      const int n = batch < max_passes - done ? batch : max_passes - done;
-      render_adaptive(cam, first_pass + done, n, date, bounces, refract_ind, variant);
-      done += n;
-      if (calls >= 2 && (calls % check_every == 0 || done >= max_passes)) {
-        rec = adaptive_select(threshold, mu_floor);
-        have = true;
-        if (rec.n_active_blocks == 0) break;
-      }
-    }
-    if (!have) rec = adaptive_select(threshold, mu_floor);   // (fewer than two batches: MCPT_ERR_NO_STATS)
-    if (rendered) *rendered = done;
+    std::vector<mcpt_adaptive_t> recs;
+    const AdaptiveUntil u = adaptive_until(
+        first_pass, batch, max_passes, check_every, queued_rounds,
+        [&](int first, int n) { render_adaptive(cam, first, n, date, bounces, refract_ind, variant); },
+        [&] { return (rec = adaptive_select(threshold, mu_floor)).n_active_blocks; },
+        [&](int first, int rounds) {
+          const mcpt_adaptive_run_t got = adaptive_run(cam, first, batch, rounds, check_every, threshold, date, bounces,
+                                                       refract_ind, recs, variant, mu_floor);
+          return AdaptiveRan{got.rounds_run, got.selects_run, recs.empty() ? 0 : (rec = recs.back()).n_active_blocks};
+        });
+    if (u.selects == 0) rec = adaptive_select(threshold, mu_floor);   // (fewer than two batches: MCPT_ERR_NO_STATS)
+    if (rendered) *rendered = u.done;
     return rec;
   }
   // frames with per-pixel sample counts (adaptive mode on, or after gather_rows_counted; mcpt.h,

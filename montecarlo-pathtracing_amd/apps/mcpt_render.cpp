@@ -320,16 +320,16 @@ int run_temporal(const Args& a, mcpt::BVH_GPU_Scene& scene, int W, int H) {
       r.render_guides(cam);
       const int rounds = std::min(a.spp / a.chunk, MCPT_ADAPTIVE_RUN_MAX_ROUNDS);
       std::vector<mcpt_adaptive_temporal_t> recs;
-      for (int done = 0; done < rounds;) {
-        const int q = std::min(a.queue_rounds > 0 ? a.queue_rounds : rounds, rounds - done);
-        const mcpt_adaptive_run_t run =
-            r.adaptive_run_temporal(cam, pass + done * a.chunk, a.chunk, q, 1, (float)a.temporal_target,
-                                    k ? &prev : nullptr, a.date, a.bounces, a.ior, recs, a.variant, a.temporal);
-        kernel_ms += run.device_ms;
-        done += run.rounds_run;
-        if (!recs.empty()) sel = recs.back();
-        if (run.rounds_run < q || (!recs.empty() && sel.raw.n_active_blocks == 0)) break;
-      }
+      const auto run = [&](int first, int q) {   // (whole chunks, a select per round: every step is a run)
+        const mcpt_adaptive_run_t got =
+            r.adaptive_run_temporal(cam, first, a.chunk, q, 1, (float)a.temporal_target, k ? &prev : nullptr, a.date,
+                                    a.bounces, a.ior, recs, a.variant, a.temporal);
+        kernel_ms += got.device_ms;
+        if (!recs.empty()) sel = recs.back();   // (the frame's last select)
+        return mcpt::AdaptiveRan{got.rounds_run, got.selects_run, sel.raw.n_active_blocks};
+      };
+      mcpt::adaptive_until(pass, a.chunk, rounds * a.chunk, 1, a.queue_rounds > 0 ? a.queue_rounds : rounds, nullptr,
+                           nullptr, run);
       samples += (double)sel.raw.samples / (double)(sel.raw.n_px > 0 ? sel.raw.n_px : 1);
       pass += a.spp;   // (pass ids never repeat, whatever the frame rendered)
       rec = r.temporal_accumulate_resolved(k ? &prev : nullptr, a.temporal);
@@ -383,6 +383,14 @@ std::string adaptive_json(double target_error, bool converged, const mcpt_adapti
                 rec.n_px, rec.sum_q, rec.samples, rec.n_active_blocks, rec.n_blocks,
                 rec.n_px > 0 ? (double)rec.samples / (double)rec.n_px : 0.0);
   return buf;
+}
+
+// one chunk for the active blocks; its render time (synchronizes)
+float render_adaptive_ms(const Args& a, mcpt::Renderer& r, const mcpt::Camera& cam, int first, int n) {
+  r.render_adaptive(cam, first, n, a.date, a.bounces, a.ior, a.variant);
+  float sel = 0.0f, ren = 0.0f;
+  r.last_adaptive_ms(sel, ren);
+  return ren;
 }
 
 // --denoise / --aov on the context that holds the whole frame: the guide buffers, the AOV files,
@@ -509,59 +517,39 @@ int main(int argc, char** argv) {
         converged = calls >= 2 && r.adaptive_info().n_active == 0;
         rendered = next - a.first_pass;
       }
-      for (int done = next - a.first_pass; a.adaptive && done < a.spp && !converged;) {
-        // --queue-rounds: the whole chunks ahead, up to K of them, as one queued run (the same
-        // renders and selects, one host wait); a short last chunk goes through the calls below
-        const int whole = (a.spp - done) / a.chunk;
-        if (a.queue_rounds > 0 && whole > 0) {
-          const int k = std::min(a.queue_rounds, whole);
-          std::vector<mcpt_adaptive_t> recs;
-          std::vector<mcpt_adaptive_filtered_t> frecs;
-          const mcpt_adaptive_run_t run =
-              a.target_denoised >= 0
-                  ? r.adaptive_run_filtered(cam, a.first_pass + done, a.chunk, k, 1, (float)a.target_error, a.raw_cap,
-                                            a.target_denoised, a.date, a.bounces, a.ior, frecs, a.variant)
-                  : r.adaptive_run(cam, a.first_pass + done, a.chunk, k, 1, (float)a.target_error, a.date, a.bounces,
-                                   a.ior, recs, a.variant);
-          kernel_ms += run.device_ms;
-          calls += run.rounds_run;
-          done += run.rounds_run * a.chunk;
-          rendered = done;
-          if (run.selects_run > 0) {
-            if (a.target_denoised >= 0) {
-              frec = frecs.back();
-              arec = frec.raw;
-            } else {
-              arec = recs.back();
-            }
-            have_arec = true;
-            converged = arec.n_active_blocks == 0;
-          }
-          if (!a.checkpoint.empty()) r.save_adaptive_checkpoint(a.checkpoint, a.first_pass + done, tag);
-          if (run.rounds_run < k) break;   // (the list was empty on entry: nothing left to render)
-          continue;
-        }
-        // adaptive sampling: the active blocks only, a select after every chunk from the second on
-        const int n = std::min(a.chunk, a.spp - done);
-        r.render_adaptive(cam, a.first_pass + done, n, a.date, a.bounces, a.ior, a.variant);
-        float sel = 0.0f, ren = 0.0f;
-        r.last_adaptive_ms(sel, ren);
-        kernel_ms += ren;
-        rendered = done + n;
-        if (++calls >= 2) {
-          if (a.target_denoised >= 0) {
-            frec = r.adaptive_select_filtered((float)a.target_error, a.raw_cap, mcpt::Renderer::kErrorMuFloor,
-                                              a.target_denoised);
-            arec = frec.raw;
-          } else {
-            arec = r.adaptive_select((float)a.target_error);
-          }
-          have_arec = true;
-          converged = arec.n_active_blocks == 0;
-        }
-        // (after the chunk's select: the resumed run continues with the next chunk's render)
-        if (!a.checkpoint.empty()) r.save_adaptive_checkpoint(a.checkpoint, a.first_pass + done + n, tag);
-        done += a.chunk;
+      if (a.adaptive && next - a.first_pass < a.spp && !converged) {
+        // chunks for the active blocks with a select after every chunk from the second on; with
+        // --queue-rounds K the whole chunks ahead go out as queued runs of up to K rounds
+        const bool filtered = a.target_denoised >= 0;
+        const float thr = (float)a.target_error;
+        std::vector<mcpt_adaptive_t> recs;
+        std::vector<mcpt_adaptive_filtered_t> frecs;
+        const mcpt::AdaptiveUntil u = mcpt::adaptive_until(
+            a.first_pass, a.chunk, a.spp, 1, a.queue_rounds,
+            [&](int first, int n) { kernel_ms += render_adaptive_ms(a, r, cam, first, n); },
+            [&] {
+              if (filtered)
+                frec = r.adaptive_select_filtered(thr, a.raw_cap, mcpt::Renderer::kErrorMuFloor, a.target_denoised);
+              return (arec = filtered ? frec.raw : r.adaptive_select(thr)).n_active_blocks;
+            },
+            [&](int first, int k) {
+              const mcpt_adaptive_run_t run =
+                  filtered ? r.adaptive_run_filtered(cam, first, a.chunk, k, 1, thr, a.raw_cap, a.target_denoised, a.date,
+                                                     a.bounces, a.ior, frecs, a.variant)
+                           : r.adaptive_run(cam, first, a.chunk, k, 1, thr, a.date, a.bounces, a.ior, recs, a.variant);
+              kernel_ms += run.device_ms;
+              if (filtered && run.selects_run > 0) frec = frecs.back();
+              if (run.selects_run > 0) arec = filtered ? frec.raw : recs.back();
+              return mcpt::AdaptiveRan{run.rounds_run, run.selects_run, arec.n_active_blocks};
+            },
+            // (after the step's select: the resumed run continues with the next chunk's render)
+            [&](int done, int) {
+              if (!a.checkpoint.empty()) r.save_adaptive_checkpoint(a.checkpoint, a.first_pass + done, tag);
+            },
+            next - a.first_pass, calls);
+        rendered = u.done;
+        have_arec = u.selects > 0;
+        if (have_arec) converged = arec.n_active_blocks == 0;
       }
       for (int done = next - a.first_pass; !a.adaptive && done < a.spp && !converged; done += a.chunk) {
         const int n = std::min(a.chunk, a.spp - done);
@@ -630,7 +618,7 @@ int main(int argc, char** argv) {
       std::vector<std::string> errors((size_t)N);
       // adaptive: every shard's own statistics window and select / render loop on its rows
       std::vector<mcpt_adaptive_t> shard_rec((size_t)N);
-      std::vector<int> shard_selects((size_t)N, 0), shard_passes((size_t)N, 0);
+      std::vector<mcpt::AdaptiveUntil> shard_until((size_t)N, mcpt::AdaptiveUntil{0, 0, 0});   // passes, calls, selects
       const auto t0 = std::chrono::steady_clock::now();
       std::vector<std::thread> workers;
       for (int k = 0; k < N; ++k)
@@ -641,20 +629,11 @@ int main(int argc, char** argv) {
               s.stats_begin();
               s.adaptive_begin(0);
             }
-            bool shard_done = false;   // its list is empty
-            for (int done = 0, calls = 0; a.adaptive && done < a.spp && !shard_done; done += a.chunk) {
-              const int n = std::min(a.chunk, a.spp - done);
-              s.render_adaptive(cam, a.first_pass + done, n, a.date, a.bounces, a.ior, a.variant);
-              float sel = 0.0f, ren = 0.0f;
-              s.last_adaptive_ms(sel, ren);   // (synchronizes this shard)
-              shard_ms[(size_t)k] += ren;
-              shard_passes[(size_t)k] = done + n;
-              if (++calls >= 2) {
-                shard_rec[(size_t)k] = s.adaptive_select((float)a.target_error);
-                ++shard_selects[(size_t)k];
-                shard_done = shard_rec[(size_t)k].n_active_blocks == 0;
-              }
-            }
+            if (a.adaptive && a.spp > 0)   // until the shard's list is empty
+              shard_until[(size_t)k] = mcpt::adaptive_until(
+                  a.first_pass, a.chunk, a.spp, 1, 0,
+                  [&](int first, int n) { shard_ms[(size_t)k] += render_adaptive_ms(a, s, cam, first, n); },
+                  [&] { return (shard_rec[(size_t)k] = s.adaptive_select((float)a.target_error)).n_active_blocks; });
             // uniform shards with --denoise-guided / --denoise-variance: a statistics window over the chunks and, after the
             // last, the shard's error map (fewer than two chunks: MCPT_ERR_NO_STATS, as on one device)
             if (!a.adaptive && a.noise_filter()) s.stats_begin();
@@ -705,8 +684,8 @@ int main(int argc, char** argv) {
         rendered = 0;
         for (int k = 0; k < N; ++k) {
           const mcpt_adaptive_t& q = shard_rec[(size_t)k];
-          every = every && shard_selects[(size_t)k] > 0;
-          rendered = std::max(rendered, shard_passes[(size_t)k]);
+          every = every && shard_until[(size_t)k].selects > 0;
+          rendered = std::max(rendered, shard_until[(size_t)k].done);
           all.n_px += q.n_px; all.n_above += q.n_above; all.sum_q += q.sum_q; all.samples += q.samples;
           all.n_active_blocks += q.n_active_blocks; all.n_blocks += q.n_blocks;
           all.max_r = std::max(all.max_r, q.max_r);

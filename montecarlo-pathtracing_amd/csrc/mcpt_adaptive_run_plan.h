@@ -1,7 +1,8 @@
 // mcpt_adaptive_run_plan.h — the schedule of a queued adaptive run (mcpt_adaptive_run*,
 // mcpt_capi_post.hip): which rounds select, the grid that holds the list whatever
 // it shrinks to, and what the host loop over mcpt_render_adaptive / mcpt_adaptive_select would have
-// done, from the list lengths the selects left on the device.  Plain host code, no HIP and no
+// done, from the list lengths the selects left on the device; and the step rule of the host loops
+// that issue those calls and runs until a render is finished (until_next).  Plain host code, no HIP and no
 // context: tests/cpp/adaptive_run_plan_test.cpp checks it against known answers on the CPU.
 #pragma once
 
@@ -53,6 +54,31 @@ inline RunOutcome run_outcome(int rounds, int check_every, int batches_on_entry,
     o.n_list = lengths[o.selects_run++];
   }
   return o;
+}
+
+// The host side of the schedule (mcpt_adaptive_until_next, mcpt.h, states the contract): the step that
+// follows `done` passes in `calls` render calls.  *rounds > 0: a queued run.  Its selects fall on the
+// multiples of check_every counted from ITS first round and after its last, so it starts on a multiple
+// of check_every calls, holds whole batches only and is trimmed to a multiple unless it ends at the
+// cap.  Else *n_passes > 0: a single call, *select: a select follows it.  Both 0: finished.  false,
+// nothing written: a bad argument.
+inline bool until_next(int done, int calls, int batch, int max_passes, int check_every, int queued_rounds,
+                       int* rounds, int* n_passes, int* select) {
+  if (batch <= 0 || max_passes <= 0 || check_every <= 0 || done < 0 || calls < 0 || queued_rounds < 0 || !rounds ||
+      !n_passes || !select)
+    return false;
+  *rounds = *n_passes = *select = 0;
+  if (done >= max_passes) return true;
+  const int left = max_passes - done, full = left / batch;
+  int r = queued_rounds > 0 && calls % check_every == 0 ? queued_rounds : 0;
+  r = r < full ? r : full;
+  r = r < kAdaptiveRunMaxRounds ? r : kAdaptiveRunMaxRounds;
+  if (!(r == full && r * batch == left)) r -= r % check_every;
+  if ((*rounds = r) > 0) return true;
+  *n_passes = batch < left ? batch : left;
+  const long long then = (long long)calls + 1;
+  *select = then >= 2 && (then % check_every == 0 || *n_passes == left);
+  return true;
 }
 
 }  // namespace plan

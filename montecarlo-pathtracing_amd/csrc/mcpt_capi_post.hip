@@ -813,6 +813,13 @@ int mcpt_adaptive_run_temporal(mcpt_ctx* c, const float* invPV, const float* inv
                       refract_ind, variant, nullptr, &t, records, records_capacity, out);
 }
 
+int mcpt_adaptive_until_next(int done, int calls, int batch, int max_passes, int check_every, int queued_rounds,
+                             int* rounds, int* n_passes, int* select) {
+  if (!plan::until_next(done, calls, batch, max_passes, check_every, queued_rounds, rounds, n_passes, select))
+    return set_err(MCPT_ERR_INVALID_ARG, "mcpt_adaptive_until_next: bad arguments");
+  return MCPT_OK;
+}
+
 // every local pixel's sample count (mcpt_read_sample_counts) or, resolved, its accum / (float)count
 // (mcpt_read_resolved), through a device buffer of the call's own, on the host
 static int read_counted(mcpt_ctx* c, void* out, bool resolved, const char* who) {

@@ -253,6 +253,7 @@ def _declare(L: ctypes.CDLL) -> None:
                                   ctypes.POINTER(AdaptiveRun)]),
         "mcpt_adaptive_run_filtered": (i, [_vp, fp, fp, i, i, i, i, f, f, f, i, f, f, f, i, f, i,
                                            ctypes.POINTER(AdaptiveFiltered), i, ctypes.POINTER(AdaptiveRun)]),
+        "mcpt_adaptive_until_next": (i, [i, i, i, i, i, i, ip, ip, ip]),
         "mcpt_read_active_blocks": (i, [_vp, ip, i, ip]),
         "mcpt_render_adaptive": (i, [_vp, fp, fp, i, i, f, i, f, i]),
         "mcpt_read_sample_counts": (i, [_vp, ip]),
@@ -635,6 +636,35 @@ def adaptive_checkpoint_read(path: str) -> dict:
     out = {k: getattr(h, k) for k, _ in AdaptiveCheckpoint._fields_}
     out.update(tag=tag.value.decode(), block_active=act, block_passes=pas, accum=acc, stats=st, emap=em)
     return out
+
+
+def _adaptive_until(render, select, run, first_pass: int, batch: int, max_passes: int, check_every: int = 1,
+                    queued_rounds: int = 0, done: int = 0, calls: int = 0) -> Tuple[dict, int, int]:
+    """The loop behind every render_adaptive_until: each step is what mcpt_adaptive_until_next (mcpt.h)
+    says follows `done` passes in `calls` render calls, issued as render(first, n), select() -> record
+    or run(first, rounds) -> adaptive_run()'s dict (None: never queued).  Ends at the cap, on a record
+    with no active block or on a run that stopped short; if no select has run, one is made at the end
+    (fewer than two batches: MCPT_ERR_NO_STATS).  Returns (the last record, done, calls)."""
+    r, n, sel, rec = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), None
+    while rec is None or rec["n_active_blocks"] > 0:
+        _check(lib().mcpt_adaptive_until_next(done, calls, batch, max_passes, check_every, queued_rounds if run else 0,
+                                              ctypes.byref(r), ctypes.byref(n), ctypes.byref(sel)),
+               "mcpt_adaptive_until_next")
+        if r.value > 0:
+            got = run(first_pass + done, r.value)
+            done, calls = done + got["rounds_run"] * batch, calls + got["rounds_run"]
+            if got["records"]:
+                rec = got["records"][-1]
+            if got["rounds_run"] < r.value:
+                break
+        elif n.value > 0:
+            render(first_pass + done, n.value)
+            done, calls = done + n.value, calls + 1
+            if sel.value:
+                rec = select()
+        else:
+            break
+    return (select() if rec is None else rec), done, calls
 
 
 class Renderer:
@@ -1100,35 +1130,8 @@ class Renderer:
                                                  bounces, refract_ind, variant)
         self.stats_begin()
         self.adaptive_begin(min_passes)
-        done, calls, rec = 0, 0, None
-        while done < max_passes:
-            # A run selects on the multiples of check_every counted from ITS first round and after its
-            # last round.  It therefore starts on a multiple of check_every calls, holds whole batches
-            # only, and ends on a multiple as well unless it ends at the cap; what does not fit (the
-            # short last batch, K below check_every) goes through the single calls below.
-            full = (max_passes - done) // batch
-            r = min(queued_rounds, full, ADAPTIVE_RUN_MAX_ROUNDS) if calls % check_every == 0 else 0
-            if r > 0 and not (r == full and done + r * batch == max_passes):
-                r -= r % check_every
-            if r > 0:
-                got = run(first_pass + done, r)
-                done += got["rounds_run"] * batch
-                calls += got["rounds_run"]
-                if got["records"]:
-                    rec = got["records"][-1]
-                if got["rounds_run"] < r or (rec is not None and rec["n_active_blocks"] == 0):
-                    break
-                continue
-            n = min(batch, max_passes - done)
-            self.render_adaptive(invPV, invV, first_pass + done, n, date, bounces, refract_ind, variant)
-            done += n
-            calls += 1
-            if calls >= 2 and (calls % check_every == 0 or done >= max_passes):
-                rec = select()
-                if rec["n_active_blocks"] == 0:
-                    break
-        if rec is None:
-            rec = select()     # (fewer than two batches: MCPT_ERR_NO_STATS)
+        render = lambda p, n: self.render_adaptive(invPV, invV, p, n, date, bounces, refract_ind, variant)
+        rec, done, _ = _adaptive_until(render, select, run, first_pass, batch, max_passes, check_every, queued_rounds)
         rec["rendered"] = done
         return rec
 
@@ -1300,14 +1303,9 @@ class Renderer:
                                              max_history, plane_tol, mu_floor, date, bounces, refract_ind, variant)
             sel, done = got["records"][-1], got["rounds_run"] * n_passes
         else:
-            sel, done = None, 0
-            for i in range(rounds):
-                self.render_adaptive(invPV, invV, first_pass + done, n_passes, date, bounces, refract_ind, variant)
-                done += n_passes
-                if i >= 1:
-                    sel = self.adaptive_select_temporal(prevPV, threshold, max_history, plane_tol, mu_floor)
-                    if sel["n_active_blocks"] == 0:
-                        break
+            render = lambda p, n: self.render_adaptive(invPV, invV, p, n, date, bounces, refract_ind, variant)
+            select = lambda: self.adaptive_select_temporal(prevPV, threshold, max_history, plane_tol, mu_floor)
+            sel, done, _ = _adaptive_until(render, select, None, first_pass, n_passes, rounds * n_passes)
         sel["rendered"] = done
         rec = self.temporal_accumulate_resolved(prevPV, max_history, plane_tol)
         return self.denoise_temporal(iterations, k_color, sigma_plane), rec, sel

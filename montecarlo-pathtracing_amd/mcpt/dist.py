@@ -327,20 +327,12 @@ class ShardedRenderer:
         plus "rendered" (passes) and "rounds" (render calls); the mode stays on for gather_counted()."""
         if batch <= 0 or check_every <= 0 or max_passes <= 0 or not threshold > 0:
             raise ValueError("render_adaptive_until: batch, check_every, max_passes and threshold must be positive")
+        import mcpt
         self.stats_begin()
         self.adaptive_begin(min_passes)
-        done, calls, rec = 0, 0, None
-        while done < max_passes:
-            n = min(batch, max_passes - done)
-            self.render_adaptive(invPV, invV, first_pass + done, n, date, bounces, refract_ind, variant)
-            done += n
-            calls += 1
-            if calls >= 2 and (calls % check_every == 0 or done >= max_passes):
-                rec = self.adaptive_select(threshold, mu_floor)
-                if rec["n_active_blocks"] == 0:
-                    break
-        if rec is None:
-            rec = self.adaptive_select(threshold, mu_floor)     # (fewer than two batches: MCPT_ERR_NO_STATS)
+        render = lambda p, n: self.render_adaptive(invPV, invV, p, n, date, bounces, refract_ind, variant)
+        select = lambda: self.adaptive_select(threshold, mu_floor)     # (merged: the same answer on every rank)
+        rec, done, calls = mcpt._adaptive_until(render, select, None, first_pass, batch, max_passes, check_every)
         rec["rendered"], rec["rounds"] = done, calls
         return rec
 

@@ -1,7 +1,9 @@
 // C++ host API test (include/mcpt.hpp over libmcpt): a caller that builds a scene the way
 // montecarlo.cpp does — Transfo products, Material ctors, BVH_GPU_Scene::add_* — gets the
 // same buffers, bit for bit, as the library's built-in reference scene.  CPU only unless
-// argv[1] == "gpu" (then it also renders through mcpt::Renderer and prints the image sum).
+// argv[1] == "gpu" (then it also renders through mcpt::Renderer and prints the image sum) or
+// "gpu_until" (the queued against the single-call adaptive render, a mode of its own so that the
+// test gives it its own time limit).
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -30,6 +32,51 @@ static void scene_4boules(mcpt::BVH_GPU_Scene& s, float light_intensity) {
 }
 
 static int same_bits(const void* a, const void* b, size_t n) { return std::memcmp(a, b, n) == 0; }
+
+// Renderer::render_adaptive_until with queued_rounds 3 against queued_rounds 0 (both through
+// mcpt::adaptive_until over mcpt_adaptive_until_next): 37x21 has partial 8x8 blocks in x and y, 22
+// passes in batches of 4 end in a short batch, and check_every 2 trims the runs of 3 rounds to 2 and
+// sends the fifth and the short sixth batch through single calls.  Threshold 0.3: Python's
+// Renderer.render_adaptive_until with these arguments (tests/test_gpu_adaptive_run.py's scene and
+// size) leaves 289 / 256 / 232 pixels at 8 / 16 / 22 passes and 4 of 15 blocks active; at 0.6 no
+// block retires at 16 and from 0.8 on none reaches the cap.  That some blocks retire early and
+// others live to the cap is asserted below.
+static bool adaptive_until_queued_equals_single(mcpt::BVH_GPU_Scene& scene6) {
+  const int W = 37, H = 21, kBatch = 4, kCap = 22, kCheckEvery = 2, kBounces = 4;
+  const float kThreshold = 0.3f;
+  const mcpt::Camera cam = mcpt::Camera::canonical(W, H);
+  mcpt_adaptive_t rec[2];
+  int rendered[2] = {0, 0};
+  std::vector<float> img[2];
+  std::vector<int> cnt[2];
+  for (int q = 0; q < 2; ++q) {
+    mcpt::Renderer r(0);
+    r.upload(scene6);
+    r.set_target(W, H);
+    rec[q] = r.render_adaptive_until(cam, kThreshold, kBatch, kCap, 0, kCheckEvery, 1, 0.0f, kBounces, 1.0f,
+                                     MCPT_MONTECARLO, &rendered[q], mcpt::Renderer::kErrorMuFloor, q ? 3 : 0);
+    img[q] = r.read_resolved();
+    cnt[q] = r.read_sample_counts();
+  }
+  int least = kCap, most = 0;
+  for (int c : cnt[0]) {
+    least = c < least ? c : least;
+    most = c > most ? c : most;
+  }
+  const mcpt_adaptive_t &a = rec[0], &b = rec[1];
+  const bool some_retire_early = least < kCap && most == kCap;
+  const bool same_image = img[0].size() == (size_t)W * H * 3 && img[0].size() == img[1].size() &&
+                          same_bits(img[0].data(), img[1].data(), img[0].size() * sizeof(float));
+  const bool same_record = a.n_px == b.n_px && a.n_above == b.n_above && a.sum_q == b.sum_q &&
+                           same_bits(&a.max_r, &b.max_r, sizeof(float)) && same_bits(&a.mean_r, &b.mean_r, sizeof(double)) &&
+                           a.passes == b.passes && a.batches == b.batches && a.n_active_blocks == b.n_active_blocks &&
+                           a.n_blocks == b.n_blocks && a.samples == b.samples;
+  const bool ok = some_retire_early && same_image && cnt[0] == cnt[1] && same_record && rendered[0] == kCap &&
+                  rendered[1] == kCap && a.batches == 6 && a.n_blocks == 5 * 3;
+  std::printf("gpu adaptive until queued == single (passes %d..%d, %lld of %lld blocks active): %s\n", least, most,
+              a.n_active_blocks, a.n_blocks, ok ? "ok" : "MISMATCH");
+  return ok;
+}
 
 int main(int argc, char** argv) {
   int fails = 0;
@@ -159,6 +206,11 @@ int main(int argc, char** argv) {
     const bool same = n1 == n2 && acc1.size() == acc2.size() && same_bits(acc1.data(), acc2.data(), acc1.size() * 4);
     std::printf("gpu reference-layout upload bit-equal: %s\n", same ? "ok" : "MISMATCH");
     fails += !same;
+  }
+  if (argc > 1 && std::strcmp(argv[1], "gpu_until") == 0) {
+    mcpt::BVH_GPU_Scene s;
+    s.build_reference(6);
+    fails += !adaptive_until_queued_equals_single(s);
   }
   return fails ? 1 : 0;
 }

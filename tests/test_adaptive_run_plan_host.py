@@ -9,7 +9,7 @@ import pytest
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(REPO, "montecarlo-pathtracing_amd", "csrc")
-CASES = ("schedule", "outcome", "list_groups")
+CASES = ("schedule", "outcome", "list_groups", "until")
 
 
 @pytest.mark.parametrize("flags", [["-O1"], ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]],

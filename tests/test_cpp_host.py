@@ -107,6 +107,16 @@ def test_cpp_host_renders_on_gpu(host_test_bin):
 
 
 @pytest.mark.gpu
+def test_cpp_render_adaptive_until_queued_equals_single(host_test_bin):
+    """Renderer::render_adaptive_until (C++) with queued_rounds 3 and 0: the same resolved bits, sample
+    counts, record and passes (host_api_test.cpp, mode gpu_until), under a time limit of its own."""
+    r = subprocess.run([host_test_bin, "gpu_until"], capture_output=True, text=True, timeout=30)
+    assert r.returncode == 0, r.stdout + r.stderr
+    until = [ln for ln in r.stdout.splitlines() if ln.startswith("gpu adaptive until queued == single")]
+    assert len(until) == 1 and until[0].endswith(": ok"), r.stdout
+
+
+@pytest.mark.gpu
 def test_headless_app_matches_oracle(oracle_mod, tmp_path):
     """mcpt_render --pfm output == fs_frag(oracle accumulation), bit for bit."""
     app = os.path.join(REPO, "montecarlo-pathtracing_amd", "bin", "mcpt_render")
