@@ -44,50 +44,6 @@ int mcpt_err_bare(int status) {
   return status;
 }
 
-// events of sub-launch k of the last call: start / mid / stop
-// (4 per sub-launch: 0 the timed interval's start — for a lane launch that follows one on the
-// other lane, that launch's render end —, 1 the render's end, 2 the combine's end, 3 the render's
-// own start on its stream: 3 -> 1 is the kernel's whole span, overlapped tails included)
-constexpr int kEvPerSub = 4;
-static hipEvent_t ev_start(const mcpt_ctx* c, int k) { return c->evs[c->ring_pos][kEvPerSub * k]; }
-static hipEvent_t ev_stop(const mcpt_ctx* c, int k) { return c->evs[c->ring_pos][kEvPerSub * k + 2]; }
-// event i of sub-launch k in ring slot `slot` (0 start, 1 mid, 2 stop)
-static hipEvent_t ev_at(const mcpt_ctx* c, int slot, int k, int i) { return c->evs[slot][kEvPerSub * k + i]; }
-static hipError_t ensure_events(mcpt_ctx* c, int slot, int n_sub) {
-  if ((int)c->ring_lane[slot].size() < n_sub) c->ring_lane[slot].resize(n_sub, 0);
-  while ((int)c->evs[slot].size() < kEvPerSub * n_sub) {
-    Event e;
-    hipError_t r = e.ensure();
-    if (r != hipSuccess) return r;
-    c->evs[slot].push_back(std::move(e));
-  }
-  return hipSuccess;
-}
-// (path-tracing kernel ms, combine kernel ms) summed over the sub-launches of the call in ring
-// slot `slot` (waits for it)
-static hipError_t slot_launch_ms(const mcpt_ctx* c, int slot, float* trace_ms, float* combine_ms) {
-  *trace_ms = 0.0f; *combine_ms = 0.0f;
-  const std::vector<Event>& v = c->evs[slot];
-  for (int k = 0; k < c->ring_n_sub[slot]; ++k) {
-    float a = 0.0f, b = 0.0f;
-    hipError_t e = hipEventSynchronize(v[kEvPerSub * k + 2]);
-    if (e == hipSuccess) e = hipEventElapsedTime(&a, v[kEvPerSub * k], v[kEvPerSub * k + 1]);
-    if (e == hipSuccess) e = hipEventElapsedTime(&b, v[kEvPerSub * k + 1], v[kEvPerSub * k + 2]);
-    if (e != hipSuccess) return e;
-    *trace_ms += a; *combine_ms += b;
-  }
-  return hipSuccess;
-}
-// ring slot of the call `back` calls before the last one; -1: no such call in the ring
-static int ring_slot_back(const mcpt_ctx* c, int back) {
-  if (back < 0 || back >= kTimingRing || back >= c->n_timed) return -1;
-  return (c->ring_pos - back + kTimingRing) % kTimingRing;
-}
-// the same for the last call
-static hipError_t sub_launch_ms(const mcpt_ctx* c, float* trace_ms, float* combine_ms) {
-  return slot_launch_ms(c, c->ring_pos, trace_ms, combine_ms);
-}
-
 // schedule candidate of the next launch (`segs`: its pass segments; mcpt_plan.h)
 static int resolve_candidate(const mcpt_ctx* c, long long segs) {
   return c->traversal != MCPT_TRAVERSAL_AUTO ? c->traversal : c->tuner.next_candidate(segs);
@@ -105,7 +61,7 @@ static hipError_t collect_tuning(mcpt_ctx* c, int keep) {
   while (c->tuner.n_pend > keep) {
     const plan::Tuner::Pending t0 = c->tuner.pop_oldest();
     float ms = 0.0f, ms_combine = 0.0f;
-    hipError_t e = slot_launch_ms(c, t0.slot, &ms, &ms_combine);
+    hipError_t e = c->ring.launch_ms(t0.slot, &ms, &ms_combine);
     if (e != hipSuccess) return e;
     c->tuner.collect(t0.cand, t0.shape, (double)ms * 1e6 / t0.samples);
   }
@@ -188,18 +144,8 @@ int mcpt_create(int device_ordinal, mcpt_ctx** out) {
   int prio_least = 0, prio_greatest = 0;
   if (hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest) != hipSuccess) prio_greatest = 0;
   hipError_t e = c->own_stream.ensure_with_priority(hipStreamNonBlocking, prio_greatest);
-  for (auto& L : c->lanes) {
-    if (e == hipSuccess) e = L.stream.ensure(hipStreamNonBlocking);
-    if (e == hipSuccess) e = L.freed.ensure(hipEventDisableTiming);
-    if (e == hipSuccess) e = L.tail.ensure(hipEventDisableTiming);
-  }
-  // (recorded once, so that the first waits on them are satisfied)
-  for (auto& L : c->lanes) {
-    if (e == hipSuccess) e = hipEventRecord(L.freed, c->own_stream);
-    if (e == hipSuccess) e = hipEventRecord(L.tail, L.stream);
-  }
+  if (e == hipSuccess) e = c->seq.create(c->own_stream);
   c->tuner.overlap = env_int("MCPT_OVERLAP", 1);
-  if (e == hipSuccess) e = ensure_events(c, 0, 1);
   if (const char* pb = std::getenv("MCPT_PARTIAL_BYTES")) c->partial_budget = (size_t)std::strtoull(pb, nullptr, 10);
 #ifdef MCPT_BLOCKTIMES
   // diagnostic build: per-wave (start, end) clock pairs after the debug slots
@@ -220,7 +166,7 @@ int mcpt_destroy(mcpt_ctx* c) {
   if (!c) return MCPT_OK;
   (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
-  for (auto& L : c->lanes) if (L.stream) (void)hipStreamSynchronize(L.stream);
+  for (auto& L : c->seq.lane) if (L.stream) (void)hipStreamSynchronize(L.stream);
   delete c;   // (every member frees what it owns: mcpt_owned.h)
   return MCPT_OK;
 }
@@ -739,10 +685,11 @@ static int free_stream_pools(mcpt_ctx* c) {
 
 // Buffers of the work-item order for `items` items (grown on demand, with the identity values
 // the sort permutes and its temporary storage)
-static hipError_t ensure_item_order(mcpt_ctx* c, mcpt_ctx::Lane& L, long long items) {
+static hipError_t ensure_item_order(mcpt_ctx* c, int li, long long items) {
+  mcpt_ctx::Lane& L = c->lanes[li];
   if (items <= L.order.cap()) return hipSuccess;
   hipError_t e = hipStreamSynchronize(c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(L.stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->seq.lane[li].stream);
   if (e != hipSuccess) return e;
   L.order = {};
   mcpt_ctx::Lane::Order o;
@@ -836,31 +783,23 @@ extern "C++" int check_renderable(const mcpt_ctx* c, bool args_ok, const char* w
   return MCPT_OK;
 }
 
-// (a lane whose last launches ran in order on `stream` is free once `stream`'s work so far is)
-static hipEvent_t lane_freed(mcpt_ctx* c, mcpt_ctx::Lane& X) {
-  if (X.freed_stale && hipEventRecord(X.freed, c->stream) == hipSuccess) X.freed_stale = false;
-  return X.freed;
-}
 static bool holds_order(const mcpt_ctx::Lane& L, const plan::Items& it) {
   return L.order.valid && std::equal(it.key, it.key + 8, L.order.key);
 }
 
-// An ordered sub-launch on lane li (its render and set-up on `ws`): the order it runs, its tail
-// pieces and its cleared item costs
-static int prepare_order(mcpt_ctx* c, int li, hipStream_t ws, const plan::ItemsIn& in, const plan::Items& it,
+// An ordered sub-launch s (its render and set-up on s.ws): the order it runs, its tail pieces and
+// its cleared item costs
+static int prepare_order(mcpt_ctx* c, const mcpt::LaneSeq::Sub& s, const plan::ItemsIn& in, const plan::Items& it,
                          mcpt::RenderParams& p) {
-  mcpt_ctx::Lane &L = c->lanes[li], &O = c->lanes[li ^ 1];
+  mcpt_ctx::Lane &L = c->lanes[s.li], &O = c->lanes[s.li ^ 1];
   // the other lane holds this shape's order (AUTO's trials alternate candidates between the
   // lanes; a new shape's first launches): copied once its last sort is done, so that a trial
   // runs the order a settled launch of its candidate would
   if (!holds_order(L, it) && holds_order(O, it) && O.order.cap() >= it.items) {
-    HIP_OR_RETURN(hipStreamWaitEvent(ws, O.tail, 0));
-    HIP_OR_RETURN(hipStreamWaitEvent(ws, lane_freed(c, O), 0));
-    HIP_OR_RETURN(hipMemcpyAsync(L.order.d_item_perm, O.order.d_item_perm, sizeof(int) * (size_t)it.items, hipMemcpyDeviceToDevice, ws));
-    HIP_OR_RETURN(hipMemcpyAsync(L.order.d_split_n, O.order.d_split_n, sizeof(int), hipMemcpyDeviceToDevice, ws));
-    // (the other lane's next sort, which rewrites its order, waits for the copy)
-    HIP_OR_RETURN(hipEventRecord(L.tail, ws));
-    HIP_OR_RETURN(hipStreamWaitEvent(O.stream, L.tail, 0));
+    HIP_OR_RETURN(c->seq.before_order_copy(s));
+    HIP_OR_RETURN(hipMemcpyAsync(L.order.d_item_perm, O.order.d_item_perm, sizeof(int) * (size_t)it.items, hipMemcpyDeviceToDevice, s.ws));
+    HIP_OR_RETURN(hipMemcpyAsync(L.order.d_split_n, O.order.d_split_n, sizeof(int), hipMemcpyDeviceToDevice, s.ws));
+    HIP_OR_RETURN(c->seq.after_order_copy(s));
     std::copy(it.key, it.key + 8, L.order.key);
     L.order.valid = true;
     L.order.age = O.order.age;
@@ -869,7 +808,7 @@ static int prepare_order(mcpt_ctx* c, int li, hipStream_t ws, const plan::ItemsI
     p.item_perm = L.order.d_item_perm;
     p.tail_m = plan::tail_m(in, it, true);
   }
-  HIP_OR_RETURN(hipMemsetAsync(L.order.d_item_cost, 0, sizeof(unsigned) * (size_t)it.items, ws));
+  HIP_OR_RETURN(hipMemsetAsync(L.order.d_item_cost, 0, sizeof(unsigned) * (size_t)it.items, s.ws));
   p.item_cost = L.order.d_item_cost;
   return MCPT_OK;
 }
@@ -952,21 +891,14 @@ static int launch(mcpt_ctx* c, const float* invPV, const float* invV, int first_
   if (split) p.seg_per_item = 1;
   const int n_sub = plan::count_sub_launches(first_pass, n_passes, lim.max_seg, split);
   const size_t seg_bytes = (size_t)p.n_local_px * 3 * sizeof(float);
-  const int slot = (c->ring_pos + 1) % kTimingRing;   // this call's events (ring of calls)
-  HIP_OR_RETURN(ensure_events(c, slot, std::max(n_sub, 1)));
+  HIP_OR_RETURN(c->ring.begin(n_sub));   // this call's events: the ring's next slot, the last call's once committed
   // lane launches (mcpt_ctx::Lane) once AUTO has settled.  (AUTO's trials run in order on
   // `stream`: on the lanes a trial's period would be charged its own tail and discounted the
   // previous trial's, which favours the candidates with short items — C2 / C5 picked two segments
   // per item where four are 3 % faster on the lanes, tools/seg_ab.py, profiles/r06_seg_ab.jsonl)
   const bool lanes_ok = tuner.overlap != 0 && !count && !stream && schedule_settled(c);
   if (count) HIP_OR_RETURN(hipMemsetAsync(c->d_events, 0, sizeof(unsigned long long) * mcpt::EV_COUNT, c->stream));
-  // The call's events go to ring slot `slot`; the ring position (what mcpt_last_render_ms and
-  // the AUTO timing read) moves there only once every event of the call has been recorded, so a
-  // call that fails part-way leaves the previous call's complete timings in place.
-  if (n_sub == 0) {   // no passes: an empty timed interval
-    for (int i = 0; i < kEvPerSub; ++i) HIP_OR_RETURN(hipEventRecord(ev_at(c, slot, 0, i), c->stream));
-    c->ring_lane[slot][0] = 0;
-  }
+  if (n_sub == 0) HIP_OR_RETURN(c->ring.record_empty(c->stream));
   plan::ItemsIn in;
   in.n_tiles = p.n_tiles; in.seg_per_item = p.seg_per_item; in.walk_exit = p.walk_exit; in.bounces = bounces;
   in.variant = variant; in.tile_w = p.tile_w; in.n_cu = c->n_cu; in.wave_traversal = p.wave_traversal != 0;
@@ -989,21 +921,16 @@ static int launch(mcpt_ctx* c, const float* invPV, const float* invV, int first_
 #ifdef MCPT_CHECKED
     p.check_inject = env_int("MCPT_CHECKED_INJECT", 0);
 #endif
-    // the sub-launch's lane: its segment-sum buffer and work-item order state.  A lane launch
-    // (several segments: the render writes only the lane's buffers) runs its set-up and render on
-    // the lane's stream once the lane's previous combine is done, so it can start while the
-    // previous launch's last workgroups still run; the combine follows on `stream` in call order.
-    const int li = c->next_lane;
-    c->next_lane ^= 1;
-    mcpt_ctx::Lane& L = c->lanes[li];
-    const bool lane = lanes_ok && p.n_segments > 1;
-    hipStream_t ws = lane ? L.stream : c->stream;   // the stream of the render and its set-up
+    // the sub-launch's lane: its segment-sum buffer and work-item order state; a lane launch renders
+    // on the lane's stream s.ws, else on `stream` (mcpt_launch_seq.h: the steps on `seq`, in its order)
+    const mcpt::LaneSeq::Sub s = c->seq.pick(k, lanes_ok && p.n_segments > 1, c->stream);
+    mcpt_ctx::Lane& L = c->lanes[s.li];
     if (p.n_segments > 1) OK_OR_RETURN(ensure_lane_bytes(c, L.d_partial, (size_t)p.n_segments * seg_bytes));
     p.partial = L.d_partial;
-    if (it.order) HIP_OR_RETURN(ensure_item_order(c, L, it.items));
-    if (lane) HIP_OR_RETURN(hipStreamWaitEvent(L.stream, lane_freed(c, L), 0));
-    if (it.order) OK_OR_RETURN(prepare_order(c, li, ws, in, it, p));
-    if (it.split_items) OK_OR_RETURN(prepare_split_items(L, ws, it.items, p));
+    if (it.order) HIP_OR_RETURN(ensure_item_order(c, s.li, it.items));
+    HIP_OR_RETURN(c->seq.acquire(s));
+    if (it.order) OK_OR_RETURN(prepare_order(c, s, in, it, p));
+    if (it.split_items) OK_OR_RETURN(prepare_split_items(L, s.ws, it.items, p));
     // pass stealing (MCPT_STEAL=0: off, tests and A/B; the same bits either way): the mesh kernels
     // in split-item launches, the LDS-scene kernels in launches of several segments (launches of
     // one segment add into the accumulator themselves, pass-split ones run one pass per item:
@@ -1013,48 +940,27 @@ static int launch(mcpt_ctx* c, const float* invPV, const float* invV, int first_
                                      (size_t)plan::steal_store_bytes(p.n_tiles, p.tile_w, p.n_segments)));
       p.steal_vals = L.d_steal;
     }
-    // The timed interval of a lane launch that follows one on the other lane starts where that
-    // launch's render ended (recorded on its stream): the launches overlap, and each is charged
-    // its period, not its whole span (which would count the overlapped tails twice)
-    const bool period = lane && c->prev_lane >= 0 && c->prev_lane != li;
-    HIP_OR_RETURN(hipEventRecord(ev_at(c, slot, k, 0), period ? c->lanes[c->prev_lane].stream : ws));
-    if (lane) HIP_OR_RETURN(hipEventRecord(ev_at(c, slot, k, 3), ws));   // (in order: the span is 0 -> 1)
-    c->ring_lane[slot][k] = lane;
+    HIP_OR_RETURN(c->seq.start(c->ring, s));
     if (stream) {
       OK_OR_RETURN(stream_run(c, p));
     } else {
-      HIP_OR_RETURN(mcpt_launch_render(p, count, ws));
+      HIP_OR_RETURN(mcpt_launch_render(p, count, s.ws));
     }
-    HIP_OR_RETURN(hipEventRecord(ev_at(c, slot, k, 1), ws));
-    if (lane) {   // the combine after the render; (the period's start too, so that the events a
-                  // caller reads once the combine's end has completed are all complete)
-      HIP_OR_RETURN(hipStreamWaitEvent(c->stream, ev_at(c, slot, k, 1), 0));
-      if (period) HIP_OR_RETURN(hipStreamWaitEvent(c->stream, ev_at(c, slot, k, 0), 0));
-    }
+    HIP_OR_RETURN(c->seq.render_done(c->ring, s));
     HIP_OR_RETURN(mcpt_launch_combine(p, c->stream));
-    HIP_OR_RETURN(hipEventRecord(ev_at(c, slot, k, 2), c->stream));
-    if (it.order && (!p.item_perm || ++L.order.age >= plan::kOrderRefresh)) OK_OR_RETURN(sort_order(c, L, ws, it, p));
-    if (lane) {   // `stream` stays ordered after all of the lane's work; the lane is free after it
-      HIP_OR_RETURN(hipEventRecord(L.tail, L.stream));
-      HIP_OR_RETURN(hipStreamWaitEvent(c->stream, L.tail, 0));
-      HIP_OR_RETURN(hipEventRecord(L.freed, c->stream));
-    }
-    L.freed_stale = !lane;
-    c->prev_lane = lane ? li : -1;
+    HIP_OR_RETURN(c->seq.combine_done(c->ring, s));
+    if (it.order && (!p.item_perm || ++L.order.age >= plan::kOrderRefresh)) OK_OR_RETURN(sort_order(c, L, s.ws, it, p));
+    HIP_OR_RETURN(c->seq.release(s));
 #ifdef MCPT_CHECKED
     // checked build: the sub-launch (render, combine, order sort) is waited for here, so a fault
     // is reported with the sub-launch that caused it, and the kernels' bounds tests are read
     OK_OR_RETURN(checked_sub_launch(c, k, n_sub, p));
 #endif
   }
+  c->ring.commit();
   if (!count && c->traversal == MCPT_TRAVERSAL_AUTO)
-    tuner.issue(cand, (double)p.n_local_px * n_passes, p.n_local_px, n_passes, total_seg, slot);
-  c->n_sub = std::max(n_sub, 1);
-  c->ring_pos = slot;
-  c->ring_n_sub[slot] = c->n_sub;
-  c->n_timed++;
+    tuner.issue(cand, (double)p.n_local_px * n_passes, p.n_local_px, n_passes, total_seg, c->ring.pos());
   c->pass_split = split ? 1 : 0;
-  c->timed = true;
   c->pass_count += n_passes;
   // adaptive mode on: a plain render reaches every pixel, retired blocks included
   if (c->adaptive.ad_on && n_passes > 0)
@@ -1283,7 +1189,7 @@ int mcpt_set_render_lanes(mcpt_ctx* c, int on) {
   HIP_OR_RETURN(hipSetDevice(c->device));
   HIP_OR_RETURN(hipStreamSynchronize(c->stream));   // (ordered after every lane's work)
   c->tuner.overlap = on ? 1 : 0;
-  c->prev_lane = -1;
+  c->seq.lanes_switched();
   return MCPT_OK;
 }
 
@@ -1295,13 +1201,13 @@ int mcpt_set_partial_budget(mcpt_ctx* c, size_t bytes) {
 
 int mcpt_last_launch_count(mcpt_ctx* c, int* n_launches) {
   if (!c || !n_launches) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
-  *n_launches = c->timed ? c->n_sub : 0;
+  *n_launches = c->ring.n_sub();
   return MCPT_OK;
 }
 
 int mcpt_last_pass_split(mcpt_ctx* c, int* split) {
   if (!c || !split) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
-  *split = c->timed ? c->pass_split : 0;
+  *split = c->ring.n_timed() > 0 ? c->pass_split : 0;
   return MCPT_OK;
 }
 
@@ -1356,45 +1262,34 @@ int mcpt_synchronize(mcpt_ctx* c) {
 
 int mcpt_last_render_ms(mcpt_ctx* c, float* ms) {
   if (!c || !ms) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
-  if (!c->timed) return set_err(MCPT_ERR_INVALID_ARG, "no render timed yet");
+  if (c->ring.n_timed() == 0) return set_err(MCPT_ERR_INVALID_ARG, "no render timed yet");
   HIP_OR_RETURN(hipSetDevice(c->device));
-  HIP_OR_RETURN(hipEventSynchronize(ev_stop(c, c->n_sub - 1)));
-  HIP_OR_RETURN(hipEventElapsedTime(ms, ev_start(c, 0), ev_stop(c, c->n_sub - 1)));
+  HIP_OR_RETURN(c->ring.call_ms(ms));
   return MCPT_OK;
 }
 
 int mcpt_kernel_ms_back(mcpt_ctx* c, int back, float* trace_ms, float* combine_ms) {
   if (!c || !trace_ms || !combine_ms) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
-  const int slot = ring_slot_back(c, back);
+  const int slot = c->ring.slot_back(back);
   if (slot < 0) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_kernel_ms_back: no such call in the timing ring");
   HIP_OR_RETURN(hipSetDevice(c->device));
-  HIP_OR_RETURN(slot_launch_ms(c, slot, trace_ms, combine_ms));
+  HIP_OR_RETURN(c->ring.launch_ms(slot, trace_ms, combine_ms));
   return MCPT_OK;
 }
 
 int mcpt_kernel_span_ms_back(mcpt_ctx* c, int back, float* span_ms) {
   if (!c || !span_ms) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
-  const int slot = ring_slot_back(c, back);
+  const int slot = c->ring.slot_back(back);
   if (slot < 0) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_kernel_span_ms_back: no such call in the timing ring");
   HIP_OR_RETURN(hipSetDevice(c->device));
-  const std::vector<Event>& v = c->evs[slot];
-  float tot = 0.0f;
-  for (int k = 0; k < c->ring_n_sub[slot]; ++k) {
-    float a = 0.0f;
-    HIP_OR_RETURN(hipEventSynchronize(v[kEvPerSub * k + 1]));
-    HIP_OR_RETURN(hipEventElapsedTime(&a, v[kEvPerSub * k + (c->ring_lane[slot][k] ? 3 : 0)], v[kEvPerSub * k + 1]));
-    tot += a;
-  }
-  *span_ms = tot;
+  HIP_OR_RETURN(c->ring.span_ms(slot, span_ms));
   return MCPT_OK;
 }
 
 int mcpt_last_kernel_ms(mcpt_ctx* c, float* trace_ms, float* combine_ms) {
   if (!c || !trace_ms || !combine_ms) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
-  if (!c->timed) return set_err(MCPT_ERR_INVALID_ARG, "no render timed yet");
-  HIP_OR_RETURN(hipSetDevice(c->device));
-  HIP_OR_RETURN(sub_launch_ms(c, trace_ms, combine_ms));
-  return MCPT_OK;
+  if (c->ring.n_timed() == 0) return set_err(MCPT_ERR_INVALID_ARG, "no render timed yet");
+  return mcpt_kernel_ms_back(c, 0, trace_ms, combine_ms);
 }
 
 }  // extern "C"

@@ -653,7 +653,7 @@ static int adaptive_round(mcpt_ctx* c, const float* invPV, const float* invV, in
     p.partial = L.d_partial;
     HIP_OR_RETURN(mcpt_launch_render_list(p, c->stream));
     HIP_OR_RETURN(mcpt_launch_combine_list(p, c->stream));
-    L.freed_stale = true;   // (the lane's next launch waits for `stream`'s work so far)
+    c->seq.used_in_order(0);   // (the lane's next launch waits for `stream`'s work so far)
 #ifdef MCPT_CHECKED
     OK_OR_RETURN(checked_sub_launch(c, k, -1, p));
 #endif

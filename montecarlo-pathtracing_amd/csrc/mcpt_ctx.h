@@ -13,6 +13,7 @@
 #include "mcpt_adaptive_run_plan.h"
 #include "mcpt_gather_plan.h"
 #include "mcpt_internal.h"
+#include "mcpt_launch_seq.h"
 #include "mcpt_owned.h"
 #include "mcpt_plan.h"
 
@@ -33,9 +34,6 @@ int set_err(int status, const char* what, hipError_t e = hipSuccess);
 
 using mcpt::DevBuf, mcpt::Event, mcpt::HostBuf, mcpt::Stream;
 
-// render calls whose events a context keeps (mcpt_kernel_ms_back)
-constexpr int kTimingRing = 64;
-
 // The context.  What it holds on the device is owned by type (mcpt_owned.h), one nested struct per
 // lifetime with the plain state that ends with it: ending a lifetime is `c->group = {}`.  Members are
 // destroyed last to first, so the streams (own_stream, the lanes', the pools') stand before the buffers.
@@ -44,18 +42,11 @@ struct mcpt_ctx {
   Stream own_stream;
   hipStream_t stream = nullptr;     // own_stream, or the caller's (mcpt_set_stream): borrowed
   // Render lanes (round 6): the sub-launches of render calls alternate between two lanes, each with
-  // its own HIP stream, segment-sum buffer and work-item order state, so that a launch's render
-  // kernel can start while the previous launch's last workgroups still run (its tail).  The
-  // combines stay in call order on `stream`; a lane's next render waits for the lane's previous
-  // combine (its buffers free).  Lane launches are only used once AUTO has settled, for launches
-  // of several pass segments (a one-segment launch adds into the accumulator itself).
-  // Lifetime: stream and events the context's; the buffers to the next mcpt_set_target*.
+  // its own HIP stream, segment-sum buffer and work-item order state, so that a launch's render can
+  // start while the previous launch's tail still runs.  Lane i's stream and events, and what orders it
+  // against `stream`: seq.lane[i] (mcpt_launch_seq.h), the context's; its buffers: to the next mcpt_set_target*.
+  mcpt::LaneSeq seq;
   struct Lane {
-    Stream stream;
-    Event freed;                    // on `stream` after the lane's last combine: its buffers are free
-    bool freed_stale = false;       // launches in order on `stream` used the lane since (not recorded:
-                                    // launch-bound calls skip the record; the next waiter records it)
-    Event tail;                     // on the lane's stream after its last operation
     DevBuf<float> d_partial;        // pass-segment sums (launches spanning > 1 chunk)
     DevBuf<float> d_split_pass;     // split items: the later pieces' per-pass values
     DevBuf<float> d_steal;          // pass stealing: every pass's value (RenderParams::steal_vals)
@@ -76,8 +67,6 @@ struct mcpt_ctx {
     void drop_target_sized() { d_partial.reset(); d_split_pass.reset(); d_steal.reset(); order = {}; }
   };
   Lane lanes[2];
-  int next_lane = 0;                // the lane of the next sub-launch
-  int prev_lane = -1;               // the lane of the previous sub-launch if it was a lane launch, else -1
   // stream schedule (MCPT_TRAVERSAL_STREAM): slot pool, payload queues, counters.  Lifetime: the
   // context's, but the slots and queues (4 GB by default) go once the schedule is deselected.
   struct Pools {
@@ -122,18 +111,8 @@ struct mcpt_ctx {
   int pass_count = 0;
   bool has_target = false;
   DevBuf<unsigned long long> d_events;
-  // per sub-launch of a render call: (start, after the path-tracing kernel, after the combine
-  // kernel); a call is split into sub-launches at chunk boundaries (partial_budget).  The last
-  // kTimingRing calls keep their events (mcpt_kernel_ms_back), so a caller can time a run of
-  // calls without waiting after each; ring_pos = the last call's slot.
-  std::vector<Event> evs[kTimingRing];
-  int ring_n_sub[kTimingRing] = {};
-  std::vector<char> ring_lane[kTimingRing];   // per sub-launch: a lane launch
-  int ring_pos = 0;
-  long long n_timed = 0;            // render calls timed so far
-  int n_sub = 0;                    // sub-launches of the last render call
+  mcpt::TimingRing ring;            // the events of the last render calls (mcpt_launch_seq.h)
   int pass_split = 0;               // the last render call ran one segment per pass (launch())
-  bool timed = false;
   size_t partial_budget = mcpt::plan::kDefaultPartialBudget;
   int traversal = MCPT_TRAVERSAL_AUTO;
   mcpt::plan::Tuner tuner;          // AUTO schedule: its trials and decision (mcpt_plan.h), overlap, BVH depth

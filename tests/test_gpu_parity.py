@@ -553,6 +553,43 @@ def test_kernel_ms_back_ring(mcpt_mod, renderer):
         r2.close()
 
 
+def test_lane_launch_timings(mcpt_mod, monkeypatch):
+    """The timing entries on lane launches (mcpt_launch_seq.h): two calls of 96 passes (three segments,
+    one lane launch each), then one of 192 passes cut into three lane sub-launches of two segments.
+    Every entry answers for the three calls, the kernels' spans and the last call's time are positive,
+    and the accumulator equals the same calls with the lanes off (MCPT_OVERLAP=0), bit for bit.  A lane
+    launch's period (the trace ms) is not asserted: at this size a later render can end before the
+    earlier one (finding 2)."""
+    W, H, B = 64, 40, 8
+    ipv, iv = mcpt_mod.camera_canonical(W, H)
+    out = {}
+    for ov in ("1", "0"):
+        monkeypatch.setenv("MCPT_OVERLAP", ov)
+        r = mcpt_mod.Renderer(0)
+        try:
+            r.set_traversal(1)   # settled at once: lanes on
+            r.upload_scene(mcpt_mod.Scene.reference(6))
+            r.set_target(W, H)
+            r.render(ipv, iv, 1, 96, 0.0, B, 1.0, 0)
+            r.render(ipv, iv, 97, 96, 0.0, B, 1.0, 0)
+            r.set_partial_budget(W * H * 12 * 2)   # two segments per sub-launch
+            r.render(ipv, iv, 193, 192, 0.0, B, 1.0, 0)
+            assert r.last_launch_count() == 3
+            if ov == "1":
+                for b in range(3):
+                    r.kernel_ms_back(b)   # (raises unless the entry returns OK)
+                    assert r.kernel_span_ms_back(b) > 0.0
+                assert r.last_render_ms() > 0.0
+                assert r.kernel_ms_back(0) == r.last_kernel_ms()
+                with pytest.raises(RuntimeError):
+                    r.kernel_ms_back(3)
+            out[ov], n = r.read_accum()
+        finally:
+            r.close()
+        assert n == 384
+    assert np.array_equal(out["1"].view(np.uint32), out["0"].view(np.uint32))
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("scene_id,traversal", [(6, 1), (8, 1), (3, 2)])
 def test_item_order_same_bits(mcpt_mod, renderer, monkeypatch, scene_id, traversal):
