@@ -118,6 +118,50 @@ int mcpt_upload_meshes(mcpt_ctx* ctx, int n_meshes, const int* info, int n_nodes
                        const int* leaves, int n_tris, const int* tris, int n_verts, const float* verts,
                        const float* normals);
 
+/* Deforming meshes (no reference equivalent: its meshes are static): new vertices
+ * into the uploaded meshes, then a refit of their BVH records on the device — same topology (the
+ * triangles, the depth and the leaf order of the upload), new boxes.
+ *
+ * mcpt_update_mesh_vertices copies n_vertices x 3 f32 positions and normals from the host (through a
+ * staging buffer of the context) over the uploaded vertices first_vertex .. (indices into the flat
+ * verts / normals arrays of mcpt_upload_meshes: mcpt_scene_mesh_vertex_range);
+ * mcpt_update_mesh_vertices_device takes them packed in memory of the context's device, complete
+ * before the call (a simulation's output).  One kernel on the context's stream widens them into
+ * place.  MCPT_ERR_BAD_SCENE with no meshes uploaded, MCPT_ERR_INVALID_ARG for a range outside the
+ * uploaded vertices.  The caller keeps every vertex inside the Mesh::BB() its mesh was added with
+ * (mcpt_scene_update_mesh checks that on the host): the instances' scene-level boxes do not move.
+ *
+ * mcpt_refit_mesh rewrites mesh mesh_id's (-1: every mesh's) leaf triangle records and child-pair
+ * records from the current vertices: the bits mcpt_upload_meshes writes from the buffers of a
+ * mcpt_scene_update_mesh with the same vertices.  It runs on the context's stream behind every
+ * queued render and ahead of every later one, without a host wait unless `out` is given (then it
+ * waits once and fills the record).  Both calls invalidate the guide buffers and empty the
+ * temporal history, as mcpt_upload_meshes does; the AUTO schedule, the work-item order, the noise
+ * statistics, the adaptive state and the accumulator stay (whether to clear them is the caller's
+ * decision).  A mesh of depth 0 (one triangle) has no records: only its vertices change.
+ * MCPT_ERR_BAD_SCENE with no meshes uploaded, or for a mesh uploaded with a leaf pair that holds no
+ * triangle (mcpt_scene_add_mesh never builds one); MCPT_ERR_INVALID_ARG for an unknown mesh id; the
+ * records stay as they are then. */
+typedef struct mcpt_refit_t {
+  long long triangles;        /* leaf triangle records written */
+  long long leaves;           /* leaves visited (2^depth per mesh) */
+  long long internal_nodes;   /* child-pair records written */
+  float device_ms;            /* the refit's kernels, from HIP events */
+  int has_root;               /* 1: root_box is set (a single mesh of depth >= 1) */
+  float root_box[6];          /* the mesh's new root box (min.xyz, max.xyz), mesh space */
+} mcpt_refit_t;
+int mcpt_update_mesh_vertices(mcpt_ctx* ctx, int first_vertex, int n_vertices, const float* verts, const float* normals);
+int mcpt_update_mesh_vertices_device(mcpt_ctx* ctx, int first_vertex, int n_vertices, const void* verts_dev,
+                                     const void* normals_dev);
+int mcpt_refit_mesh(mcpt_ctx* ctx, int mesh_id, mcpt_refit_t* out);
+/* Diagnostics: the device's mesh BVH records as they stand — the child-pair slots (4 x 4 f32 per
+ * slot: (c_left, has) (w_left, in_range) (c_right, has) (w_right, 0); each mesh's run starts at an
+ * even slot, internal node i at slot i + 1 of the run) and the leaf triangle records (4 x 4 f32 per
+ * leaf: (A, triangle id bits) (B - A, 0) (C - A, 0) (0)).  mcpt_debug_mesh_record_sizes gives the
+ * float counts the copy expects; a NULL pointer skips that array.  Synchronizes. */
+int mcpt_debug_mesh_record_sizes(mcpt_ctx* ctx, size_t* pair_floats, size_t* leaf_floats);
+int mcpt_debug_mesh_records(mcpt_ctx* ctx, float* pairs_out, size_t pair_floats, float* leaves_out, size_t leaf_floats);
+
 /* uniform flat_face (raytracer_func.frag:26, location 3): flat triangle normals instead of
  * the area-weighted vertex normals.  The reference never sets it (false); default 0. */
 int mcpt_set_flat_face(mcpt_ctx* ctx, int flat_face);
@@ -914,6 +958,18 @@ int mcpt_scene_place_mesh(mcpt_scene* s, int mesh_id, const float* trf16, const 
 int mcpt_scene_mesh_sizes(mcpt_scene* s, int* n_meshes, int* n_nodes, int* n_leaves, int* n_tris, int* n_verts);
 int mcpt_scene_get_mesh_buffers(mcpt_scene* s, int* info, float* nodes, int* leaves, int* tris, float* verts,
                                 float* normals);
+/* Same-topology update of mesh mesh_id (no reference equivalent): replaces its vertices and normals
+ * (n_vertices must be the mesh's count, else MCPT_ERR_INVALID_ARG) and refits its BVH boxes; the
+ * triangles, the depth and the leaves are kept.  Every leaf gets its triangle's box, a -1 leaf its
+ * sibling's, the internal boxes are merged bottom-up as add_mesh merges them: an update with the
+ * mesh's own vertices leaves mcpt_scene_get_mesh_buffers bit-identical.  Every new vertex must lie
+ * inside the Mesh::BB() the mesh was added with (pass a roomy bb6 to add_mesh for a mesh that will
+ * move): the instances' scene-level boxes are trf · BB, and geometry outside would be clipped
+ * silently — MCPT_ERR_BAD_SCENE then, and nothing changes.  The scene stays finalized; its prims,
+ * nodes and leaves are untouched.  This is the specification of mcpt_refit_mesh. */
+int mcpt_scene_update_mesh(mcpt_scene* s, int mesh_id, const float* vertices, const float* normals, int n_vertices);
+/* mesh mesh_id's range in the flat verts / normals arrays of mcpt_scene_get_mesh_buffers */
+int mcpt_scene_mesh_vertex_range(mcpt_scene* s, int mesh_id, int* first_vertex, int* n_vertices);
 /* sortEmissiveFirst + BVH_KDtree::compute (scene.cpp:70-88, bvh.cpp:34-93) */
 int mcpt_scene_finalize(mcpt_scene* s);
 int mcpt_scene_nb_prim(mcpt_scene* s, int* n);

@@ -235,6 +235,19 @@ class BVH_GPU_Scene {
     mat.pack(m7);
     check(mcpt_scene_place_mesh(s(), i, trf.m, m7), "mcpt_scene_place_mesh");
   }
+  // same-topology update of mesh i (no reference equivalent): m's vertices and normals replace the
+  // mesh's and its BVH boxes are refitted; every vertex inside the bb the mesh was added with
+  void update_mesh(int i, const SP_Mesh& m) {
+    if (!m || m->vertices_.empty() || m->normals_.size() != m->vertices_.size())
+      throw Error("update_mesh (mesh needs vertices and one normal per vertex)", MCPT_ERR_INVALID_ARG);
+    check(mcpt_scene_update_mesh(s(), i, m->vertices_[0].v, m->normals_[0].v, m->nb_vertices()), "mcpt_scene_update_mesh");
+  }
+  // mesh i's first vertex in the flat vertex arrays (Renderer::update_mesh_vertices)
+  int mesh_first_vertex(int i) const {
+    int first = 0, n = 0;
+    check(mcpt_scene_mesh_vertex_range(s(), i, &first, &n), "mcpt_scene_mesh_vertex_range");
+    return first;
+  }
   void finalize() { check(mcpt_scene_finalize(s()), "mcpt_scene_finalize"); }
   int depth(int /*bvh*/ = 0) const { return scene_->depth_(); }
   int nb_prim() const { return scene_->nb(); }
@@ -357,6 +370,22 @@ class Renderer {
                                verts.data(), norms.data()),
             "mcpt_upload_meshes");
     }
+  }
+  // deforming meshes (mcpt.h): n x 3 positions and normals over the uploaded vertices from `first`
+  // on (BVH_GPU_Scene::mesh_first_vertex), then the refit of mesh i's records (-1: every mesh's) on
+  // the device; want_record waits once and fills the record
+  void update_mesh_vertices(int first, const std::vector<GLVec3>& verts, const std::vector<GLVec3>& normals) {
+    if (verts.empty() || normals.size() != verts.size())
+      throw Error("update_mesh_vertices (one normal per vertex)", MCPT_ERR_INVALID_ARG);
+    check(mcpt_update_mesh_vertices(c_, first, (int)verts.size(), verts[0].v, normals[0].v), "mcpt_update_mesh_vertices");
+  }
+  void update_mesh_vertices_device(int first, int n, const void* verts_dev, const void* normals_dev) {
+    check(mcpt_update_mesh_vertices_device(c_, first, n, verts_dev, normals_dev), "mcpt_update_mesh_vertices_device");
+  }
+  mcpt_refit_t refit_mesh(int i = -1, bool want_record = true) {
+    mcpt_refit_t rec{};
+    check(mcpt_refit_mesh(c_, i, want_record ? &rec : nullptr), "mcpt_refit_mesh");
+    return rec;
   }
   // the reference's own arrays, as BVH_GPU_Scene::finalize hands them to its textures:
   // ScenePrimitives::prim_data() (scene.h:86-89) and the root BVH_KDtree's data_BB() /

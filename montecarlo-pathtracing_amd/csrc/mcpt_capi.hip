@@ -361,11 +361,16 @@ int mcpt_upload_meshes(mcpt_ctx* c, int n_meshes, const int* info, int n_nodes, 
   // (-1: an empty leaf) as int bits
   std::vector<float4> hl((size_t)n_leaves * 4, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
   for (int k = 0; k < n_leaves; ++k) hl[(size_t)k * 4].w = int_bits_f(-1);
+  std::vector<int> leaf_tris(n_meshes, 0);
+  std::vector<char> empty_pair(n_meshes, 0);
   for (int m = 0; m < n_meshes; ++m) {
     const int lo = info[4 * m + 1], d = info[4 * m + 2], to = info[4 * m + 3];
     for (int k = 0; k < (1 << d); ++k) {
       const int t = leaves[lo + k];
+      // (a leaf pair without a triangle has no box to refit from: mcpt_refit_mesh refuses the mesh)
+      if (t < 0 && d >= 1 && leaves[lo + (k ^ 1)] < 0) empty_pair[m] = 1;
       if (t < 0) continue;
+      ++leaf_tris[m];
       const int4 vi = ht[to + t];
       const float4 A = hv[vi.x], B = hv[vi.y], C = hv[vi.z];
       float4* r = &hl[(size_t)(lo + k) * 4];
@@ -391,7 +396,10 @@ int mcpt_upload_meshes(mcpt_ctx* c, int n_meshes, const int* info, int n_nodes, 
   HIP_OR_RETURN(hipMemcpy(ms.d_mtris, ht.data(), ht.size() * sizeof(int4), hipMemcpyHostToDevice));
   HIP_OR_RETURN(hipMemcpy(ms.d_mverts, hv.data(), hv.size() * sizeof(float4), hipMemcpyHostToDevice));
   HIP_OR_RETURN(hipMemcpy(ms.d_mnorms, hm.data(), hm.size() * sizeof(float4), hipMemcpyHostToDevice));
-  ms.n_meshes = n_meshes; c->meshes = std::move(ms);
+  ms.n_meshes = n_meshes;
+  ms.info = std::move(hi); ms.leaf_tris = std::move(leaf_tris); ms.empty_pair = std::move(empty_pair);
+  ms.n_pair_f4 = hn.size(); ms.n_leaf_f4 = hl.size();
+  c->meshes = std::move(ms);
   return MCPT_OK;
 }
 

@@ -98,6 +98,16 @@ struct mcpt_ctx {
     DevBuf<int4> d_mtris;
     DevBuf<float4> d_mverts, d_mnorms;
     int n_meshes = 0;
+    // what a refit (mcpt_refit.hip) needs of the upload: per mesh the device info
+    // (first pair slot, first leaf, depth, first triangle), how many leaves hold a triangle and
+    // whether some leaf pair holds none (such a mesh cannot be refitted); the records' sizes
+    std::vector<int4> info;
+    std::vector<int> leaf_tris;
+    std::vector<char> empty_pair;
+    size_t n_pair_f4 = 0, n_leaf_f4 = 0;
+    DevBuf<float4> d_refit_scratch; // subtree roots between a refit's stages: sized at the first refit
+    DevBuf<float> d_vert_staging;   // mcpt_update_mesh_vertices: the host arrays on their way
+    Event refit_ev[2];              // around the last refit that asked for its record
   } meshes;
   int flat_face = 0;
   std::vector<int> mesh_ids;     // per primitive: mesh id of a CODE_MESH record, else -1

@@ -115,6 +115,7 @@ static Vec3 apply_pt(const Mat4& t, float x, float y, float z) {
 
 static void kd_build(const std::vector<Vec3>& centre, const std::vector<float>& box, int& depth,
                      std::vector<float>& nodes, std::vector<int>& leaves);
+static void merge_up(std::vector<float>& nodes);
 
 // PrimData record (scene.h:64-73) + the BVH built over the records
 class PrimScene {
@@ -271,6 +272,36 @@ class PrimScene {
     return (int)meshes.size() - 1;
   }
 
+  // Same-topology update (no reference equivalent: the reference's meshes are static): new
+  // vertices and normals, the triangles, depth and leaves kept; the boxes refitted — every leaf
+  // its triangle's tri_box, a -1 leaf its sibling's box (kd_build's lone item), the internal boxes
+  // merged as kd_build merges them.  Every vertex must lie inside the Mesh::BB() the mesh was
+  // added with: the instances' scene-level boxes are trf · BB and do not move.
+  int update_mesh(int mesh, const float* v, const float* nrm, int nv) {
+    if (mesh < 0 || mesh >= (int)meshes.size() || !v || !nrm) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+    Mesh& m = meshes[mesh];
+    if (nv != (int)(m.verts.size() / 3)) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+    for (int i = 0; i < nv; ++i)
+      for (int k = 0; k < 3; ++k) {
+        const float x = v[(size_t)i * 3 + k];
+        if (!(x >= m.bbmin[k] && x <= m.bbmax[k])) return mcpt_err_bare(MCPT_ERR_BAD_SCENE);
+      }
+    m.verts.assign(v, v + (size_t)nv * 3);
+    m.normals.assign(nrm, nrm + (size_t)nv * 3);
+    const int n_leaf = 1 << m.depth;
+    if (m.depth == 0) {   // one triangle, leaf id -1 (kd_build): the root is its box
+      tri_box(m, 0, &m.nodes[0]);
+      return MCPT_OK;
+    }
+    for (int k = 0; k < n_leaf; ++k)
+      if (m.leaves[k] >= 0) tri_box(m, m.leaves[k], &m.nodes[(size_t)(n_leaf - 1 + k) * 6]);
+    for (int k = 0; k < n_leaf; ++k)
+      if (m.leaves[k] < 0 && m.leaves[k ^ 1] >= 0)
+        std::memcpy(&m.nodes[(size_t)(n_leaf - 1 + k) * 6], &m.nodes[(size_t)(n_leaf - 1 + (k ^ 1)) * 6], 24);
+    merge_up(m.nodes);
+    return MCPT_OK;
+  }
+
   // ScenePrimitives::add_mesh: transfo = trf · BB.matrix(), inverse = trf^-1, mesh transfo = trf,
   // type (0, mesh line) — the mesh id here; area 0
   int place_mesh(int mesh, const Mat4& trf, const Material& mat) {
@@ -335,7 +366,13 @@ static void kd_build(const std::vector<Vec3>& centre, const std::vector<float>& 
       leaves[leaf - 1] = order[first]; put(node - 1, order[first]);
     }
   }
-  for (int k = n_node - 1; k >= 2; k -= 2) {   // merge (scene.cpp:91-100)
+  merge_up(nodes);
+}
+
+// internal boxes from the leaf boxes, bottom-up (scene.cpp:91-100): kd_build's and update_mesh's
+static void merge_up(std::vector<float>& nodes) {
+  const int n_node = (int)(nodes.size() / 6);
+  for (int k = n_node - 1; k >= 2; k -= 2) {
     float* parent = &nodes[(size_t)((k - 2) / 2) * 6];
     const float* c1 = &nodes[(size_t)k * 6];
     const float* c2 = &nodes[(size_t)(k - 1) * 6];
@@ -594,6 +631,19 @@ int mcpt_scene_place_mesh(mcpt_scene* s, int mesh_id, const float* trf16, const 
   Mat4 t; Material m;
   if (!s || !unpack(trf16, m7, t, m)) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
   return s->s.place_mesh(mesh_id, t, m) >= 0 ? MCPT_OK : MCPT_ERR_INVALID_ARG;
+}
+int mcpt_scene_update_mesh(mcpt_scene* s, int mesh_id, const float* vertices, const float* normals, int n_vertices) {
+  if (!s) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  return s->s.update_mesh(mesh_id, vertices, normals, n_vertices);
+}
+int mcpt_scene_mesh_vertex_range(mcpt_scene* s, int mesh_id, int* first_vertex, int* n_vertices) {
+  if (!s || mesh_id < 0 || mesh_id >= (int)s->s.meshes.size() || !first_vertex || !n_vertices)
+    return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  int vo = 0;
+  for (int k = 0; k < mesh_id; ++k) vo += (int)(s->s.meshes[k].verts.size() / 3);
+  *first_vertex = vo;
+  *n_vertices = (int)(s->s.meshes[mesh_id].verts.size() / 3);
+  return MCPT_OK;
 }
 int mcpt_scene_mesh_sizes(mcpt_scene* s, int* n_meshes, int* n_nodes, int* n_leaves, int* n_tris, int* n_verts) {
   if (!s || !n_meshes || !n_nodes || !n_leaves || !n_tris || !n_verts) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);

@@ -129,6 +129,12 @@ class AdaptiveCheckpoint(ctypes.Structure):
                 ("emap_valid", ctypes.c_int), ("n_blocks", ctypes.c_int), ("blocks_x", ctypes.c_int)]
 
 
+class Refit(ctypes.Structure):
+    """mcpt_refit_t (include/mcpt.h): what a mesh refit wrote, its device time and the new root box."""
+    _fields_ = [("triangles", ctypes.c_longlong), ("leaves", ctypes.c_longlong), ("internal_nodes", ctypes.c_longlong),
+                ("device_ms", ctypes.c_float), ("has_root", ctypes.c_int), ("root_box", ctypes.c_float * 6)]
+
+
 class Hit(ctypes.Structure):
     """mcpt_hit (include/mcpt.h): one ray-query result."""
     _fields_ = [("shape", ctypes.c_int), ("prim", ctypes.c_int), ("dir", ctypes.c_int), ("dist", ctypes.c_float),
@@ -210,6 +216,13 @@ def _declare(L: ctypes.CDLL) -> None:
         "mcpt_scene_mesh_sizes": (i, [_vp, ip, ip, ip, ip, ip]),
         "mcpt_scene_get_mesh_buffers": (i, [_vp, ip, fp, ip, ip, fp, fp]),
         "mcpt_upload_meshes": (i, [_vp, i, ip, i, fp, i, ip, i, ip, i, fp, fp]),
+        "mcpt_scene_update_mesh": (i, [_vp, i, fp, fp, i]),
+        "mcpt_scene_mesh_vertex_range": (i, [_vp, i, ip, ip]),
+        "mcpt_update_mesh_vertices": (i, [_vp, i, i, fp, fp]),
+        "mcpt_update_mesh_vertices_device": (i, [_vp, i, i, _vp, _vp]),
+        "mcpt_refit_mesh": (i, [_vp, i, ctypes.POINTER(Refit)]),
+        "mcpt_debug_mesh_record_sizes": (i, [_vp, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t)]),
+        "mcpt_debug_mesh_records": (i, [_vp, fp, ctypes.c_size_t, fp, ctypes.c_size_t]),
         "mcpt_set_flat_face": (i, [_vp, i]),
         "mcpt_scene_nb_prim": (i, [_vp, ip]),
         "mcpt_scene_depth": (i, [_vp, ip]),
@@ -429,6 +442,22 @@ class Scene:
         t = _f32(self._colmajor(trf), 16)
         m = _f32(mat, 7)
         _check(lib().mcpt_scene_place_mesh(self._h, int(mesh_id), _fp(t), _fp(m)), "mcpt_scene_place_mesh")
+
+    def update_mesh(self, mesh_id: int, vertices, normals) -> None:
+        """mcpt_scene_update_mesh: new vertices and normals for mesh `mesh_id` (same triangles, depth and
+        leaves) and its BVH boxes refitted; every vertex inside the bb the mesh was added with."""
+        v = np.ascontiguousarray(np.asarray(vertices, np.float32).reshape(-1, 3))
+        n = np.ascontiguousarray(np.asarray(normals, np.float32).reshape(-1, 3))
+        if n.shape != v.shape:
+            raise ValueError("one normal per vertex")
+        _check(lib().mcpt_scene_update_mesh(self._h, int(mesh_id), _fp(v), _fp(n), v.shape[0]), "mcpt_scene_update_mesh")
+
+    def mesh_vertex_range(self, mesh_id: int) -> Tuple[int, int]:
+        """(first vertex, vertex count) of mesh `mesh_id` in mesh_buffers()'s verts / normals."""
+        first, n = ctypes.c_int(), ctypes.c_int()
+        _check(lib().mcpt_scene_mesh_vertex_range(self._h, int(mesh_id), ctypes.byref(first), ctypes.byref(n)),
+               "mcpt_scene_mesh_vertex_range")
+        return first.value, n.value
 
     def mesh_buffers(self):
         """dict of the flat mesh buffers (mcpt_scene_get_mesh_buffers layouts), or None."""
@@ -721,6 +750,54 @@ class Renderer:
         _check(lib().mcpt_upload_meshes(self._h, info.shape[0], _ip(info), nodes.shape[0], _fp(nodes), leaves.size,
                                         _ip(leaves), tris.shape[0], _ip(tris), verts.shape[0], _fp(verts),
                                         _fp(norms)), "mcpt_upload_meshes")
+
+    def update_mesh_vertices(self, first: int, verts, normals) -> None:
+        """New positions and normals (n x 3 f32 each) over the uploaded vertices first .. first + n
+        (Scene.mesh_vertex_range): numpy arrays (mcpt_update_mesh_vertices), or two torch tensors on
+        this renderer's device (mcpt_update_mesh_vertices_device; the torch stream that wrote them is
+        waited for here).  Follow it with refit_mesh."""
+        if hasattr(verts, "data_ptr") and hasattr(normals, "data_ptr"):
+            import torch
+            if not (verts.is_cuda and normals.is_cuda) or verts.dtype != torch.float32 or normals.dtype != torch.float32:
+                raise ValueError("update_mesh_vertices: float32 tensors on the device, or numpy arrays")
+            v, n = verts.reshape(-1, 3).contiguous(), normals.reshape(-1, 3).contiguous()
+            if n.shape != v.shape:
+                raise ValueError("one normal per vertex")
+            torch.cuda.current_stream(v.device).synchronize()
+            self._vertex_src = (v, n)   # (kept until the next update: the queued kernel still reads them)
+            _check(lib().mcpt_update_mesh_vertices_device(self._h, int(first), v.shape[0], _vp(v.data_ptr()),
+                                                          _vp(n.data_ptr())), "mcpt_update_mesh_vertices_device")
+            return
+        v = np.ascontiguousarray(np.asarray(verts, np.float32).reshape(-1, 3))
+        n = np.ascontiguousarray(np.asarray(normals, np.float32).reshape(-1, 3))
+        if n.shape != v.shape:
+            raise ValueError("one normal per vertex")
+        _check(lib().mcpt_update_mesh_vertices(self._h, int(first), v.shape[0], _fp(v), _fp(n)),
+               "mcpt_update_mesh_vertices")
+
+    def refit_mesh(self, mesh_id: int = -1, record: bool = True) -> Optional[dict]:
+        """mcpt_refit_mesh: the BVH records of mesh `mesh_id` (-1: every mesh) rewritten on the device from
+        the current vertices.  record=True waits and returns {triangles, leaves, internal_nodes,
+        device_ms, root_box (a single mesh of depth >= 1, else None)}; record=False queues it only."""
+        if not record:
+            _check(lib().mcpt_refit_mesh(self._h, int(mesh_id), None), "mcpt_refit_mesh")
+            return None
+        rec = Refit()
+        _check(lib().mcpt_refit_mesh(self._h, int(mesh_id), ctypes.byref(rec)), "mcpt_refit_mesh")
+        return {"triangles": rec.triangles, "leaves": rec.leaves, "internal_nodes": rec.internal_nodes,
+                "device_ms": rec.device_ms,
+                "root_box": np.array(rec.root_box[:], np.float32) if rec.has_root else None}
+
+    def mesh_records(self) -> dict:
+        """mcpt_debug_mesh_records: {"pairs": (slots, 4, 4) f32, "leaves": (leaves, 4, 4) f32}, the device's
+        child-pair slots and leaf triangle records as they stand (diagnostics; synchronizes)."""
+        np_, nl = ctypes.c_size_t(), ctypes.c_size_t()
+        _check(lib().mcpt_debug_mesh_record_sizes(self._h, ctypes.byref(np_), ctypes.byref(nl)),
+               "mcpt_debug_mesh_record_sizes")
+        pairs, leaves = np.zeros(np_.value, np.float32), np.zeros(nl.value, np.float32)
+        _check(lib().mcpt_debug_mesh_records(self._h, _fp(pairs), pairs.size, _fp(leaves), leaves.size),
+               "mcpt_debug_mesh_records")
+        return {"pairs": pairs.reshape(-1, 4, 4), "leaves": leaves.reshape(-1, 4, 4)}
 
     def set_flat_face(self, flat: bool) -> None:
         _check(lib().mcpt_set_flat_face(self._h, int(bool(flat))), "mcpt_set_flat_face")
