@@ -154,6 +154,34 @@ int mcpt_update_mesh_vertices(mcpt_ctx* ctx, int first_vertex, int n_vertices, c
 int mcpt_update_mesh_vertices_device(mcpt_ctx* ctx, int first_vertex, int n_vertices, const void* verts_dev,
                                      const void* normals_dev);
 int mcpt_refit_mesh(mcpt_ctx* ctx, int mesh_id, mcpt_refit_t* out);
+/* Rebuild of the uploaded mesh mesh_id's BVH on the device: a new leaf order from
+ * the current vertices by segmented stable radix sorts of the triangle centres (depth - 1 rounds),
+ * the triangle ids into the leaf records, then mcpt_refit_mesh's stages — the bits
+ * mcpt_upload_meshes writes from the buffers of a mcpt_scene_rebuild_mesh with the same vertices
+ * and triangles.  mesh_id == -1: every mesh, and only with tris == NULL.  tris: n_tris x 3
+ * mesh-local vertex indices that replace the mesh's triangle rows first (n_tris must be the mesh's
+ * count, every index below its vertex count, else MCPT_ERR_INVALID_ARG).  The flat arrays of
+ * mcpt_upload_meshes do not say where a mesh's vertices begin: mcpt_set_mesh_vertex_counts gives the
+ * context each mesh's vertex count, in mesh order (mcpt_scene_mesh_vertex_range; the counts add up
+ * to the uploaded vertices and every mesh's triangles lie inside its range, else
+ * MCPT_ERR_INVALID_ARG), once after an upload; without it a rebuild with tris is MCPT_ERR_BAD_SCENE
+ * (the Python and C++ upload_scene make the call).  Ordering, state and refusals are
+ * mcpt_refit_mesh's: the context's stream behind every queued render, no host wait unless `out` is
+ * given, guides invalid and temporal history emptied, everything else kept; MCPT_ERR_BAD_SCENE with
+ * no meshes, for a mesh uploaded with an all-empty leaf pair or with a depth other than
+ * ceil(log2(triangles)); MCPT_ERR_INVALID_ARG for an unknown id; the records and triangles stay
+ * as they are then.  A mesh of depth 0 has no order: with tris only its triangle row changes. */
+typedef struct mcpt_rebuild_t {
+  long long triangles;        /* triangles sorted (meshes of depth >= 2) */
+  int rounds;                 /* segmented sort rounds run (depth - 1 per mesh) */
+  int sort_passes;            /* radix passes launched (8 bits each) */
+  float sort_ms;              /* triangle rows, centres, the sort and the leaf ids, from HIP events */
+  float refit_ms;             /* the refit stages, from HIP events */
+  int has_root;               /* 1: root_box is set (a single mesh of depth >= 1) */
+  float root_box[6];          /* the mesh's new root box (min.xyz, max.xyz), mesh space */
+} mcpt_rebuild_t;
+int mcpt_rebuild_mesh(mcpt_ctx* ctx, int mesh_id, const int* tris, int n_tris, mcpt_rebuild_t* out);
+int mcpt_set_mesh_vertex_counts(mcpt_ctx* ctx, int n_meshes, const int* counts);
 /* Diagnostics: the device's mesh BVH records as they stand — the child-pair slots (4 x 4 f32 per
  * slot: (c_left, has) (w_left, in_range) (c_right, has) (w_right, 0); each mesh's run starts at an
  * even slot, internal node i at slot i + 1 of the run) and the leaf triangle records (4 x 4 f32 per
@@ -968,6 +996,20 @@ int mcpt_scene_get_mesh_buffers(mcpt_scene* s, int* info, float* nodes, int* lea
  * silently — MCPT_ERR_BAD_SCENE then, and nothing changes.  The scene stays finalized; its prims,
  * nodes and leaves are untouched.  This is the specification of mcpt_refit_mesh. */
 int mcpt_scene_update_mesh(mcpt_scene* s, int mesh_id, const float* vertices, const float* normals, int n_vertices);
+/* Rebuild of mesh mesh_id's tree from its current vertices (no reference equivalent; DESIGN.md
+ * §3.12).  tris == NULL keeps the triangles; otherwise n_tris x 3 mesh-local vertex indices replace
+ * them (n_tris must be the mesh's count and every index below its vertex count, else
+ * MCPT_ERR_INVALID_ARG and nothing changes), so every buffer size and the depth stay.  The leaves
+ * come from a builder with add_mesh's shape (depth, mid = (lo + hi) / 2, axes x, y, z in turn over
+ * depth - 1 rounds) and a defined order: `order` starts 0 .. n-1 and every round stable-sorts each
+ * of its ranges by the triangle boxes' centre on the round's axis (float `<`; equal keys, -0 and +0
+ * among them, keep their order); range s of the last round gives leaves 2s and 2s + 1 (the second
+ * -1 for a range of one).  With pairwise distinct keys every internal node holds the triangles
+ * add_mesh's tree holds there.  The boxes are then written as mcpt_scene_update_mesh writes them.
+ * A mesh of depth 0 has no order: only its triangle row and box follow `tris`.  Mesh::BB() and the
+ * instances' boxes do not move; the scene stays finalized.  MCPT_ERR_INVALID_ARG for an unknown
+ * mesh.  This is the specification of mcpt_rebuild_mesh. */
+int mcpt_scene_rebuild_mesh(mcpt_scene* s, int mesh_id, const unsigned* tris, int n_tris);
 /* mesh mesh_id's range in the flat verts / normals arrays of mcpt_scene_get_mesh_buffers */
 int mcpt_scene_mesh_vertex_range(mcpt_scene* s, int mesh_id, int* first_vertex, int* n_vertices);
 /* sortEmissiveFirst + BVH_KDtree::compute (scene.cpp:70-88, bvh.cpp:34-93) */

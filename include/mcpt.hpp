@@ -242,6 +242,12 @@ class BVH_GPU_Scene {
       throw Error("update_mesh (mesh needs vertices and one normal per vertex)", MCPT_ERR_INVALID_ARG);
     check(mcpt_scene_update_mesh(s(), i, m->vertices_[0].v, m->normals_[0].v, m->nb_vertices()), "mcpt_scene_update_mesh");
   }
+  // mesh i's tree rebuilt from its current vertices by stable median splits (mcpt_scene_rebuild_mesh);
+  // tris (3 mesh-local vertex indices per triangle, the mesh's count) replaces its triangles first
+  void rebuild_mesh(int i, const std::vector<unsigned>* tris = nullptr) {
+    check(mcpt_scene_rebuild_mesh(s(), i, tris ? tris->data() : nullptr, tris ? (int)(tris->size() / 3) : 0),
+          "mcpt_scene_rebuild_mesh");
+  }
   // mesh i's first vertex in the flat vertex arrays (Renderer::update_mesh_vertices)
   int mesh_first_vertex(int i) const {
     int first = 0, n = 0;
@@ -369,6 +375,10 @@ class Renderer {
       check(mcpt_upload_meshes(c_, nm, info.data(), nn, nodes.data(), nl, leaves.data(), nt, tris.data(), nv,
                                verts.data(), norms.data()),
             "mcpt_upload_meshes");
+      std::vector<int> counts((size_t)nm);   // (where each mesh's vertices lie: rebuild_mesh with new triangles)
+      for (int m = 0, first = 0; m < nm; ++m)
+        check(mcpt_scene_mesh_vertex_range(sc.handle(), m, &first, &counts[m]), "mcpt_scene_mesh_vertex_range");
+      check(mcpt_set_mesh_vertex_counts(c_, nm, counts.data()), "mcpt_set_mesh_vertex_counts");
     }
   }
   // deforming meshes (mcpt.h): n x 3 positions and normals over the uploaded vertices from `first`
@@ -385,6 +395,14 @@ class Renderer {
   mcpt_refit_t refit_mesh(int i = -1, bool want_record = true) {
     mcpt_refit_t rec{};
     check(mcpt_refit_mesh(c_, i, want_record ? &rec : nullptr), "mcpt_refit_mesh");
+    return rec;
+  }
+  // mesh i's BVH (-1: every mesh's, without tris) rebuilt on the device: a new leaf order from the
+  // current vertices, then the refit (mcpt_rebuild_mesh); tris as BVH_GPU_Scene::rebuild_mesh's
+  mcpt_rebuild_t rebuild_mesh(int i = -1, const std::vector<int>* tris = nullptr, bool want_record = true) {
+    mcpt_rebuild_t rec{};
+    check(mcpt_rebuild_mesh(c_, i, tris ? tris->data() : nullptr, tris ? (int)(tris->size() / 3) : 0,
+                            want_record ? &rec : nullptr), "mcpt_rebuild_mesh");
     return rec;
   }
   // the reference's own arrays, as BVH_GPU_Scene::finalize hands them to its textures:

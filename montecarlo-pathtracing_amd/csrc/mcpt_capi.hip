@@ -399,6 +399,18 @@ int mcpt_upload_meshes(mcpt_ctx* c, int n_meshes, const int* info, int n_nodes, 
   ms.n_meshes = n_meshes;
   ms.info = std::move(hi); ms.leaf_tris = std::move(leaf_tris); ms.empty_pair = std::move(empty_pair);
   ms.n_pair_f4 = hn.size(); ms.n_leaf_f4 = hl.size();
+  // a rebuild's view (mcpt_rebuild.hip): each mesh's triangle count and the vertex ids its triangles
+  // use; its vertex range is not known until mcpt_set_mesh_vertex_counts tells it (count 0)
+  ms.n_tris.resize(n_meshes); ms.vert_lo.assign(n_meshes, n_verts); ms.vert_hi.assign(n_meshes, 0);
+  ms.vert_first.assign(n_meshes, 0); ms.vert_count.assign(n_meshes, 0);
+  for (int m = 0; m < n_meshes; ++m) {
+    const int to = info[4 * m + 3];
+    ms.n_tris[m] = (m + 1 < n_meshes ? info[4 * (m + 1) + 3] : n_tris) - to;
+    for (int t = to; t < to + ms.n_tris[m]; ++t) {
+      ms.vert_lo[m] = std::min(ms.vert_lo[m], std::min(ht[t].x, std::min(ht[t].y, ht[t].z)));
+      ms.vert_hi[m] = std::max(ms.vert_hi[m], std::max(ht[t].x, std::max(ht[t].y, ht[t].z)));
+    }
+  }
   c->meshes = std::move(ms);
   return MCPT_OK;
 }

@@ -108,6 +108,17 @@ struct mcpt_ctx {
     DevBuf<float4> d_refit_scratch; // subtree roots between a refit's stages: sized at the first refit
     DevBuf<float> d_vert_staging;   // mcpt_update_mesh_vertices: the host arrays on their way
     Event refit_ev[2];              // around the last refit that asked for its record
+    // what a rebuild (mcpt_rebuild.hip) needs of the upload: per mesh its triangle
+    // count, the smallest and largest vertex id its triangles use, and its vertex range (first,
+    // count; count 0 until mcpt_set_mesh_vertex_counts); the sort's scratch, sized at the first
+    // rebuild for the largest mesh
+    std::vector<int> n_tris, vert_lo, vert_hi, vert_first, vert_count;
+    DevBuf<unsigned> d_sort_ckey;   // 3 x n: the centre keys per axis, by triangle id
+    DevBuf<unsigned long long> d_sort_key;   // n: (range << 32) | axis key of the round, by triangle id
+    DevBuf<int> d_sort_ids[2];      // the order, ping-pong
+    DevBuf<unsigned> d_sort_hist;   // 256 digits x workgroups, digit-major
+    DevBuf<int> d_tri_staging;      // mcpt_rebuild_mesh: the host's triangle rows on their way
+    Event rebuild_ev[3];            // start / sort end / refit end of the last rebuild that asked for its record
   } meshes;
   int flat_face = 0;
   std::vector<int> mesh_ids;     // per primitive: mesh id of a CODE_MESH record, else -1
@@ -286,6 +297,24 @@ void scene_params(const mcpt_ctx* c, const float* invPV, const float* invV, mcpt
 void pass_params(int first_pass, int n_passes, float date, int bounces, float refract_ind, int variant,
                  mcpt::RenderParams& p);
 int checked_sub_launch(mcpt_ctx* c, int k, int n_sub, const mcpt::RenderParams& p);
+// mcpt_refit.hip: what a refit and a rebuild (mcpt_rebuild.hip) share — the refusals and the scratch
+// for meshes m0 .. m1 - 1 (`who`: the caller's name, for the detail), the refit stages of mesh m
+// queued on the context's stream (*root: its root's {min, has} {max, 0} on the device, untouched for
+// a mesh of depth 0), and the state a change of geometry behind the queued renders leaves
+#if defined(__HIPCC__)
+// std::min(a, b) / std::max(a, b): the first operand unless the comparison says otherwise
+__device__ __forceinline__ float min_ab(float a, float b) { return b < a ? b : a; }
+__device__ __forceinline__ float max_ab(float a, float b) { return a < b ? b : a; }
+// SceneMesh::prim_bb as the host's tri_box evaluates it (std::min / std::max over {A, B, C}, then -+ 0.001)
+__device__ __forceinline__ void tri_box_dev(const float4 A, const float4 B, const float4 C, float mn[3], float mx[3]) {
+  mn[0] = min_ab(min_ab(A.x, B.x), C.x) - 0.001f; mx[0] = max_ab(max_ab(A.x, B.x), C.x) + 0.001f;
+  mn[1] = min_ab(min_ab(A.y, B.y), C.y) - 0.001f; mx[1] = max_ab(max_ab(A.y, B.y), C.y) + 0.001f;
+  mn[2] = min_ab(min_ab(A.z, B.z), C.z) - 0.001f; mx[2] = max_ab(max_ab(A.z, B.z), C.z) + 0.001f;
+}
+#endif
+int refit_prepare(mcpt_ctx* c, int mesh_id, const char* who, int& m0, int& m1);
+int refit_launch(mcpt_ctx* c, int m, const float4** root);
+void geometry_changed(mcpt_ctx* c);
 // mcpt_capi_post.hip: one batch of the noise statistics behind the last combine (d_count: the counted
 // twin of a queued adaptive run, reading the list's length there; timed false: no events)
 hipError_t stats_batch(mcpt_ctx* c, int n, const int* d_count = nullptr, bool timed = true);

@@ -24,10 +24,6 @@ namespace {
 constexpr int kRefitK = 8;                    // levels a stage walks up
 constexpr int kRefitThreads = 1 << kRefitK;   // ... and its workgroup
 
-// std::min(a, b) / std::max(a, b): the first operand unless the comparison says otherwise
-__device__ __forceinline__ float min_ab(float a, float b) { return b < a ? b : a; }
-__device__ __forceinline__ float max_ab(float a, float b) { return a < b ? b : a; }
-
 struct RefitStage {
   float4* pairs;         // the mesh's pair slots (its slot 0)
   float4* leafrec;       // the mesh's leaf records
@@ -64,12 +60,9 @@ __global__ __launch_bounds__(kRefitThreads) void refit_stage_kernel(RefitStage p
     int t = -1;
     if (live) t = __float_as_int(p.leafrec[(size_t)g * 4].w);
     if (t >= 0) {
-      // SceneMesh::prim_bb as tri_box evaluates it (std::min / std::max over {A, B, C}, then -+ 0.001)
       const int4 vi = p.tris[t];
       const float4 A = p.verts[vi.x], B = p.verts[vi.y], C = p.verts[vi.z];
-      mn[0] = min_ab(min_ab(A.x, B.x), C.x) - 0.001f; mx[0] = max_ab(max_ab(A.x, B.x), C.x) + 0.001f;
-      mn[1] = min_ab(min_ab(A.y, B.y), C.y) - 0.001f; mx[1] = max_ab(max_ab(A.y, B.y), C.y) + 0.001f;
-      mn[2] = min_ab(min_ab(A.z, B.z), C.z) - 0.001f; mx[2] = max_ab(max_ab(A.z, B.z), C.z) + 0.001f;
+      tri_box_dev(A, B, C, mn, mx);
       has = 1.0f;
       float4* r = p.leafrec + (size_t)g * 4;
       r[0] = make_float4(A.x, A.y, A.z, __int_as_float(t));
@@ -146,15 +139,6 @@ unsigned stage_groups(int lev) { return lev > kRefitK ? 1u << (lev - kRefitK) : 
 size_t scratch_half_a(int d) { return 2 * (size_t)stage_groups(d); }
 size_t scratch_half_b(int d) { return 2 * (size_t)stage_groups(std::max(d - kRefitK, 0)); }
 
-// the geometry changed behind the queued renders: what was derived from it is stale, and the render
-// lanes' next launches must wait for the context's stream again (LaneSeq::used_in_order)
-void geometry_changed(mcpt_ctx* c) {
-  c->denoise.guides_valid = false;
-  c->temporal.tp_frames = 0;
-  c->seq.used_in_order(0);
-  c->seq.used_in_order(1);
-}
-
 int update_vertices(mcpt_ctx* c, int first, int n, const float* d_v, const float* d_n) {
   if (n == 0) return MCPT_OK;
   widen_vertices_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream>>>(
@@ -179,6 +163,70 @@ int check_vertex_range(const mcpt_ctx* c, int first, int n, const void* v, const
 }
 
 }  // namespace
+
+// the geometry changed behind the queued renders: what was derived from it is stale, and the render
+// lanes' next launches must wait for the context's stream again (LaneSeq::used_in_order)
+void geometry_changed(mcpt_ctx* c) {
+  c->denoise.guides_valid = false;
+  c->temporal.tp_frames = 0;
+  c->seq.used_in_order(0);
+  c->seq.used_in_order(1);
+}
+
+int refit_prepare(mcpt_ctx* c, int mesh_id, const char* who, int& m0, int& m1) {
+  char what[96];
+  if (!c) {
+    std::snprintf(what, sizeof(what), "%s: bad arguments", who);
+    return set_err(MCPT_ERR_INVALID_ARG, what);
+  }
+  mcpt_ctx::Meshes& ms = c->meshes;
+  if (ms.n_meshes == 0) return set_err(MCPT_ERR_BAD_SCENE, "no meshes uploaded");
+  if (mesh_id < -1 || mesh_id >= ms.n_meshes) {
+    std::snprintf(what, sizeof(what), "%s: no such mesh", who);
+    return set_err(MCPT_ERR_INVALID_ARG, what);
+  }
+  m0 = mesh_id < 0 ? 0 : mesh_id; m1 = mesh_id < 0 ? ms.n_meshes : mesh_id + 1;
+  size_t half_a = 2, half_b = 2;
+  for (int m = m0; m < m1; ++m) {
+    if (ms.empty_pair[m]) {
+      std::snprintf(what, sizeof(what), "%s: a leaf pair of the mesh holds no triangle", who);
+      return set_err(MCPT_ERR_BAD_SCENE, what);
+    }
+    half_a = std::max(half_a, scratch_half_a(ms.info[m].z));
+    half_b = std::max(half_b, scratch_half_b(ms.info[m].z));
+  }
+  HIP_OR_RETURN(hipSetDevice(c->device));
+  if (half_a + half_b > ms.d_refit_scratch.size()) {
+    HIP_OR_RETURN(hipStreamSynchronize(c->stream));   // (an earlier refit of a shallower mesh may still use it)
+    HIP_OR_RETURN(ms.d_refit_scratch.alloc(half_a + half_b));
+  }
+  return MCPT_OK;
+}
+
+int refit_launch(mcpt_ctx* c, int m, const float4** root) {
+  mcpt_ctx::Meshes& ms = c->meshes;
+  const int4 mi = ms.info[m];   // (first pair slot, first leaf, depth, first triangle)
+  if (mi.z == 0) return MCPT_OK;   // one triangle in a leaf with id -1: no records
+  float4* const half[2] = {ms.d_refit_scratch, ms.d_refit_scratch + std::max<size_t>(2, scratch_half_a(mi.z))};
+  RefitStage p;
+  p.pairs = ms.d_mpairs + (size_t)mi.x * 4;
+  p.leafrec = ms.d_mleaftris + (size_t)mi.y * 4;
+  p.tris = ms.d_mtris + mi.w;
+  p.verts = ms.d_mverts;
+  p.in = nullptr;
+  int side = 0;
+  for (int lev = mi.z; lev > 0; side ^= 1) {
+    p.lev = lev; p.up = std::min(kRefitK, lev); p.out = half[side];
+    const dim3 grid(stage_groups(lev)), block(kRefitThreads);
+    if (lev == mi.z) refit_stage_kernel<true><<<grid, block, 0, c->stream>>>(p);
+    else refit_stage_kernel<false><<<grid, block, 0, c->stream>>>(p);
+    HIP_OR_RETURN(hipGetLastError());
+    lev -= p.up;
+    p.in = p.out;
+  }
+  *root = p.in;
+  return MCPT_OK;
+}
 
 extern "C" {
 
@@ -205,23 +253,9 @@ int mcpt_update_mesh_vertices(mcpt_ctx* c, int first_vertex, int n_vertices, con
 }
 
 int mcpt_refit_mesh(mcpt_ctx* c, int mesh_id, mcpt_refit_t* out) {
-  if (!c) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_refit_mesh: bad arguments");
+  int m0 = 0, m1 = 0;
+  OK_OR_RETURN(refit_prepare(c, mesh_id, "mcpt_refit_mesh", m0, m1));
   mcpt_ctx::Meshes& ms = c->meshes;
-  if (ms.n_meshes == 0) return set_err(MCPT_ERR_BAD_SCENE, "no meshes uploaded");
-  if (mesh_id < -1 || mesh_id >= ms.n_meshes) return set_err(MCPT_ERR_INVALID_ARG, "mcpt_refit_mesh: no such mesh");
-  const int m0 = mesh_id < 0 ? 0 : mesh_id, m1 = mesh_id < 0 ? ms.n_meshes : mesh_id + 1;
-  size_t half_a = 2, half_b = 2;
-  for (int m = m0; m < m1; ++m) {
-    if (ms.empty_pair[m]) return set_err(MCPT_ERR_BAD_SCENE, "mcpt_refit_mesh: a leaf pair of the mesh holds no triangle");
-    half_a = std::max(half_a, scratch_half_a(ms.info[m].z));
-    half_b = std::max(half_b, scratch_half_b(ms.info[m].z));
-  }
-  HIP_OR_RETURN(hipSetDevice(c->device));
-  if (half_a + half_b > ms.d_refit_scratch.size()) {
-    HIP_OR_RETURN(hipStreamSynchronize(c->stream));   // (an earlier refit of a shallower mesh may still use it)
-    HIP_OR_RETURN(ms.d_refit_scratch.alloc(half_a + half_b));
-  }
-  float4* const half[2] = {ms.d_refit_scratch, ms.d_refit_scratch + half_a};
   if (out) {
     std::memset(out, 0, sizeof(*out));
     HIP_OR_RETURN(ensure_timing_events(ms.refit_ev, 2));
@@ -230,26 +264,10 @@ int mcpt_refit_mesh(mcpt_ctx* c, int mesh_id, mcpt_refit_t* out) {
   long long n_tris = 0, n_leaves = 0, n_internal = 0;
   const float4* root = nullptr;
   for (int m = m0; m < m1; ++m) {
-    const int4 mi = ms.info[m];   // (first pair slot, first leaf, depth, first triangle)
-    if (mi.z == 0) continue;      // one triangle in a leaf with id -1: no records
-    RefitStage p;
-    p.pairs = ms.d_mpairs + (size_t)mi.x * 4;
-    p.leafrec = ms.d_mleaftris + (size_t)mi.y * 4;
-    p.tris = ms.d_mtris + mi.w;
-    p.verts = ms.d_mverts;
-    p.in = nullptr;
-    int side = 0;
-    for (int lev = mi.z; lev > 0; side ^= 1) {
-      p.lev = lev; p.up = std::min(kRefitK, lev); p.out = half[side];
-      const dim3 grid(stage_groups(lev)), block(kRefitThreads);
-      if (lev == mi.z) refit_stage_kernel<true><<<grid, block, 0, c->stream>>>(p);
-      else refit_stage_kernel<false><<<grid, block, 0, c->stream>>>(p);
-      HIP_OR_RETURN(hipGetLastError());
-      lev -= p.up;
-      p.in = p.out;
-    }
-    root = p.in;
-    n_tris += ms.leaf_tris[m]; n_leaves += 1LL << mi.z; n_internal += (1LL << mi.z) - 1;
+    const int d = ms.info[m].z;
+    if (d == 0) continue;
+    OK_OR_RETURN(refit_launch(c, m, &root));
+    n_tris += ms.leaf_tris[m]; n_leaves += 1LL << d; n_internal += (1LL << d) - 1;
   }
   geometry_changed(c);
   if (!out) return MCPT_OK;

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/mcpt.h"
+#include "mcpt_rebuild_plan.h"
 
 // mcpt_capi.hip: an error return without a detail (drops the thread's unread detail)
 int mcpt_err_bare(int status);
@@ -116,6 +117,7 @@ static Vec3 apply_pt(const Mat4& t, float x, float y, float z) {
 static void kd_build(const std::vector<Vec3>& centre, const std::vector<float>& box, int& depth,
                      std::vector<float>& nodes, std::vector<int>& leaves);
 static void merge_up(std::vector<float>& nodes);
+static void kd_build_stable(const std::vector<Vec3>& centre, int depth, std::vector<int>& leaves);
 
 // PrimData record (scene.h:64-73) + the BVH built over the records
 class PrimScene {
@@ -288,10 +290,16 @@ class PrimScene {
       }
     m.verts.assign(v, v + (size_t)nv * 3);
     m.normals.assign(nrm, nrm + (size_t)nv * 3);
+    refit_boxes(m);
+    return MCPT_OK;
+  }
+
+  // every box of the mesh from its vertices, triangles and leaves: update_mesh's and rebuild_mesh's
+  static void refit_boxes(Mesh& m) {
     const int n_leaf = 1 << m.depth;
     if (m.depth == 0) {   // one triangle, leaf id -1 (kd_build): the root is its box
       tri_box(m, 0, &m.nodes[0]);
-      return MCPT_OK;
+      return;
     }
     for (int k = 0; k < n_leaf; ++k)
       if (m.leaves[k] >= 0) tri_box(m, m.leaves[k], &m.nodes[(size_t)(n_leaf - 1 + k) * 6]);
@@ -299,6 +307,33 @@ class PrimScene {
       if (m.leaves[k] < 0 && m.leaves[k ^ 1] >= 0)
         std::memcpy(&m.nodes[(size_t)(n_leaf - 1 + k) * 6], &m.nodes[(size_t)(n_leaf - 1 + (k ^ 1)) * 6], 24);
     merge_up(m.nodes);
+  }
+
+  // Rebuild of mesh `mesh`'s tree from its current vertices (no reference equivalent; DESIGN.md
+  // §3.12): optionally new triangle rows (same count, so every buffer size and the depth stay), the
+  // leaves from kd_build_stable, the boxes as update_mesh writes them.  Mesh::BB() and the
+  // instances' scene-level boxes do not move; the scene stays finalized.
+  int rebuild_mesh(int mesh, const uint32_t* t, int nt) {
+    if (mesh < 0 || mesh >= (int)meshes.size()) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+    Mesh& m = meshes[mesh];
+    const int n = (int)(m.tris.size() / 3);
+    if (t) {
+      if (nt != n) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+      const uint32_t nv = (uint32_t)(m.verts.size() / 3);
+      for (size_t i = 0; i < (size_t)n * 3; ++i)
+        if (t[i] >= nv) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+    }
+    if (m.depth != mcpt::rebuild::depth_of(n)) return mcpt_err_bare(MCPT_ERR_BAD_SCENE);   // (not below 2^22 triangles)
+    if (t) m.tris.assign(t, t + (size_t)n * 3);
+    if (m.depth == 0) {
+      if (t) refit_boxes(m);   // (the lone triangle's box follows its row)
+      return MCPT_OK;
+    }
+    std::vector<Vec3> centre(n);
+    float bb[6];
+    for (int i = 0; i < n; ++i) centre[i] = tri_box(m, i, bb);
+    kd_build_stable(centre, m.depth, m.leaves);
+    refit_boxes(m);
     return MCPT_OK;
   }
 
@@ -367,6 +402,35 @@ static void kd_build(const std::vector<Vec3>& centre, const std::vector<float>& 
     }
   }
   merge_up(nodes);
+}
+
+// kd_build's shape and triangle sets with a defined order inside them (the
+// specification of the device rebuild, mcpt_rebuild.hip): the same depth, bounds recursion and axis
+// cycle, but every round stable-sorts each range of `order` by the axis key (float `<`: equal keys,
+// -0 and +0 among them, keep their order) where kd_build leaves nth_element's permutation.  Range s
+// of the last round gives leaves 2s and 2s + 1.  The index arithmetic is mcpt_rebuild_plan.h's.
+static void kd_build_stable(const std::vector<Vec3>& centre, int depth, std::vector<int>& leaves) {
+  namespace rb = mcpt::rebuild;
+  const int n = (int)centre.size();
+  std::vector<int> order(n);
+  for (int i = 0; i < n; ++i) order[i] = i;
+  int axis = 0;
+  for (int round = 1; round < depth; ++round) {
+    auto key = [&](int id) { return axis == 0 ? centre[id].x : (axis == 1 ? centre[id].y : centre[id].z); };
+    for (int s = 0; s < (1 << (round - 1)); ++s) {
+      int lo, hi;
+      rb::range_bounds(n, round - 1, s, lo, hi);
+      std::stable_sort(order.begin() + lo, order.begin() + hi, [&](int a, int b) { return key(a) < key(b); });
+    }
+    axis = (axis + 1) % 3;
+  }
+  leaves.assign((size_t)1 << depth, -1);
+  for (int s = 0; s < (1 << (depth - 1)); ++s) {
+    int first, second;
+    rb::leaf_pair(n, depth, s, first, second);
+    leaves[2 * (size_t)s] = order[first];
+    leaves[2 * (size_t)s + 1] = second >= 0 ? order[second] : -1;
+  }
 }
 
 // internal boxes from the leaf boxes, bottom-up (scene.cpp:91-100): kd_build's and update_mesh's
@@ -635,6 +699,10 @@ int mcpt_scene_place_mesh(mcpt_scene* s, int mesh_id, const float* trf16, const 
 int mcpt_scene_update_mesh(mcpt_scene* s, int mesh_id, const float* vertices, const float* normals, int n_vertices) {
   if (!s) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
   return s->s.update_mesh(mesh_id, vertices, normals, n_vertices);
+}
+int mcpt_scene_rebuild_mesh(mcpt_scene* s, int mesh_id, const unsigned* tris, int n_tris) {
+  if (!s) return mcpt_err_bare(MCPT_ERR_INVALID_ARG);
+  return s->s.rebuild_mesh(mesh_id, tris, n_tris);
 }
 int mcpt_scene_mesh_vertex_range(mcpt_scene* s, int mesh_id, int* first_vertex, int* n_vertices) {
   if (!s || mesh_id < 0 || mesh_id >= (int)s->s.meshes.size() || !first_vertex || !n_vertices)

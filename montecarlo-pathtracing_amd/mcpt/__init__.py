@@ -135,6 +135,13 @@ class Refit(ctypes.Structure):
                 ("device_ms", ctypes.c_float), ("has_root", ctypes.c_int), ("root_box", ctypes.c_float * 6)]
 
 
+class Rebuild(ctypes.Structure):
+    """mcpt_rebuild_t (include/mcpt.h): what a mesh rebuild sorted, its device times and the new root box."""
+    _fields_ = [("triangles", ctypes.c_longlong), ("rounds", ctypes.c_int), ("sort_passes", ctypes.c_int),
+                ("sort_ms", ctypes.c_float), ("refit_ms", ctypes.c_float), ("has_root", ctypes.c_int),
+                ("root_box", ctypes.c_float * 6)]
+
+
 class Hit(ctypes.Structure):
     """mcpt_hit (include/mcpt.h): one ray-query result."""
     _fields_ = [("shape", ctypes.c_int), ("prim", ctypes.c_int), ("dir", ctypes.c_int), ("dist", ctypes.c_float),
@@ -221,6 +228,9 @@ def _declare(L: ctypes.CDLL) -> None:
         "mcpt_update_mesh_vertices": (i, [_vp, i, i, fp, fp]),
         "mcpt_update_mesh_vertices_device": (i, [_vp, i, i, _vp, _vp]),
         "mcpt_refit_mesh": (i, [_vp, i, ctypes.POINTER(Refit)]),
+        "mcpt_scene_rebuild_mesh": (i, [_vp, i, ctypes.POINTER(ctypes.c_uint), i]),
+        "mcpt_rebuild_mesh": (i, [_vp, i, ip, i, ctypes.POINTER(Rebuild)]),
+        "mcpt_set_mesh_vertex_counts": (i, [_vp, i, ip]),
         "mcpt_debug_mesh_record_sizes": (i, [_vp, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t)]),
         "mcpt_debug_mesh_records": (i, [_vp, fp, ctypes.c_size_t, fp, ctypes.c_size_t]),
         "mcpt_set_flat_face": (i, [_vp, i]),
@@ -451,6 +461,17 @@ class Scene:
         if n.shape != v.shape:
             raise ValueError("one normal per vertex")
         _check(lib().mcpt_scene_update_mesh(self._h, int(mesh_id), _fp(v), _fp(n), v.shape[0]), "mcpt_scene_update_mesh")
+
+    def rebuild_mesh(self, mesh_id: int, tris=None) -> None:
+        """mcpt_scene_rebuild_mesh: mesh `mesh_id`'s tree rebuilt from its current vertices by stable median
+        splits (same depth and buffer sizes); tris (n x 3 mesh-local vertex indices, the mesh's count)
+        replaces its triangles first."""
+        if tris is None:
+            _check(lib().mcpt_scene_rebuild_mesh(self._h, int(mesh_id), None, 0), "mcpt_scene_rebuild_mesh")
+            return
+        t = np.ascontiguousarray(np.asarray(tris, np.uint32).reshape(-1, 3))
+        _check(lib().mcpt_scene_rebuild_mesh(self._h, int(mesh_id), t.ctypes.data_as(ctypes.POINTER(ctypes.c_uint)),
+                                             t.shape[0]), "mcpt_scene_rebuild_mesh")
 
     def mesh_vertex_range(self, mesh_id: int) -> Tuple[int, int]:
         """(first vertex, vertex count) of mesh `mesh_id` in mesh_buffers()'s verts / normals."""
@@ -734,6 +755,9 @@ class Renderer:
             mb = scene.mesh_buffers()
             if mb is not None:
                 self.upload_meshes(mb)
+                # (where each mesh's vertices lie: rebuild_mesh with new triangles)
+                counts = np.array([scene.mesh_vertex_range(m)[1] for m in range(len(mb["info"]))], np.int32)
+                _check(lib().mcpt_set_mesh_vertex_counts(self._h, len(counts), _ip(counts)), "mcpt_set_mesh_vertex_counts")
 
     def upload_meshes(self, mb) -> None:
         """mcpt_upload_meshes from a Scene.mesh_buffers() dict (None/empty: no meshes)."""
@@ -786,6 +810,25 @@ class Renderer:
         _check(lib().mcpt_refit_mesh(self._h, int(mesh_id), ctypes.byref(rec)), "mcpt_refit_mesh")
         return {"triangles": rec.triangles, "leaves": rec.leaves, "internal_nodes": rec.internal_nodes,
                 "device_ms": rec.device_ms,
+                "root_box": np.array(rec.root_box[:], np.float32) if rec.has_root else None}
+
+    def rebuild_mesh(self, mesh_id: int = -1, tris=None, record: bool = True) -> Optional[dict]:
+        """mcpt_rebuild_mesh: the BVH of mesh `mesh_id` (-1: every mesh, without tris) rebuilt on the device
+        from the current vertices — a new leaf order by stable median splits, then the refit; tris (n x 3
+        mesh-local vertex indices, the mesh's count) replaces its triangles first.  record=True waits and
+        returns {triangles, rounds, sort_passes, sort_ms, refit_ms, device_ms, root_box (a single mesh of
+        depth >= 1, else None)}; record=False queues it only."""
+        t, tp, nt = None, None, 0
+        if tris is not None:
+            t = np.ascontiguousarray(np.asarray(tris, np.int32).reshape(-1, 3))
+            tp, nt = _ip(t), t.shape[0]
+        if not record:
+            _check(lib().mcpt_rebuild_mesh(self._h, int(mesh_id), tp, nt, None), "mcpt_rebuild_mesh")
+            return None
+        rec = Rebuild()
+        _check(lib().mcpt_rebuild_mesh(self._h, int(mesh_id), tp, nt, ctypes.byref(rec)), "mcpt_rebuild_mesh")
+        return {"triangles": rec.triangles, "rounds": rec.rounds, "sort_passes": rec.sort_passes,
+                "sort_ms": rec.sort_ms, "refit_ms": rec.refit_ms, "device_ms": rec.sort_ms + rec.refit_ms,
                 "root_box": np.array(rec.root_box[:], np.float32) if rec.has_root else None}
 
     def mesh_records(self) -> dict:
